@@ -1,11 +1,16 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X-native CVAE / CGAN hot path on synthetic 512x512 dark-matter -> pressure tiles.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
-HEADLINE (metric / value / config / dtype / roofline of the JSON line): the CVAE fiducial train step (forward +
-backward + Adam), fp32, 64 tiles per GPU -- BASELINE.json configs[1].  The same line carries, as bounded secondary
-legs (their own objects, each with its own roofline; none of them changes the headline fields):
+HEADLINE (metric / value / config / dtype / ms_per_step of the JSON line): the CVAE fiducial train step (forward +
+backward + Adam), fp32, 64 tiles per GPU -- BASELINE.json configs[1].  A plain run sets up, warms up, times the K
+steps and prints the line; nothing else runs.
+  --dump-outputs DIR -- after the timed steps, what the last one computed (ELBO and loss terms, parameters after the
+              update, gradients, seeded samples of the generator's output) as DIR/<name>.npy; same arguments, same inputs.
+  --full   -- also the figures that take runs of their own.  The line then carries the headline's roofline and, as
+              bounded secondary legs (their own objects, each with its own roofline; none of them changes the headline
+              fields):
   "paint" -- configs[4] per GPU: CVAEPainter.paint_stream, raw host tile -> physical host tile, hipGraph forward;
   "bf16"  -- configs[3] per GPU: the same train step with bf16 activations / gradients in the generator trunk
              (+ its own paint leg);
@@ -18,8 +23,9 @@ no WORLD_SIZE in the environment) this script launches that itself as a CHILD pr
 relays rank 0's JSON line.  The batch is sharded data-parallel (weak scaling: 64 tiles per GPU), gradients are
 all-reduced as one flat buffer and batch-norm statistics are all-reduced per layer (global-batch arithmetic).
 Timing: W untimed warm-up steps, then exactly K steps between barrier + synchronize on both sides, MAX over ranks.
-  roofline -- the dominant kernel's achieved rate from HIP events recorded around every launch (on the stream the
-              kernels are launched on) in extra steps of the serial schedule right after the timed region.
+  roofline (--full) -- the dominant kernel's achieved rate from HIP events recorded around every launch (on the stream
+              the kernels are launched on) in extra steps of the serial schedule right after the timed region; under
+              N > 1 also the collectives of two further steps.
 """
 import argparse
 import json
@@ -40,6 +46,27 @@ PEAK_HBM_GBS = 8000.0           # MI355X_MICROARCH.md: HBM3E peak (spec); ~6.3 T
 CGAN_FLOP_PER_TILE = 0.609e12 * 1.0   # alternating D+G iteration ~ 255 + 354 GFLOP per 512^2 tile
 TILE = 512
 BATCH_PER_GPU = 64
+DUMP_MAX_BYTES = 64 << 20       # --dump-outputs: all files together
+DUMP_SAMPLE = 1 << 21           # elements kept of a larger array (the same seeded flat indices on every run)
+
+
+def dump_outputs(dirname, arrays):
+    """{name: tensor / array} -> dirname/<name>.npy, float64 kept, everything else as float32."""
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach()
+            a = (a if a.dtype == torch.float64 else a.float()).cpu().numpy()
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        if a.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).integers(0, a.size, DUMP_SAMPLE))
+            a = a.reshape(-1)[idx]
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise RuntimeError(f"--dump-outputs: more than {DUMP_MAX_BYTES >> 20} MB at '{name}'")
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def source_hash():
@@ -282,9 +309,10 @@ def _collective_report(sync, step):
 
 
 # ---------------------------------------------------------------------------------------------- CVAE train step + paint
-def cvae_leg(args, dtype, dev, world, rank, sync, steps, warmup, paint=True):
-    """One CVAE leg: timed train steps, collectives report (N > 1), per-kernel HIP-event profile of the serial
-    schedule -> roofline, paint_stream.  Returns the leg's dict (every rank runs it; rank 0's is printed)."""
+def cvae_leg(args, dtype, dev, world, rank, sync, steps, warmup, paint=True, full=True, dump=None):
+    """One CVAE leg: timed train steps, outputs of the last one to `dump` (rank 0); with `full` also the collectives
+    report (N > 1), per-kernel HIP-event profile of the serial schedule -> roofline, paint_stream.  Returns the leg's
+    dict (every rank runs it; rank 0's is printed)."""
     import contextlib
     from baryon_painter_amd.models import arch as A
     from baryon_painter_amd.models.cvae import CVAE
@@ -321,8 +349,40 @@ def cvae_leg(args, dtype, dev, world, rank, sync, steps, warmup, paint=True):
 
     dt, elbo = _timed(step, steps, warmup, world)
     dt = _reduce_max_time(dt, dev, world)
+    if dump and rank == 0:
+        # (before any further step: the parameters are the ones the last timed step's update left)
+        outs = {"elbo": elbo.detach().double().reshape(1), "loss_terms": model._last.stats,
+                "parameters": model._flat_params, "gradients": model._flat_grads,
+                "x_mu": model.x_mu, "z_mu": model.z_mu, "z_log_var": model.z_log_var}
+        if model.predict_var:
+            outs["x_log_var"] = model._last.x_log_var
+        dump_outputs(dump, outs)
     plan = model._last
     final_elbo = float(elbo.detach())
+    step_s = dt / steps
+    leg = {
+        "metric": "cvae_train_tiles_per_sec", "value": round(world * n * steps / dt, 2), "unit": "tiles/s",
+        "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": round(step_s * 1e3, 3),
+        "dtype": dtype,
+        "config": {"workload": f"CVAE fiducial train step (fwd+bwd+Adam), batch {n}/GPU of "
+                               f"{args.tile}x{args.tile} tiles, " + (
+                                   "fp32 (BASELINE.json configs[1])" if dtype == "f32" else
+                                   "bf16 activations/gradients in the generator trunk, fp32 accumulation, master "
+                                   "weights and statistics (BASELINE.json configs[3] per GPU)"),
+                   "tile": args.tile, "batch_per_gpu": n, "global_batch": n * world,
+                   "parallelism": f"dp{world}",
+                   "batch_norm": "single device" if world == 1 else
+                                 ("local statistics (--local-bn)" if args.local_bn else "global (all-reduced statistics)"),
+                   "optimizer": "torch.optim.Adam(lr=1e-3)" if args.torch_adam
+                                else "FlatAdam(lr=1e-3) = torch.optim.Adam arithmetic, fused",
+                   "schedule": ("weight gradients on a second HIP stream beside the rest of the backward pass"
+                                + ("; the whole step replayed from one hipGraph" if use_graph else ""))
+                               if os.environ.get("BP_SIDE_WGRAD", "1") != "0" else "single stream",
+                   "final_elbo": final_elbo}}
+    if not full:
+        del model, opt, plan
+        _free()
+        return leg
     coll = _collective_report(sync, step) if sync is not None else None
 
     # ---- kernel times for the roofline: PROF_STEPS further steps of the SERIAL schedule (not timed above).
@@ -384,7 +444,6 @@ def cvae_leg(args, dtype, dev, world, rank, sync, steps, warmup, paint=True):
                     "flop_per_launch": d["flop"] / d["launches"],
                     "algorithmic_bytes_per_launch": d["bytes"] / d["launches"]}
     all_bytes = sum(v["bytes"] for v in per.values()) / PROF_STEPS
-    step_s = dt / steps
     step_flop = n * 61.4e9 * (args.tile / 512) ** 2                  # 3 x forward convention
     step_bytes = n * (310e6 if hbm else 615e6) * (args.tile / 512) ** 2   # fused-ideal activation traffic
     top = sorted(per.items(), key=lambda kv: -kv[1]["ms"])[:14]
@@ -405,26 +464,7 @@ def cvae_leg(args, dtype, dev, world, rank, sync, steps, warmup, paint=True):
         "top_kernels": {k: {"ms_per_step": round(v["ms"] / PROF_STEPS, 3), "launches": v["launches"] // PROF_STEPS,
                             "tflops": round(v["flop"] / (v["ms"] * 1e-3) / 1e12, 2),
                             "GBs": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1)} for k, v in top}})
-    leg = {
-        "metric": "cvae_train_tiles_per_sec", "value": round(world * n * steps / dt, 2), "unit": "tiles/s",
-        "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": round(step_s * 1e3, 3),
-        "dtype": dtype,
-        "config": {"workload": f"CVAE fiducial train step (fwd+bwd+Adam), batch {n}/GPU of "
-                               f"{args.tile}x{args.tile} tiles, " + (
-                                   "fp32 (BASELINE.json configs[1])" if dtype == "f32" else
-                                   "bf16 activations/gradients in the generator trunk, fp32 accumulation, master "
-                                   "weights and statistics (BASELINE.json configs[3] per GPU)"),
-                   "tile": args.tile, "batch_per_gpu": n, "global_batch": n * world,
-                   "parallelism": f"dp{world}",
-                   "batch_norm": "single device" if world == 1 else
-                                 ("local statistics (--local-bn)" if args.local_bn else "global (all-reduced statistics)"),
-                   "optimizer": "torch.optim.Adam(lr=1e-3)" if args.torch_adam
-                                else "FlatAdam(lr=1e-3) = torch.optim.Adam arithmetic, fused",
-                   "schedule": ("weight gradients on a second HIP stream beside the rest of the backward pass"
-                                + ("; the whole step replayed from one hipGraph" if use_graph else ""))
-                               if os.environ.get("BP_SIDE_WGRAD", "1") != "0" else "single stream",
-                   "final_elbo": final_elbo},
-        "roofline": roofline, "paint": paint_leg}
+    leg.update({"roofline": roofline, "paint": paint_leg})
     if coll is not None:
         leg["config"].update(coll)
     del model, opt, plan, prof_events
@@ -432,11 +472,12 @@ def cvae_leg(args, dtype, dev, world, rank, sync, steps, warmup, paint=True):
     return leg
 
 
-def _paint_leg(args, model, dtype, dev, world, rank, n):
+def _paint_leg(args, model, dtype, dev, world, rank, n, full=True, dump=None):
     """paint() (SURVEY.md 8d metric (B), BASELINE.json configs[4]): RAW host tiles in -> physical host tiles out through
     CVAEPainter.paint_stream -- device-side transforms, Philox per-tile prior noise, one captured hipGraph per batch
     (prior + sampler + generator on four streams), pinned double-buffered H2D / D2H on side streams.  This rank
-    paints its contiguous share of the tiles; no collective."""
+    paints its contiguous share of the tiles; no collective.  `full`: also the captured forward alone on resident
+    tiles, and the checks of the painted tiles; `dump`: a seeded sample of them (rank 0)."""
     from baryon_painter_amd.painter import CVAEPainter
     from baryon_painter_amd.utils.datasets import SyntheticTileDataset
     model.train(False)
@@ -468,28 +509,31 @@ def _paint_leg(args, model, dtype, dev, world, rank, n):
         if world > 1:
             torch.distributed.barrier()
         tp = _reduce_max_time(time.perf_counter() - t0p, dev, world)
-        # the captured forward alone, tiles resident in HBM (no transforms, no copies): the kernel-side ceiling
-        g = model.paint_graph(pb)
-        torch.cuda.synchronize()
-        t0p = time.perf_counter()
-        for _ in range(10):
-            g["graph"].replay()
-        torch.cuda.synchronize()
-        tg = (time.perf_counter() - t0p) / 10
-    # every painted tile is finite and positive-definite pressure; tiles 0 and 8 are the same raw tile with different
-    # Philox streams (tile ids): they must differ, and differ little (the prior noise is a small modulation)
-    o = tout.numpy()
-    assert np.isfinite(o).all() and (o >= 0).all(), "paint_stream produced non-finite / negative pressure"
-    if n_paint > 8:
-        rel = np.abs(o[0] - o[8]).sum() / max(np.abs(o[0]).sum(), 1e-30)
-        assert 0 < rel < 1.0, f"tiles 0 and 8 (same input, different noise stream) differ by {rel}"
+        if dump and rank == 0:
+            dump_outputs(dump, {"painted_tiles": tout})
+        if full:
+            # the captured forward alone, tiles resident in HBM (no transforms, no copies): the kernel-side ceiling
+            g = model.paint_graph(pb)
+            torch.cuda.synchronize()
+            t0p = time.perf_counter()
+            for _ in range(10):
+                g["graph"].replay()
+            torch.cuda.synchronize()
+            tg = (time.perf_counter() - t0p) / 10
+    if full:
+        # every painted tile is finite and positive-definite pressure; tiles 0 and 8 are the same raw tile with
+        # different Philox streams (tile ids): they must differ, and differ little (the prior noise is a small modulation)
+        o = tout.numpy()
+        assert np.isfinite(o).all() and (o >= 0).all(), "paint_stream produced non-finite / negative pressure"
+        if n_paint > 8:
+            rel = np.abs(o[0] - o[8]).sum() / max(np.abs(o[0]).sum(), 1e-30)
+            assert 0 < rel < 1.0, f"tiles 0 and 8 (same input, different noise stream) differ by {rel}"
     alg = 190e6 * (args.tile / 512) ** 2 * (0.5 if dtype == "bf16" else 1.0)   # fused-ideal
     #                                                      activation bytes of one painted tile (fp32; half in bf16)
     flop = 20.25e9 * (args.tile / 512) ** 2      # paint = prior + generator forward
     rate = n_paint / tp
     leg = {"metric": "paint_tiles_per_sec", "value": round(world * rate, 1), "unit": "tiles/s",
            "tiles": n_paint, "batch": pb, "ms_per_batch": round(tp / (n_paint / pb) * 1e3, 3),
-           "resident_tiles_per_sec": round(world * pb / tg, 1), "ms_per_batch_graph_only": round(tg * 1e3, 3),
            # fp32 paint is matrix-core bound like the fp32 train step (AI ~107 FLOP/B), bf16 paint HBM-bound
            "roofline": ({"bound": "hbm", "achieved": round(alg * rate / 1e9, 1), "peak": PEAK_HBM_GBS,
                          "unit": "GB/s", "frac": round(alg * rate / 1e9 / PEAK_HBM_GBS, 4),
@@ -503,13 +547,16 @@ def _paint_leg(args, model, dtype, dev, world, rank, n):
            "note": "host float32 raw tile in -> host float32 physical tile out (pinned memory), per rank its "
                    "own tiles, no collective; 'resident' = the captured forward alone on tiles already in HBM; "
                    "roofline per GPU"}
+    if full:
+        leg.update({"resident_tiles_per_sec": round(world * pb / tg, 1), "ms_per_batch_graph_only": round(tg * 1e3, 3)})
     model.train(True)
     return leg
 
 
 # ---------------------------------------------------------------------------------------------- CGAN iteration
-def cgan_leg(args, dev, world, rank, sync, steps, warmup):
-    """BASELINE.json configs[2]: CGAN fiducial, alternating discriminator / generator iteration."""
+def cgan_leg(args, dev, world, rank, sync, steps, warmup, full=True, dump=None):
+    """BASELINE.json configs[2]: CGAN fiducial, alternating discriminator / generator iteration (`full`: and the
+    roofline of one further serial iteration; `dump`: losses and parameters after the last timed one, rank 0)."""
     import contextlib
     from baryon_painter_amd.models.cgan import CGAN
     from baryon_painter_amd.utils import synthetic as syn
@@ -528,7 +575,22 @@ def cgan_leg(args, dev, world, rank, sync, steps, warmup):
     step = lambda: model.train_step(x, y, z, opt_g, opt_d)
     dt, losses = _timed(step, steps, warmup, world)
     dt = _reduce_max_time(dt, dev, world)
+    if dump and rank == 0:
+        dump_outputs(dump, {"losses": torch.tensor([float(losses[k]) for k in ("D", "G_adv", "G_perceptual")],
+                                                   dtype=torch.float64),
+                            "generator_parameters": torch.cat([p.detach().reshape(-1) for p in model.g_parameters()]),
+                            "discriminator_parameters": torch.cat([p.detach().reshape(-1) for p in model.d_parameters()])})
     losses = {k: float(v) for k, v in losses.items()}
+    step_s = dt / steps
+    leg = {"metric": "cgan_train_tiles_per_sec", "value": round(world * n * steps / dt, 2), "unit": "tiles/s",
+           "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": round(step_s * 1e3, 3), "dtype": "f32",
+           "config": {"workload": f"CGAN fiducial alternating D+G iteration, batch {n} of {args.tile}x{args.tile} tiles, "
+                                  "fp32 (BASELINE.json configs[2]); parity vs own restatement only (no reference code)",
+                      "parallelism": f"dp{world}", "global_batch": n * world, "losses": losses}}
+    if not full:
+        del model, opt_g, opt_d
+        _free()
+        return leg
     # one further iteration of the serial schedule with HIP events around every launch (as the CVAE leg)
     plan = model._plan(n)
     side, plan.side = plan.side, None
@@ -551,7 +613,6 @@ def cgan_leg(args, dev, world, rank, sync, steps, warmup):
     dom = max(conv, key=lambda k: conv[k]["ms"])
     d = per[dom]
     tf = d["flop"] / (d["ms"] * 1e-3) / 1e12
-    step_s = dt / steps
     flop_step = sum(v["flop"] for v in conv.values())          # counted from the launches of one iteration
     top = sorted(per.items(), key=lambda kv: -kv[1]["ms"])[:10]
     roofline = {"bound": "mfma", "kernel": dom, "achieved": round(tf, 2), "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s",
@@ -566,12 +627,7 @@ def cgan_leg(args, dev, world, rank, sync, steps, warmup):
                                "flop_per_tile_survey": CGAN_FLOP_PER_TILE * (args.tile / 512) ** 2},
                 "top_kernels": {k: {"ms_per_step": round(v["ms"], 3), "launches": v["launches"],
                                     "tflops": round(v["flop"] / (v["ms"] * 1e-3) / 1e12, 2)} for k, v in top}}
-    leg = {"metric": "cgan_train_tiles_per_sec", "value": round(world * n * steps / dt, 2), "unit": "tiles/s",
-           "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": round(step_s * 1e3, 3), "dtype": "f32",
-           "config": {"workload": f"CGAN fiducial alternating D+G iteration, batch {n} of {args.tile}x{args.tile} tiles, "
-                                  "fp32 (BASELINE.json configs[2]); parity vs own restatement only (no reference code)",
-                      "parallelism": f"dp{world}", "global_batch": n * world, "losses": losses},
-           "roofline": roofline}
+    leg["roofline"] = roofline
     del model, opt_g, opt_d, plan, ev
     _free()
     return leg
@@ -643,7 +699,14 @@ def main():
                     help="comma list of secondary legs beside the headline: bf16,cgan (default: bf16,cgan on one GPU, "
                          "bf16 on several; 'none' for the headline alone)")
     ap.add_argument("--secondary-steps", type=int, default=8, help="timed steps of the bf16 leg (CGAN: a quarter)")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own: rooflines (serial profiling steps), collectives report, "
+                         "paint legs, the secondary legs, the CPU baseline.  Without it a run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, <= 64 MB)")
     args = ap.parse_args()
+    if not args.full and (args.layers or (args.legs is not None and args.legs != "none")):
+        ap.error("--layers and --legs (other than 'none') need --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))                 # (before anything touches the GPU)
@@ -677,7 +740,9 @@ def main():
         from baryon_painter_amd.dist import Sync
         sync = Sync(sync_bn=not args.local_bn)
 
-    if args.legs is None:
+    if not args.full:
+        legs = []
+    elif args.legs is None:
         legs = ["bf16", "cgan"] if world == 1 else ["bf16"]
     else:
         legs = [s for s in args.legs.split(",") if s and s != "none"]
@@ -690,7 +755,7 @@ def main():
         torch.manual_seed(1234)
         with contextlib.redirect_stdout(sys.stderr):
             model = CVAE(A.fiducial_architecture(args.tile), dev, sync=None, dtype=args.dtype)
-        leg = _paint_leg(args, model, args.dtype, dev, world, rank, args.batch)
+        leg = _paint_leg(args, model, args.dtype, dev, world, rank, args.batch, full=args.full, dump=args.dump_outputs)
         if rank == 0:
             leg.update({"n_gpus": world, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype,
                         "data": "synthetic (8 distinct raw tiles per rank, repeated; random-init weights)",
@@ -702,10 +767,11 @@ def main():
             torch.distributed.destroy_process_group()
         return
     if args.workload == "cgan":
-        head = cgan_leg(args, dev, world, rank, sync, args.steps, args.warmup)
+        head = cgan_leg(args, dev, world, rank, sync, args.steps, args.warmup, full=args.full, dump=args.dump_outputs)
         legs = []
     else:
-        head = cvae_leg(args, args.dtype, dev, world, rank, sync, args.steps, args.warmup, paint=not args.no_paint)
+        head = cvae_leg(args, args.dtype, dev, world, rank, sync, args.steps, args.warmup,
+                        paint=not args.no_paint, full=args.full, dump=args.dump_outputs)
     extra = {}
     for name in legs:
         try:
@@ -743,8 +809,9 @@ def main():
         if other:
             out["config"]["other_configs"] = other
         # (the per-kernel table first, the numbers a reader wants last: a log tail keeps the end of the line)
-        out["roofline"] = head["roofline"]
-        if world == 1 and not args.no_cpu_baseline:
+        if "roofline" in head:
+            out["roofline"] = head["roofline"]
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         if head.get("paint") is not None:
             out["paint"] = head["paint"]

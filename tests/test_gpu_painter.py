@@ -477,7 +477,7 @@ def test_bench_two_ranks_rehearsal():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "BP_EARLY_ALLREDUCE"):
         env.pop(k, None)
     cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2", "--tile", "64",
-           "--no-paint", "--secondary-steps", "2"]
+           "--no-paint", "--secondary-steps", "2", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -497,6 +497,41 @@ def test_bench_two_ranks_rehearsal():
     assert b["dtype"] == "bf16" and b["n_gpus"] == 2 and b["value"] > 0 and b["roofline"]["bound"] == "hbm"
     assert out["config"]["other_configs"]["bf16 (configs[3] per GPU)"]["value"] == b["value"]
     assert "cgan" not in out                      # (single-GPU leg)
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """`python bench.py` without --full times the headline alone; --dump-outputs writes what the last timed step
+    computed, and two runs with the same arguments start from the same inputs (same outputs up to the order of
+    floating-point sums)."""
+    import json
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "BP_SYNC_FORCE"):
+        env.pop(k, None)
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"out{i}"
+        cmd = [sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--batch", "2", "--tile", "64",
+               "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+        out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert out["metric"] == "cvae_train_tiles_per_sec" and out["unit"] == "tiles/s" and out["higher_is_better"]
+        assert out["dtype"] == "f32" and out["steps"] == 3 and out["warmup"] == 1
+        assert out["ms_per_step"] > 0 and out["value"] == pytest.approx(2 * 1e3 / out["ms_per_step"], rel=1e-2)
+        assert not {"roofline", "cpu_baseline", "paint", "bf16", "cgan"} & set(out)
+        assert "other_configs" not in out["config"]
+        files = {p.name: np.load(p) for p in d.iterdir()}
+        assert {"elbo.npy", "loss_terms.npy", "parameters.npy", "gradients.npy", "x_mu.npy"} <= set(files)
+        assert sum(p.stat().st_size for p in d.iterdir()) <= 64 << 20
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in files.values())
+        assert files["elbo.npy"][0] == pytest.approx(out["config"]["final_elbo"], rel=1e-6)
+        assert files["parameters.npy"].size == 1662961
+        runs.append(files)
+    a, b = runs
+    assert a["elbo.npy"][0] == pytest.approx(b["elbo.npy"][0], rel=1e-3)
+    # (Adam moves a parameter by at most lr = 1e-3 per step: different initial weights would differ by far more)
+    assert np.abs(a["parameters.npy"] - b["parameters.npy"]).max() < 1e-2
+    assert np.abs(a["x_mu.npy"] - b["x_mu.npy"]).max() <= 1e-2 * np.abs(a["x_mu.npy"]).max()
 
 
 def test_training_script_two_ranks_rehearsal(tmp_path):

@@ -20,14 +20,14 @@ cd /tmp && export TMPDIR=/tmp
 export BP_SIDE_WGRAD=0 BP_BRANCH_STREAMS=0
 PMC="SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVES GRBM_GUI_ACTIVE"
 for d in f32 bf16; do
-  timeout -k 10 400 rocprofv3 --pmc $PMC --kernel-trace -d $F/mfma_$d -o r --output-format csv -- python3 $R/bench.py --legs none --dtype $d --steps 2 --warmup 1 --no-cpu-baseline --no-paint > $F/mfma_$d.log 2>&1
+  timeout -k 10 400 rocprofv3 --pmc $PMC --kernel-trace -d $F/mfma_$d -o r --output-format csv -- python3 $R/bench.py --full --legs none --dtype $d --steps 2 --warmup 1 --no-cpu-baseline --no-paint > $F/mfma_$d.log 2>&1
   python3 $R/tools/mfma_util.py $(ls $F/mfma_$d/*counter_collection.csv | head -1) 30 > $F/mfma_util_$d.txt
   rm -rf $F/mfma_$d
   head -14 $F/mfma_util_$d.txt | cut -c1-150
 done
 unset BP_SIDE_WGRAD BP_BRANCH_STREAMS
 cd $R
-python bench.py --steps 20 --warmup 5 > $F/bench_default.json 2> $F/bench_default.err; echo "bench rc=$?"
+python bench.py --full --steps 20 --warmup 5 > $F/bench_default.json 2> $F/bench_default.err; echo "bench rc=$?"
 tail -c 600 $F/bench_default.json
 for d in f32 bf16; do python tools/phase_times.py $d 20 > $F/phase_times_$d.txt 2>/dev/null; cat $F/phase_times_$d.txt; done
 bash tools/rccl_one_rank.sh > $F/dp_one_rank_peer.txt 2>&1
