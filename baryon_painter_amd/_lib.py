@@ -16,6 +16,7 @@ IMPL_SHARED = 0x100
 IMPL_DEFER = 0x200
 PACK_FWD, PACK_BWD = 0, 1
 F32, BF16 = 0, 1
+F64 = 2            # bp_plane_cut's float64 planes
 
 
 class View(C.Structure):
@@ -119,6 +120,12 @@ SIGNATURES = {
     "bp_paint_store": (C.c_int, [_VP, _PWP, C.c_int32, _P, _P, _P]),
     "bp_philox_normal": (C.c_int, [C.c_uint64, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "bp_philox_normal_dev": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "bp_plane_cut_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "bp_plane_cut": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P,
+                               C.c_size_t, _P, _P]),
+    "bp_plane_blend": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P,
+                                 C.c_int32, C.c_double, _P, _P, _P, C.c_int32, C.c_int32, _P]),
+    "bp_plane_finish": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
     "bp_latent_forward": (C.c_int, [C.POINTER(Latent), _VP, _PWP, _VP, _PWP, _P, _P, _VP, _P, _P,
                                     C.c_size_t, _P]),
     "bp_latent_backward": (C.c_int, [C.POINTER(Latent), _VP, _P, _P, _P, C.c_float, _VP, _VP, _P]),

@@ -1,0 +1,296 @@
+// Light-cone planes on the device (lightcone.paint_plane(on_device=True), process_SLICS.py:198-220): the pieces that
+// sit on either side of the captured paint graph when a whole periodic plane is painted, so that the plane is uploaded
+// once and only the finished plane comes back.
+//   bp_plane_cut     wrap-around tile cut of lightcone.get_tile straight into the graph's raw tiles; when the cut is
+//                    not the network's tile size, the cubic-spline resampling of scipy.ndimage.zoom(order=3,
+//                    mode="reflect") in float64 (prefilter along axis 0, then axis 1; tensor-product sampling)
+//   bp_plane_blend   acc += w * p, wsum += w for a batch of painted tiles, tile by tile in tile order, each product
+//                    formed in double from the float32 tile (the host loop's order: no atomics, no fused multiply-add)
+//   bp_plane_finish  acc / wsum (0 / 0 = NaN where no tile reaches, as in the reference)
+// The whole file is compiled without floating-point contraction: the host expressions these kernels restate round
+// every product and every sum separately.
+#include "common.hpp"
+#include <math.h>
+
+#include <algorithm>
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int RB = 256;
+
+__device__ __forceinline__ int wrap(int i, int n) {
+  const int r = i % n;
+  return r < 0 ? r + n : r;
+}
+
+// half-sample symmetric boundary (SciPy's "reflect"): i mod 2n, then 2n - 1 - i above n
+__device__ __forceinline__ int mirror(int i, int n) {
+  const int m = wrap(i, 2 * n);
+  return m >= n ? 2 * n - 1 - m : m;
+}
+
+// cut == tile: a gather, (float) of the plane's value (bit-exact to get_tile + astype(float32))
+template <typename T>
+__global__ __launch_bounds__(RB) void cut_gather_kernel(const T* plane, int rows, int cols, const int* org, int tile,
+                                                        unsigned total, float* out) {
+  const unsigned i = blockIdx.x * RB + threadIdx.x;
+  if (i >= total) return;
+  const unsigned tt = (unsigned)tile * (unsigned)tile;
+  const unsigned t = i / tt, rc = i - t * tt, r = rc / (unsigned)tile, c = rc - r * (unsigned)tile;
+  const int x = wrap(wrap(org[2 * t], rows) + (int)r, rows), y = wrap(wrap(org[2 * t + 1], cols) + (int)c, cols);
+  out[i] = (float)plane[(int64_t)x * cols + y];
+}
+
+// cut != tile, step 1: the cut as float64, a[t][r][c]
+template <typename T>
+__global__ __launch_bounds__(RB) void cut_load_kernel(const T* plane, int rows, int cols, const int* org, int cut,
+                                                      unsigned total, double* a) {
+  const unsigned i = blockIdx.x * RB + threadIdx.x;
+  if (i >= total) return;
+  const unsigned cc = (unsigned)cut * (unsigned)cut;
+  const unsigned t = i / cc, rc = i - t * cc, r = rc / (unsigned)cut, c = rc - r * (unsigned)cut;
+  const int x = wrap(wrap(org[2 * t], rows) + (int)r, rows), y = wrap(wrap(org[2 * t + 1], cols) + (int)c, cols);
+  a[i] = (double)plane[(int64_t)x * cols + y];
+}
+
+// step 2 / 4: cubic B-spline prefilter of n_lines lines of n elements, in place.  Line L = (t, j) of a [t][k][j]
+// image: element k at a[t * n * n + k * n + j], so the threads of a wave (consecutive j) load consecutive doubles.
+// Called on [t][r][c] it filters along axis 0, on the transposed [t][c][r] along axis 1.
+__global__ __launch_bounds__(RB) void prefilter_kernel(double* a, int n, unsigned n_lines) {
+  const unsigned L = blockIdx.x * RB + threadIdx.x;
+  if (L >= n_lines) return;
+  const unsigned t = L / (unsigned)n, j = L - t * (unsigned)n;
+  double* c = a + (size_t)t * n * n + j;
+  const int s = n;
+  const double z = sqrt(3.0) - 2.0;
+  for (int i = 0; i < n; ++i) c[i * s] *= 6.0;                 // gain (1 - z) (1 - 1/z)
+  const double zn = pow(z, (double)n);
+  // causal initialisation under half-sample symmetric boundaries
+  const double c0 = c[0], cl = c[(n - 1) * s];
+  double sum = c0 + zn * cl, zi = z;
+  for (int i = 1; i < n; ++i) {
+    if (fabs(zi) < 1e-18) break;
+    sum += zi * (c[i * s] + zn * c[(n - 1 - i) * s]);
+    zi *= z;
+  }
+  double prev = sum * z / (1.0 - zn * zn) + c0;
+  c[0] = prev;
+  for (int i = 1; i < n; ++i) {                                // causal pass
+    prev = c[i * s] + z * prev;
+    c[i * s] = prev;
+  }
+  prev *= z / (z - 1.0);                                       // anti-causal initialisation
+  c[(n - 1) * s] = prev;
+  for (int i = n - 2; i >= 0; --i) {                           // anti-causal pass
+    prev = z * (prev - c[i * s]);
+    c[i * s] = prev;
+  }
+}
+
+// step 3: b[t][c][r] = a[t][r][c] through LDS, 32 x 32 blocks (reads and writes along rows of 32 doubles)
+constexpr int TB = 32;
+__global__ __launch_bounds__(TB * 8) void transpose_kernel(const double* a, double* b, int n) {
+  __shared__ double s[TB][TB + 1];
+  const int t = blockIdx.z, r0 = blockIdx.y * TB, c0 = blockIdx.x * TB;
+  const double* src = a + (size_t)t * n * n;
+  double* dst = b + (size_t)t * n * n;
+  const int tx = threadIdx.x % TB, ty = threadIdx.x / TB;
+  for (int k = ty; k < TB; k += 8) {
+    const int r = r0 + k, c = c0 + tx;
+    if (r < n && c < n) s[k][tx] = src[(size_t)r * n + c];
+  }
+  __syncthreads();
+  for (int k = ty; k < TB; k += 8) {
+    const int c = c0 + k, r = r0 + tx;
+    if (r < n && c < n) dst[(size_t)c * n + r] = s[tx][k];
+  }
+}
+
+// per-axis taps and weights of output coordinate k (cc = k (n_in - 1) / (n_out - 1))
+__device__ __forceinline__ void spline_taps(int k, int n_in, int n_out, int (&idx)[4], double (&w)[4]) {
+  const double cc = (double)k * (double)(n_in - 1) / (double)(n_out - 1);
+  const double f = floor(cc), t = cc - f, u = 1.0 - t;
+  w[0] = u * u * u / 6.0;
+  w[1] = (4.0 - 6.0 * t * t + 3.0 * t * t * t) / 6.0;
+  w[3] = t * t * t / 6.0;
+  w[2] = 1.0 - w[0] - w[1] - w[3];
+  const int fi = (int)f;
+#pragma unroll
+  for (int p = 0; p < 4; ++p) idx[p] = mirror(fi - 1 + p, n_in);
+}
+
+// step 5: out[t][i][j] = sum_p wi[p] * (sum_q wj[q] * coef(row ti[p], col tj[q])), coefficients as b[t][col][row]
+__global__ __launch_bounds__(RB) void zoom_sample_kernel(const double* b, int cut, int tile, unsigned total, float* out) {
+  const unsigned i = blockIdx.x * RB + threadIdx.x;
+  if (i >= total) return;
+  const unsigned tt = (unsigned)tile * (unsigned)tile;
+  const unsigned t = i / tt, rc = i - t * tt, r = rc / (unsigned)tile, c = rc - r * (unsigned)tile;
+  int ti[4], tj[4];
+  double wi[4], wj[4];
+  spline_taps((int)r, cut, tile, ti, wi);
+  spline_taps((int)c, cut, tile, tj, wj);
+  const double* bt = b + (size_t)t * cut * cut;
+  double v = 0.0;
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    double inner = 0.0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) inner += wj[q] * bt[(size_t)tj[q] * cut + ti[p]];
+    v += wi[p] * inner;
+  }
+  out[i] = (float)v;
+}
+
+// mean and population standard deviation of each painted tile in float64, one workgroup per tile, a fixed-order
+// reduction (strided partial sums, then a tree over the workgroup): stats[2t] = mean, stats[2t + 1] = std
+__global__ __launch_bounds__(RB) void tile_stats_kernel(const float* tiles, int tt, double* stats) {
+  __shared__ double red[RB];
+  const float* p = tiles + (size_t)blockIdx.x * tt;
+  double s = 0.0;
+  for (int k = threadIdx.x; k < tt; k += RB) s += (double)p[k];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int h = RB / 2; h > 0; h /= 2) {
+    if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+    __syncthreads();
+  }
+  const double mean = red[0] / (double)tt;
+  __syncthreads();
+  s = 0.0;
+  for (int k = threadIdx.x; k < tt; k += RB) {
+    const double d = (double)p[k] - mean;
+    s += d * d;
+  }
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int h = RB / 2; h > 0; h /= 2) {
+    if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    stats[2 * blockIdx.x] = mean;
+    stats[2 * blockIdx.x + 1] = sqrt(red[0] / (double)tt);
+  }
+}
+
+// one thread per plane pixel of the batch's bounding box [bx0, bx1) x [by0, by1); the covering tiles in tile order
+__global__ __launch_bounds__(RB) void blend_kernel(const float* tiles, int n, int tile, const int* dst, int bx0,
+                                                   int by0, int bw, unsigned total, const double* weight, int reg,
+                                                   double reg_std, const double* stats, double* acc, double* wsum,
+                                                   int cols) {
+  const unsigned i = blockIdx.x * RB + threadIdx.x;
+  if (i >= total) return;
+  const unsigned ry = i / (unsigned)bw;
+  const int x = bx0 + (int)ry, y = by0 + (int)(i - ry * (unsigned)bw);
+  const int64_t o = (int64_t)x * cols + y;
+  double a = acc[o], s = wsum[o];
+  const size_t tt = (size_t)tile * tile;
+  for (int t = 0; t < n; ++t) {
+    const int lx = x - dst[2 * t], ly = y - dst[2 * t + 1];
+    if (lx < 0 || lx >= tile || ly < 0 || ly >= tile) continue;
+    const int l = lx * tile + ly;
+    const double p = (double)tiles[t * tt + l];
+    double w = weight[l];
+    if (reg && fabs(p - stats[2 * t]) > stats[2 * t + 1] * reg_std) w = 0.0;
+    a += w * p;
+    s += w;
+  }
+  acc[o] = a;
+  wsum[o] = s;
+}
+
+__global__ __launch_bounds__(RB) void finish_kernel(const double* acc, const double* wsum, int64_t count, double* out) {
+  const int64_t i = (int64_t)blockIdx.x * RB + threadIdx.x;
+  if (i < count) out[i] = acc[i] / wsum[i];
+}
+
+static inline unsigned nblocks(int64_t total) { return (unsigned)((total + RB - 1) / RB); }
+
+template <typename T>
+int plane_cut(const T* plane, int32_t rows, int32_t cols, const int32_t* origins, int32_t n, int32_t cut,
+              int32_t tile, double* scratch, size_t scratch_bytes, float* out, hipStream_t sm) {
+  if (cut == tile) {
+    const int64_t total = (int64_t)n * tile * tile;
+    hipLaunchKernelGGL(cut_gather_kernel<T>, dim3(nblocks(total)), dim3(RB), 0, sm, plane, rows, cols, origins, tile,
+                       (unsigned)total, out);
+    BP_CHECK_LAUNCH();
+    return BP_OK;
+  }
+  // chunks of as many tiles as two float64 images of the cut per tile in the scratch allow
+  const size_t per = (size_t)2 * cut * cut * sizeof(double);
+  const int chunk = (int)std::min<size_t>(std::min<size_t>((size_t)n, 65535), scratch_bytes / per);   // (grid z)
+  if (chunk < 1) return BP_EWORKSPACE;
+  double* a = scratch;
+  double* b = scratch + (size_t)chunk * cut * cut;
+  for (int t0 = 0; t0 < n; t0 += chunk) {
+    const int m = std::min(chunk, n - t0);
+    const int64_t cells = (int64_t)m * cut * cut;
+    hipLaunchKernelGGL(cut_load_kernel<T>, dim3(nblocks(cells)), dim3(RB), 0, sm, plane, rows, cols, origins + 2 * t0,
+                       cut, (unsigned)cells, a);
+    const unsigned lines = (unsigned)m * (unsigned)cut;
+    hipLaunchKernelGGL(prefilter_kernel, dim3(nblocks(lines)), dim3(RB), 0, sm, a, (int)cut, lines);      // axis 0
+    const dim3 tg((cut + TB - 1) / TB, (cut + TB - 1) / TB, m);
+    hipLaunchKernelGGL(transpose_kernel, tg, dim3(TB * 8), 0, sm, (const double*)a, b, (int)cut);
+    hipLaunchKernelGGL(prefilter_kernel, dim3(nblocks(lines)), dim3(RB), 0, sm, b, (int)cut, lines);      // axis 1
+    const int64_t px = (int64_t)m * tile * tile;
+    hipLaunchKernelGGL(zoom_sample_kernel, dim3(nblocks(px)), dim3(RB), 0, sm, (const double*)b, (int)cut, (int)tile,
+                       (unsigned)px, out + (size_t)t0 * tile * tile);
+    BP_CHECK_LAUNCH();
+  }
+  return BP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t bp_plane_cut_workspace(int32_t n, int32_t cut, int32_t tile) {
+  if (n <= 0 || cut <= 0 || cut == tile) return 0;
+  return (size_t)2 * n * cut * cut * sizeof(double);
+}
+
+int bp_plane_cut(const void* plane, int32_t dtype, int32_t rows, int32_t cols, const int32_t* origins, int32_t n,
+                 int32_t cut, int32_t tile, double* scratch, size_t scratch_bytes, float* out, void* stream) {
+  if (!plane || !origins || !out || rows <= 0 || cols <= 0 || n <= 0 || cut <= 0 || tile <= 0 ||
+      (dtype != BP_F32 && dtype != BP_F64) || (cut != tile && (!scratch || cut < 2 || tile < 2)))
+    return BP_EINVAL;
+  if ((int64_t)rows * cols >= ((int64_t)1 << 31) || (int64_t)n * tile * tile >= ((int64_t)1 << 31) ||
+      (int64_t)n * cut * cut >= ((int64_t)1 << 31))
+    return BP_EUNSUPPORTED;
+  const hipStream_t sm = bp_stream(stream);
+  return dtype == BP_F32
+             ? plane_cut(static_cast<const float*>(plane), rows, cols, origins, n, cut, tile, scratch, scratch_bytes, out, sm)
+             : plane_cut(static_cast<const double*>(plane), rows, cols, origins, n, cut, tile, scratch, scratch_bytes, out, sm);
+}
+
+int bp_plane_blend(const float* tiles, int32_t n, int32_t tile, const int32_t* dst, int32_t bx0, int32_t by0,
+                   int32_t bx1, int32_t by1, const double* weight, int32_t regularise, double regularise_std,
+                   double* stats, double* acc, double* wsum, int32_t rows, int32_t cols, void* stream) {
+  if (!tiles || !dst || !weight || !acc || !wsum || n <= 0 || tile <= 0 || rows <= 0 || cols <= 0 ||
+      (regularise && !stats) || bx0 < 0 || by0 < 0 || bx1 > rows || by1 > cols || bx0 >= bx1 || by0 >= by1)
+    return BP_EINVAL;
+  if ((int64_t)rows * cols >= ((int64_t)1 << 31) || (int64_t)n * tile * tile >= ((int64_t)1 << 31))
+    return BP_EUNSUPPORTED;
+  const hipStream_t sm = bp_stream(stream);
+  if (regularise) {
+    hipLaunchKernelGGL(tile_stats_kernel, dim3(n), dim3(RB), 0, sm, tiles, tile * tile, stats);
+    BP_CHECK_LAUNCH();
+  }
+  const int64_t total = (int64_t)(bx1 - bx0) * (by1 - by0);
+  hipLaunchKernelGGL(blend_kernel, dim3(nblocks(total)), dim3(RB), 0, sm, tiles, n, tile, dst, bx0, by0, by1 - by0,
+                     (unsigned)total, weight, regularise ? 1 : 0, regularise_std, (const double*)stats, acc, wsum,
+                     cols);
+  BP_CHECK_LAUNCH();
+  return BP_OK;
+}
+
+int bp_plane_finish(const double* acc, const double* wsum, int64_t count, double* out, void* stream) {
+  if (!acc || !wsum || !out || count <= 0) return BP_EINVAL;
+  hipLaunchKernelGGL(finish_kernel, dim3(nblocks(count)), dim3(RB), 0, bp_stream(stream), acc, wsum, count, out);
+  BP_CHECK_LAUNCH();
+  return BP_OK;
+}
+
+}  // extern "C"

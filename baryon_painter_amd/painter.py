@@ -371,6 +371,7 @@ class CVAEPainter(Painter):
         four (batch, 1, H, W) fp32 buffers -- 256 MiB of pinned memory at batch 64 of 512^2 tiles -- which otherwise live
         as long as the painter (page-locking them costs tens of milliseconds per call, hence the cache)."""
         self.__dict__.pop("_paint_host_buffers", None)
+        self.__dict__.pop("_plane_device_buffers", None)      # (and _paint_plane_device's accumulators and scratch)
 
     def paint_stream(self, inputs, z, batch_size=64, tile_ids=None, seed=0, rank=0, world_size=1, out=None):
         """Paint MANY raw tiles: ``inputs`` (N, H, W) float32 host array (NumPy, memory map, or a pinned torch tensor),
@@ -500,6 +501,106 @@ class CVAEPainter(Painter):
                 harvest(sl)
             torch.cuda.synchronize(dev)
         return (result, (lo, hi)) if world_size > 1 else result
+
+    def _paint_plane_device(self, delta, geo, z, weight_map, batch_size, tile_ids, seed, regularise_std=None, out=None):
+        """The device form of ``lightcone.paint_plane`` (on_device=True): ``geo`` is ``lightcone.plane_geometry``'s,
+        ``weight_map`` the host's ``make_weight_map`` (float64, uploaded as it is), ``tile_ids`` / ``seed`` / ``batch_size``
+        those the host path hands to ``paint_stream``.  Per batch, on ONE stream: the tiles are cut (and resampled) from
+        the device plane into a slot's ``raw`` (bp_plane_cut), the batch's parameter block is copied in from a per-plane
+        device copy, the graph is replayed, and the slot's ``out`` is blended into float64 accumulators
+        (bp_plane_blend); bp_plane_finish divides.  Returns the (n_plane, n_plane) float64 plane, or ``out`` (a CUDA
+        float64 tensor of that shape) filled in place."""
+        import ctypes as C
+        from . import _lib as L
+        model = self.model
+        model.train(False)
+        dev = model.device
+        cy, H, W = model.dim_y
+        tile, cut, n_plane = H, geo["cut"], geo["n_plane"]
+        if cy != 1 or H != W:
+            raise NotImplementedError("device planes need single-channel square tiles")
+        if tuple(weight_map.shape) != (tile, tile):
+            raise ValueError(f"weight map {weight_map.shape} does not match the model's {tile}^2 tiles")
+        n = len(geo["origins"])
+        B = int(batch_size)
+        zs = np.full(n, float(z))
+        s_in, k_in, k_out, s_out = self._shift_log_parameters(zs)          # (NotImplementedError before any capture)
+        if isinstance(delta, torch.Tensor):
+            if delta.device != torch.device(dev):
+                raise ValueError(f"delta lives on {delta.device}, the painter on {dev}")
+            d = delta if delta.is_contiguous() else delta.contiguous()
+        else:
+            d = torch.from_numpy(np.ascontiguousarray(delta)).to(dev)
+        if d.dim() != 2 or d.dtype not in (torch.float32, torch.float64):
+            raise TypeError("delta must be a 2-d float32 or float64 plane")
+        if out is not None and (not isinstance(out, torch.Tensor) or out.device != torch.device(dev) or
+                                out.dtype != torch.float64 or tuple(out.shape) != (n_plane, n_plane) or
+                                not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous float64 ({n_plane}, {n_plane}) tensor on {dev}")
+        g = model.paint_graph(B)
+        # per-plane parameter blocks, one per batch, built like paint_stream's pinned ones and uploaded once: a batch
+        # then costs one device-to-device copy of its block into the slot
+        layout = g["block_layout"]
+        n_batches = (n + B - 1) // B
+        blocks = torch.zeros((n_batches, g["block_bytes"]), dtype=torch.uint8)
+        for bi in range(n_batches):
+            a, b = bi * B, min(bi * B + B, n)
+            m = b - a
+            hv = {}
+            for name, (o, dt, shape) in layout.items():
+                nb = torch.tensor([], dtype=dt).element_size() * int(np.prod(shape))
+                hv[name] = blocks[bi, o:o + nb].view(dt).view(shape).numpy()
+            hv["seed"][0] = np.array(int(seed) & 0xFFFFFFFFFFFFFFFF, dtype=np.uint64).astype(np.int64)
+            hv["xf_in"][:m, 0], hv["xf_in"][:m, 1] = s_in[a:b], k_in
+            hv["xf_out"][:m, 0], hv["xf_out"][:m, 1] = k_out, s_out[a:b]
+            hv["aux"][:m, 0] = zs[a:b]
+            hv["tile_ids"][:m] = tile_ids[a:b]
+            if m < B:                                     # a short last batch: pad with its last tile's parameters
+                for k in ("xf_in", "xf_out", "aux", "tile_ids"):
+                    hv[k][m:] = hv[k][m - 1]
+        lib = L.load()
+        # accumulators and the resampling scratch are kept between calls (release_paint_buffers() frees them)
+        cache = self.__dict__.setdefault("_plane_device_buffers", {})
+        ws = int(lib.bp_plane_cut_workspace(B, cut, tile))
+        key = (n_plane, B, ws, str(dev))
+        if key not in cache:
+            cache.clear()
+            cache[key] = {"acc": torch.empty((n_plane, n_plane), dtype=torch.float64, device=dev),
+                          "wsum": torch.empty((n_plane, n_plane), dtype=torch.float64, device=dev),
+                          "scratch": torch.empty(max(ws // 8, 1), dtype=torch.float64, device=dev),
+                          "stats": torch.empty(2 * B, dtype=torch.float64, device=dev)}
+        buf = cache[key]
+        acc, wsum = buf["acc"], buf["wsum"]
+        result = out if out is not None else torch.empty((n_plane, n_plane), dtype=torch.float64, device=dev)
+        with torch.no_grad():
+            blocks_d = blocks.to(dev)
+            org_d = torch.from_numpy(geo["origins"]).to(dev)
+            dst_d = torch.from_numpy(geo["dst"]).to(dev)
+            w_d = torch.from_numpy(np.ascontiguousarray(weight_map, dtype=np.float64)).to(dev)
+            acc.zero_()
+            wsum.zero_()
+            sm = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            dtype = L.F32 if d.dtype == torch.float32 else L.F64
+            reg = regularise_std is not None
+            rows, cols = d.shape
+            for bi in range(n_batches):
+                a, b = bi * B, min(bi * B + B, n)
+                m = b - a
+                gs = g["slots"][bi % 2]               # (one stream: the slots' reuse is ordered by the stream itself)
+                L.check(lib.bp_plane_cut(L.ptr(d), dtype, rows, cols, C.c_void_p(org_d.data_ptr() + 8 * a), m, cut,
+                                         tile, L.ptr(buf["scratch"]), ws, L.ptr(gs["raw"]), sm), "plane cut")
+                gs["block"].copy_(blocks_d[bi])
+                gs["graph"].replay()
+                box = geo["dst"][a:b]
+                L.check(lib.bp_plane_blend(L.ptr(gs["out"]), m, tile, C.c_void_p(dst_d.data_ptr() + 8 * a),
+                                           int(box[:, 0].min()), int(box[:, 1].min()), int(box[:, 0].max()) + tile,
+                                           int(box[:, 1].max()) + tile, L.ptr(w_d), 1 if reg else 0,
+                                           float(regularise_std) if reg else 0.0, L.ptr(buf["stats"]), L.ptr(acc),
+                                           L.ptr(wsum), n_plane, n_plane, sm), "plane blend")
+            L.check(lib.bp_plane_finish(L.ptr(acc), L.ptr(wsum), n_plane * n_plane, L.ptr(result), sm), "plane finish")
+            if out is not None:
+                return out
+            return result.cpu().numpy()
 
     # ------------------------------------------------------------------------------ checkpoints
     def save_state_to_file(self, filename, mode="model_state_dict+metadata"):

@@ -337,6 +337,33 @@ int bp_philox_normal(uint64_t seed, const int64_t* tile_ids, int32_t n, int32_t 
 int bp_philox_normal_dev(const uint64_t* seed_dev, const int64_t* tile_ids, int32_t n, int32_t L, int32_t per_tile,
                          float* eps, void* stream);
 
+/* ---- light-cone planes (lightcone.paint_plane(on_device=True), process_SLICS.py:198-220) -----------------------
+ * A periodic plane is cut into the paint graph's raw tiles, and the painted tiles are blended into float64 planes, on
+ * the device: the plane goes up once and only the finished plane comes back.  Integers (cut origins, destinations,
+ * bounding boxes) are computed on the host with lightcone.get_tile / generate_tiling's expressions.
+ *   bp_plane_cut   : out[t] (n, tile, tile) float32 = the cut x cut block of `plane` (rows x cols, BP_F32 or BP_F64)
+ *                    at origins[t] = {x0, y0} (device, int32 (n, 2)), rows wrapped modulo `rows`, columns modulo
+ *                    `cols`.  cut == tile: a gather, bit-exact to get_tile + astype(float32).  cut != tile:
+ *                    scipy.ndimage.zoom(cut_block, tile / cut, order=3, mode="reflect") in float64 (spline prefilter
+ *                    along axis 0 then axis 1, tensor-product sampling at k (cut - 1) / (tile - 1)), rounded once to
+ *                    float32; needs bp_plane_cut_workspace(n, cut, tile) bytes of `scratch` (less works in chunks of
+ *                    tiles, down to one tile's share; BP_EWORKSPACE below that)
+ *   bp_plane_blend : for t = 0 .. n-1 in order, acc[dst[t] + (i, j)] += w[i, j] * (double) tiles[t][i, j] and
+ *                    wsum[...] += w[i, j], over the plane pixels of the bounding box [bx0, bx1) x [by0, by1) (pixels
+ *                    of a tile outside it are not blended).  `weight` is the float64 (tile, tile) feathering map.
+ *                    regularise != 0: w = 0 where |p - mean| > std * regularise_std, with the tile's mean and
+ *                    population std in float64 (fixed-order reduction into stats, 2n doubles).  No atomics: the same
+ *                    tiles give the same bits as the host loop
+ *   bp_plane_finish: out = acc / wsum (IEEE: 0 / 0 = NaN where no tile reaches) */
+enum { BP_F64 = 2 }; /* bp_plane_cut's float64 planes (views are BP_F32 / BP_BF16 only) */
+size_t bp_plane_cut_workspace(int32_t n, int32_t cut, int32_t tile);
+int bp_plane_cut(const void* plane, int32_t dtype, int32_t rows, int32_t cols, const int32_t* origins, int32_t n,
+                 int32_t cut, int32_t tile, double* scratch, size_t scratch_bytes, float* out, void* stream);
+int bp_plane_blend(const float* tiles, int32_t n, int32_t tile, const int32_t* dst, int32_t bx0, int32_t by0,
+                   int32_t bx1, int32_t by1, const double* weight, int32_t regularise, double regularise_std,
+                   double* stats, double* acc, double* wsum, int32_t rows, int32_t cols, void* stream);
+int bp_plane_finish(const double* acc, const double* wsum, int64_t count, double* out, void* stream);
+
 /* ---- latent heads: reparametrisation sampler + KL (cvae.py:63-66, 76-77, 126-130) ----------- */
 typedef struct bp_latent {
   int32_t n;      /* batch M                         */
