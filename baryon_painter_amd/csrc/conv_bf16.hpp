@@ -758,7 +758,10 @@ static inline BConfig b_config_for(const ConvGeom& g, int NT, int WN, int NW = 4
   //  output tile, and for the four-phase transposed forms -- 32->16 forward 0.71 -> 0.61 ms; the unit-stride k7 head
   //  is the same either way)
   static const bool p_all = getenv("BP_BF16_PALL") != nullptr;
-  c.persistent = c.ok && !no_p && NW == 4 && c.nchunk == 1 && c.lds_p <= 64 * 1024 && (g.IS == 2 || g.nphase > 1 || p_all);
+  // (NT <= 2: b_launch_slots has the persistent form for those only.  Without this term a wider block took the FUSED
+  //  tile geometry below into the tiled kernel, which then computed a stride-2 transposed form with out_pad wrongly)
+  c.persistent = c.ok && !no_p && NW == 4 && c.NT <= 2 && c.nchunk == 1 && c.lds_p <= 64 * 1024 &&
+                 (g.IS == 2 || g.nphase > 1 || p_all);
   if (c.persistent && !no_fuse && g.gather_transposed && g.nphase == 2) {
     // all four phases from one staged tile: the union of their halos is `spread` rows / columns larger
     const int spread = bp_t_i0(g.nphase - 1, g.pad, g.stride, g.taps) - bp_t_i0(0, g.pad, g.stride, g.taps);

@@ -343,13 +343,20 @@ static bool wide_side_chunks(const bp_conv* cv, const bp_view* X, const bp_view*
   if (X->c > 16 && Y->c <= 2) *on_x = true;
   else if (Y->c > 16 && X->c <= 2) *on_x = false;
   else return false;
-  bp_view sub = *on_x ? *X : *Y;
-  sub.c = 16;
-  size_t need = 0;
-  int ns, cxp, cyp;
+  // every chunk size that occurs needs an instantiation: the full 16 channels and the ragged tail (33 = 2 x 16 + 1 has
+  // a one-channel tail without one -- such a layer is not chunked at all, rather than refused after two chunks of dW)
+  const int wide = *on_x ? X->c : Y->c;
   const PW none{nullptr, nullptr, nullptr};
-  return bp_wgrad_small(cv, *on_x ? &sub : X, none, *on_x ? Y : &sub, none, nullptr, 0, &need, &ns, &cxp, &cyp, nullptr,
-                        true) == BP_OK;
+  for (int c = 16; c > 0; c = (c == 16 ? wide % 16 : 0)) {
+    bp_view sub = *on_x ? *X : *Y;
+    sub.c = c;
+    size_t need = 0;
+    int ns, cxp, cyp;
+    if (bp_wgrad_small(cv, *on_x ? &sub : X, none, *on_x ? Y : &sub, none, nullptr, 0, &need, &ns, &cxp, &cyp, nullptr,
+                       true) != BP_OK)
+      return false;
+  }
+  return true;
 }
 
 static PW pw_offset(const PW& p, int c0) {
@@ -501,12 +508,7 @@ int bp_wgrad_mfma(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_v
   else
     hipLaunchKernelGGL((wgrad_kernel<1>), grid, dim3(256), p.lds_bytes, st, a);
   BP_CHECK_LAUNCH();
-  WreduceArgs r{};
-  r.ws = a.ws; r.dst = dst; r.k = cv->k; r.cx = X->c; r.cy = Y->c; r.CXP = p.CXP; r.CYP = p.CYP;
-  r.nsplit = p.nsplit;
-  const int64_t total = (int64_t)Y->c * X->c * cv->k * cv->k;
-  if (r.nsplit > 64) hipLaunchKernelGGL(wgrad_reduce_kernel<16>, dim3((unsigned)((total + 63) / 64)), dim3(1024), 0, st, r);
-  else hipLaunchKernelGGL(wgrad_reduce_kernel<4>, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, st, r);
-  BP_CHECK_LAUNCH();
-  return BP_OK;
+  // (the same reduction as every other kernel's partial sums: it fills in the position of this block inside dW --
+  //  a WreduceArgs built here with cx_total left at 0 wrote every produced channel onto the first one's row)
+  return wgrad_reduce(a.ws, dst, cv->k, X->c, Y->c, p.CXP, p.CYP, p.nsplit, st);
 }

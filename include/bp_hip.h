@@ -124,7 +124,9 @@ int bp_conv_pack_jobs(const void* jobs_dev, const int64_t* first_block_dev, int3
  * the kernels take a layer / direction with the given views (NULL: any).  The packed image is opaque: for the thin
  * full-resolution layers (unit-stride k7 / k5 heads and stem, stride-2 k4 16<->32 and 32<->64) it carries a second,
  * flattened-K weight image behind the generic one (csrc/conv_bf16_flat.hip), and the run picks the kernel by the
- * views it is given -- always size the buffer with bp_conv_bf16_packed_elems. */
+ * views it is given -- always size the buffer with bp_conv_bf16_packed_elems.  bp_conv_bf16_supported answers for the tiled /
+ * flattened-K kernels; the data gradient of the 8 -> 1 k5 head (fp32 dy, bf16 dx; csrc/conv_bf16_head.hip) reads its one
+ * channel with scalar loads and also runs on dy views of any channel stride, for which the query says 0. */
 int64_t bp_conv_bf16_packed_elems(const bp_conv* cv, int dir);
 /* Which weights-stationary kernel serves this layer / direction with these views (`in` = the gathered tensor of the
  * direction: x for BP_PACK_FWD, dy for BP_PACK_BWD; `out` = the produced one): 3 = the k3 s1 128 -> 128 trunk kernel (bf16
