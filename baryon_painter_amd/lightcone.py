@@ -150,3 +150,294 @@ def _paint_plane_device(painter, delta, tile_relative_size, n_pixel_tile, z, min
     w = make_weight_map((n_pixel_tile, n_pixel_tile), falloff=falloff, sigma=sigma)
     return painter._paint_plane_device(delta, geo, z, w, batch_size=min(batch_size, n_tiles), tile_ids=ids, seed=seed,
                                        regularise_std=regularise_std, out=out)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# From painted planes to one Compton-y map (process_SLICS.py:12-66), and the light cone end to end.
+
+_SLAB = 252.5                                     # comoving thickness of a SLICS slab in Mpc/h (process_SLICS.py:26, 29)
+_projection_buffers = {}                          # per device: the float64 scratch of bp_plane_project
+
+
+def release_projection_buffers():
+    """Free the device scratch ``project_planes(on_device=True)`` keeps between calls (two float64 images of the
+    largest plane projected so far, per device)."""
+    _projection_buffers.clear()
+
+
+def _project_host(y_map, d, scale, order):
+    """One turn of the reference loop (process_SLICS.py:56-64) with its per-plane factor given as ``scale``."""
+    import scipy.ndimage
+    zoom_factor = y_map.shape[0] / d.shape[0]
+    d = d.copy()
+    d[np.isnan(d)] = 0
+    d *= scale
+    y_map += scipy.ndimage.zoom(d, zoom=zoom_factor, order=order, mode="mirror")
+
+
+def _project_device(plane, scale, y_map):
+    """y_map += zoom(nan_to_zero(plane) * scale) on the device (csrc/ymap.hip), on the current stream of the plane's
+    device, without a host synchronisation: ``plane`` a contiguous square CUDA float64 tensor (left as it is),
+    ``y_map`` a contiguous CUDA float64 (res, res) tensor."""
+    import ctypes as C
+    import torch
+    from . import _lib as L
+    lib = L.load()
+    n, res = plane.shape[0], y_map.shape[0]
+    ws = int(lib.bp_plane_project_workspace(n, res))
+    key = str(plane.device)
+    scratch = _projection_buffers.get(key)
+    if scratch is None or scratch.numel() * 8 < ws:
+        _projection_buffers.pop(key, None)
+        scratch = _projection_buffers[key] = torch.empty(max(ws // 8, 1), dtype=torch.float64, device=plane.device)
+    with torch.cuda.device(plane.device):
+        sm = C.c_void_p(torch.cuda.current_stream(plane.device).cuda_stream)
+        L.check(lib.bp_plane_project(L.ptr(plane), plane.shape[0], plane.shape[1], float(scale), L.ptr(scratch),
+                                     scratch.numel() * 8, L.ptr(y_map), res, sm), "plane project")
+
+
+def _check_map(out, resolution, device=None):
+    import torch
+    if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float64 or
+            tuple(out.shape) != (resolution, resolution) or not out.is_contiguous() or
+            (device is not None and out.device != device)):
+        raise ValueError(f"out must be a contiguous CUDA float64 ({resolution}, {resolution}) tensor"
+                         + (f" on {device}" if device is not None else ""))
+
+
+def project_planes(planes, scales, resolution, order=3, on_device=False, out=None):
+    """Sum painted planes into one (resolution, resolution) map: NaNs (pixels no tile reached) are zeroed, plane i is
+    multiplied by ``scales[i]`` and resampled to the map's resolution with ``scipy.ndimage.zoom(order, mode="mirror")``
+    (the loop of ``create_y_map``, process_SLICS.py:55-64).  ``scales[i]`` is the whole per-plane factor: the reference's
+    division by ``zoom_factor**2`` is part of it (``y_map_scales`` computes it).  The planes are not modified.
+
+    ``on_device=True`` (order 3 only; NotImplementedError otherwise, before anything is launched): planes may be NumPy
+    arrays (uploaded as float64) or square CUDA float64 tensors (used in place), and each is projected by
+    ``bp_plane_project`` (csrc/ymap.hip) in float64, within 1e-12 of the largest pixel of SciPy's result.  The map is
+    downloaded once, or, with ``out`` (a CUDA float64 (resolution, resolution) tensor), ACCUMULATED into ``out``, which
+    is returned.  The scratch is kept between calls (``release_projection_buffers``)."""
+    if not on_device:
+        if out is not None:
+            raise ValueError("out= needs on_device=True")
+        y_map = np.zeros((resolution, resolution))
+        for d, s in zip(planes, scales):
+            _project_host(y_map, d, s, order)
+        return y_map
+    if order != 3:
+        raise NotImplementedError("project_planes(on_device=True) resamples with cubic splines (order=3) only")
+    import torch
+    if out is not None:
+        _check_map(out, resolution)
+    dev = out.device if out is not None else None
+    y_map = out
+    with torch.no_grad():
+        for d, s in zip(planes, scales):
+            if isinstance(d, torch.Tensor):
+                if not d.is_cuda or d.dtype != torch.float64 or d.dim() != 2 or d.shape[0] != d.shape[1]:
+                    raise TypeError("a device plane must be a square CUDA float64 tensor")
+                if dev is not None and d.device != dev:
+                    raise ValueError(f"a plane lives on {d.device}, the map on {dev}")
+                p = d if d.is_contiguous() else d.contiguous()
+            else:
+                d = np.asarray(d)
+                if d.ndim != 2 or d.shape[0] != d.shape[1]:
+                    raise TypeError("a plane must be a square 2-d array")
+                if dev is None:
+                    dev = torch.device("cuda", torch.cuda.current_device())
+                p = torch.from_numpy(np.ascontiguousarray(d, dtype=np.float64)).to(dev)
+            if y_map is None:
+                dev = p.device
+                y_map = torch.zeros((resolution, resolution), dtype=torch.float64, device=dev)
+            _project_device(p, s, y_map)
+        if out is not None:
+            return out
+        if y_map is None:                                        # no planes
+            return np.zeros((resolution, resolution))
+        return y_map.cpu().numpy()
+
+
+def pixel_area_mean(chi_lo, chi_hi, theta_pix, scale_factor_of_chi):
+    """Mean over the comoving slab [chi_lo, chi_hi] of the squared physical size ``(chi a(chi) theta_pix)**2`` of a map
+    pixel of ``theta_pix`` radians (``A_pix_mean`` / ``L_pix`` of process_SLICS.py:13-20, with pyccl's scale factor
+    replaced by the callable ``scale_factor_of_chi``)."""
+    import scipy.integrate
+    f = lambda chi: (chi * scale_factor_of_chi(chi) * theta_pix) ** 2          # noqa: E731
+    return scipy.integrate.quad(f, chi_lo, chi_hi)[0] / (chi_hi - chi_lo)
+
+
+def slab_edges(chi, h):
+    """Comoving edges of the slabs whose mid-planes lie at ``chi``: half a slab in front of every plane (not in front
+    of the observer), one slab behind the last (process_SLICS.py:25-29)."""
+    d_A = np.array(chi, dtype=np.float64)
+    d_A -= _SLAB / h / 2
+    if d_A[0] < 0:
+        d_A[0] = 0
+    return np.append(d_A, d_A[-1] + _SLAB / h)
+
+
+def y_map_scales(n_pixel_planes, resolution, map_size, chi, scale_factor_of_chi, h):
+    """The factor that turns painted plane i (``n_pixel_planes[i]`` pixels a side) into its contribution to a Compton-y
+    map of ``resolution`` pixels and ``map_size`` degrees a side, in float64 and in the reference's order of
+    operations (process_SLICS.py:31-32, 41-50, 56, 60): ``V_c (Xe + Xi) / Xe y_fac / A_pix_eff[i] / zoom_factor**2``."""
+    d_A = slab_edges(chi, h)
+    theta_pix = map_size / resolution * np.pi / 180            # pixel size in radians
+    A_pix_eff = np.array([pixel_area_mean(d_A[i], d_A[i + 1], theta_pix, scale_factor_of_chi)
+                          for i in range(len(n_pixel_planes))])
+    y_fac = 8.125561e-16                                       # sigma_T / m_e c^2 in SI
+    mpc = 3.086e22                                             # m / Mpc
+    eV = 1.60218e-19                                           # J
+    cm = 0.01                                                  # m
+    Xe = 1.17
+    Xi = 1.08
+    V_c = (400 / h / 2048 * mpc / cm) ** 3                     # volume of a simulation cell in cm^3
+    y_fac = y_fac * eV * mpc ** -2                             # sigma_T / m_e c^2 in Mpc^2 / eV
+    scales = []
+    for i, n in enumerate(n_pixel_planes):
+        zoom_factor = resolution / n
+        scales.append(V_c * (Xe + Xi) / Xe * y_fac / A_pix_eff[i] / zoom_factor ** 2)
+    return np.array(scales, dtype=np.float64)
+
+
+def create_y_map(painted_planes, z, resolution, map_size, chi, scale_factor_of_chi, h, order=3, on_device=False,
+                 out=None):
+    """Compton-y map of ``map_size`` degrees and ``resolution`` pixels a side from the painted planes of a light cone
+    (``create_y_map`` of process_SLICS.py:12-66).  The cosmology is the caller's: ``chi[i]`` is the comoving angular
+    distance of plane i (what ``ccl.comoving_angular_distance`` gave at ``1 / (1 + z[i])``), ``scale_factor_of_chi`` a
+    callable a(chi), ``h`` the dimensionless Hubble parameter.  The rest is ``y_map_scales`` and ``project_planes``."""
+    painted_planes = list(painted_planes)
+    if not len(painted_planes) == len(z) == len(chi):
+        raise ValueError("painted_planes, z and chi need one entry per plane")
+    scales = y_map_scales([d.shape[0] for d in painted_planes], resolution, map_size, chi, scale_factor_of_chi, h)
+    return project_planes(painted_planes, scales, resolution, order=order, on_device=on_device, out=out)
+
+
+def _streams(painter, z):
+    return hasattr(painter, "paint_stream") and getattr(painter, "can_paint_stream", lambda z=0.0: True)(z)
+
+
+def paint_small_plane(painter, massplane, shift, delta_size, tile_size, mass_size, n_pixel_tile, z, seed=None,
+                      tile_id=0, subtract_minimum=False):
+    """Paint a plane whose footprint ``delta_size`` is smaller than the network's tile ``tile_size`` (the low-redshift
+    branch of ``process_SLICS``, process_SLICS.py:149-176): ONE tile, expanded to the network's size around the
+    footprint, is cut with wrap-around at ``shift`` from the periodic mass plane of ``mass_size`` (all three sizes in
+    the same unit), resampled to ``n_pixel_tile`` pixels with ``scipy.ndimage.zoom(mode="mirror")`` and painted, and
+    the central footprint of the painted tile is returned.  ``subtract_minimum``: the reference's ``SLICS_density``
+    switch (the tile's minimum is subtracted before resampling).
+
+    One tile per plane: cut and zoom stay on the host.  A painter with a device pipeline for this redshift
+    (``can_paint_stream``) paints through ``paint_stream`` with the Philox key (``seed``, ``tile_id``); ``seed=None``
+    draws a fresh key from torch's global generator.  Any other painter goes through ``paint``.  The plane is returned
+    as float64, like ``paint_plane``'s."""
+    import scipy.ndimage
+    tile = get_tile(massplane, shift, tile_relative_size=delta_size / mass_size,
+                    expansion_factor=tile_size / delta_size)
+    if subtract_minimum:
+        tile = tile - tile.min()
+    tile = scipy.ndimage.zoom(tile, zoom=n_pixel_tile / tile.shape[0], mode="mirror")
+    if _streams(painter, z):
+        if tile.shape != (n_pixel_tile, n_pixel_tile):
+            raise ValueError(f"the expanded tile zooms to {tile.shape}, not to {n_pixel_tile} pixels")
+        if seed is None:
+            import torch
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        painted = painter.paint_stream(np.asarray(tile, dtype=np.float32)[None], z, batch_size=1,
+                                       tile_ids=np.array([tile_id], dtype=np.int64), seed=seed)[0]
+    else:
+        painted = painter.paint(input=tile, z=z, transform=True, inverse_transform=True)
+    centre = (1 - delta_size / tile_size) / 2
+    # (float64 like paint_plane's planes: the projection then scales a float32 tile in double on either path)
+    return get_tile(np.asarray(painted, dtype=np.float64), shift=(centre, centre),
+                    tile_relative_size=delta_size / tile_size)
+
+
+def paint_light_cone(painter, planes, z, delta_size, tile_size, n_pixel_tile, resolution, scales, min_tile_overlap=0.5,
+                     falloff=0.05, sigma=0.5, regularise_std=None, batch_size=64, order=3, subtract_minimum=False,
+                     on_device=False, seed=None, out=None, return_planes=False):
+    """Mass planes in, one y map out (``process_SLICS`` followed by ``create_y_map``'s loop, process_SLICS.py:147-220 and
+    55-64): plane i of the light cone is painted at redshift ``z[i]`` and projected into the (resolution, resolution)
+    map with the factor ``scales[i]`` (``y_map_scales``) at once; no list of painted planes is kept.
+
+    ``planes`` is any iterable with one entry per redshift, consumed one at a time.  Where ``delta_size[i] >=
+    tile_size`` the entry is the periodic delta plane and goes through ``paint_plane`` with ``tile_relative_size =
+    tile_size / delta_size[i]`` (``min_tile_overlap``, ``falloff``, ``sigma``, ``regularise_std``, ``batch_size`` are
+    passed on).  Otherwise the entry is ``(massplane, shift, mass_size)`` and goes through ``paint_small_plane``.
+
+    One Philox key serves the whole light cone (``seed``; None draws a fresh one from torch's global generator) and
+    every tile has its own counter: a tiled plane takes as many tile ids as it has tiles, a small plane one.
+
+    ``on_device=True`` (order 3 and a painter with a device pipeline at every redshift; NotImplementedError otherwise,
+    before any random number is drawn): ``paint_plane(on_device=True, out=...)`` leaves each plane in a device buffer
+    that ``bp_plane_project`` reads on the same stream and the next plane reuses; only the finished map is downloaded,
+    or nothing with ``out`` (a CUDA float64 (resolution, resolution) tensor that is accumulated into and returned).
+    Small planes are painted as on the host path and uploaded.
+
+    Returns the map, or (map, painted planes as host arrays) with ``return_planes=True``."""
+    z, delta_size = list(z), list(delta_size)
+    if not len(z) == len(delta_size) == len(scales):
+        raise ValueError("z, delta_size and scales need one entry per plane")
+    if out is not None and not on_device:
+        raise ValueError("out= needs on_device=True")
+    # eligibility is decided UP FRONT, as in paint_plane: no random number is drawn for a light cone that cannot run
+    if on_device:
+        if order != 3:
+            raise NotImplementedError("paint_light_cone(on_device=True) resamples with cubic splines (order=3) only")
+        if not (hasattr(painter, "_paint_plane_device") and all(painter.can_paint_stream(zi) for zi in z)):
+            raise NotImplementedError("paint_light_cone(on_device=True) needs a painter with a device paint pipeline "
+                                      "(CVAEPainter.can_paint_stream) at every redshift")
+        import torch
+        dev = torch.device(painter.model.device)
+        if out is not None:
+            _check_map(out, resolution, dev)
+    if seed is None and any(_streams(painter, zi) for zi in z):
+        import torch
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    if on_device:
+        y_map = out if out is not None else torch.zeros((resolution, resolution), dtype=torch.float64, device=dev)
+        buf = None                                               # the painted plane, reused from plane to plane
+    else:
+        y_map = np.zeros((resolution, resolution))
+    kept = []
+    tile_id = 0
+    n_done = 0
+    for i, entry in enumerate(planes):
+        if i >= len(z):
+            raise ValueError("more planes than redshifts")
+        n_done += 1
+        if delta_size[i] >= tile_size:
+            rel = tile_size / delta_size[i]
+            geo = plane_geometry(entry.shape[0], rel, n_pixel_tile, min_tile_overlap)
+            kw = dict(min_tile_overlap=min_tile_overlap, falloff=falloff, sigma=sigma, regularise_std=regularise_std,
+                      batch_size=batch_size, seed=seed, first_tile_id=tile_id)
+            tile_id += geo["n_side"] ** 2
+            if on_device:
+                n_plane = geo["n_plane"]
+                if buf is None or buf.numel() < n_plane * n_plane:
+                    buf = None                                   # (let go of the smaller one first)
+                    buf = torch.empty(n_plane * n_plane, dtype=torch.float64, device=dev)
+                plane = paint_plane(painter, entry, rel, n_pixel_tile, z[i], on_device=True,
+                                    out=buf[:n_plane * n_plane].view(n_plane, n_plane), **kw)
+            else:
+                plane = paint_plane(painter, entry, rel, n_pixel_tile, z[i], **kw)
+        else:
+            massplane, shift, mass_size = entry
+            if on_device:                                        # paint_stream copies on streams of its own
+                torch.cuda.current_stream(dev).synchronize()
+            plane = paint_small_plane(painter, massplane, shift, delta_size[i], tile_size, mass_size, n_pixel_tile,
+                                      z[i], seed=seed, tile_id=tile_id, subtract_minimum=subtract_minimum)
+            tile_id += 1
+            if on_device:
+                host = plane
+                plane = torch.from_numpy(np.ascontiguousarray(plane)).to(dev)
+        if on_device:
+            _project_device(plane, scales[i], y_map)
+            if return_planes:
+                kept.append(plane.cpu().numpy() if delta_size[i] >= tile_size else host)
+        else:
+            _project_host(y_map, plane, scales[i], order)
+            if return_planes:
+                kept.append(plane)
+    if n_done != len(z):
+        raise ValueError("fewer planes than redshifts")
+    if on_device and out is None:
+        y_map = y_map.cpu().numpy()
+    return (y_map, kept) if return_planes else y_map

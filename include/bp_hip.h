@@ -366,6 +366,23 @@ int bp_plane_blend(const float* tiles, int32_t n, int32_t tile, const int32_t* d
                    double* stats, double* acc, double* wsum, int32_t rows, int32_t cols, void* stream);
 int bp_plane_finish(const double* acc, const double* wsum, int64_t count, double* out, void* stream);
 
+/* ---- Compton-y map of a light cone (lightcone.project_planes(on_device=True), process_SLICS.py:55-64) -----------
+ * A painted plane is resampled to the map's resolution and added into the y map on the device, right behind
+ * bp_plane_finish on the same stream: only the finished map comes back.
+ *   bp_plane_project: y (res, res) float64 += scipy.ndimage.zoom(where(isnan(P), 0, P) * scale, res / n, order=3,
+ *                     mode="mirror") for the square float64 plane P (rows == cols == n), in float64: cubic B-spline
+ *                     prefilter under whole-sample symmetric boundaries along axis 0 then axis 1 (parallel along the
+ *                     line: pieces of 224 samples with 32-sample warm-ups on the mirrored extension, exact to double
+ *                     precision; lines shorter than 32 samples take SciPy's closed-form initialisation), then
+ *                     tensor-product sampling at i (n - 1) / (res - 1) with mirrored taps, one thread per pixel of y.
+ *                     P is not modified.  No atomics: the same inputs give the same bits.  Needs
+ *                     bp_plane_project_workspace(n, res) bytes of `scratch` (two float64 images of the plane);
+ *                     BP_EWORKSPACE if it is shorter, BP_EINVAL for rows != cols, n < 2 or res < 2, and nothing is
+ *                     written in either case.  No host synchronisation. */
+size_t bp_plane_project_workspace(int32_t n, int32_t res);
+int bp_plane_project(const double* plane, int32_t rows, int32_t cols, double scale, double* scratch,
+                     size_t scratch_bytes, double* y, int32_t res, void* stream);
+
 /* ---- latent heads: reparametrisation sampler + KL (cvae.py:63-66, 76-77, 126-130) ----------- */
 typedef struct bp_latent {
   int32_t n;      /* batch M                         */
