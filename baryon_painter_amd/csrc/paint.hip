@@ -5,6 +5,9 @@
 //                     (merge_aux_label, utils.py:159-182): the fused form of the host transform + bp_nchw_to_view
 //   bp_paint_store    head view -> [softplus] -> inverse shift-log (data_transforms.py:97) -> NCHW tile: the fused
 //                     form of bp_view_to_nchw + the host inverse transform
+//   bp_paint_load_cam / bp_paint_store_cam   the same pair for the conditional GAN: its "shift-log-cam" transform into the
+//                     tanh range, log(x / sigma + 1) / k0 - k1 (painter.CGANPainter.transform), and the generator's tanh
+//                     head followed by the inverse, both evaluated in double as the host's NumPy expressions are
 //   bp_philox_normal  the prior noise of cvae.py:64-65 from a counter-based generator keyed on (seed, GLOBAL tile id):
 //                     a tile's sample does not depend on which batch, stream or rank paints it
 // Float semantics are those of the host path (the reference's NumPy expressions on float32 tiles, evaluated in
@@ -63,6 +66,45 @@ __global__ __launch_bounds__(RB) void paint_store_kernel(const float* src, int s
   const float e = (float)exp((double)t);            // correctly rounded float32 exponential
   const float r = e - 1.0f;
   dst[i] = (float)((double)r * k_sigma[2 * n + 1]);
+}
+
+// The CGAN's pair.  Same thread-to-element maps as the two kernels above (NHWC order on the way in, NCHW order on the
+// way out: the side that is written is the coalesced one), same 32-bit index arithmetic.  xf holds three doubles per
+// sample: {sigma, k0, k1} on the way in, {k0, k1, sigma} on the way out.
+__global__ __launch_bounds__(RB) void paint_load_cam_kernel(const float* src, int c, const double* xf, const float* aux,
+                                                            int caux, float* out, int out_cs, int out_co, int64_t hw,
+                                                            int64_t total) {
+  const int64_t i = (int64_t)blockIdx.x * RB + threadIdx.x;
+  if (i >= total) return;
+  const unsigned ct = (unsigned)(c + caux), iu = (unsigned)i, hwu = (unsigned)hw;
+  const unsigned pu = ct == 2u ? iu >> 1 : iu / ct;
+  const int ch = (int)(iu - pu * ct);
+  const unsigned nu = (hwu & (hwu - 1u)) == 0u ? pu >> (__ffs((int)hwu) - 1) : pu / hwu;
+  const int64_t p = pu, n = nu, yx = pu - nu * hwu;
+  float v;
+  if (ch < c) {
+    // np.log(x / sigma + 1) / k0 - k1 with float32 x and float64 sigma: evaluated in double, stored as float32
+    const double x = (double)src[(n * c + ch) * hw + yx];
+    v = (float)(log(x / xf[3 * n] + 1.0) / xf[3 * n + 1] - xf[3 * n + 2]);
+  } else {
+    v = aux[n * caux + (ch - c)];
+  }
+  out[p * out_cs + out_co + ch] = v;
+}
+
+__global__ __launch_bounds__(RB) void paint_store_cam_kernel(const float* src, int src_cs, int src_co, int c,
+                                                             const double* xf, float* dst, int64_t hw, int64_t total) {
+  const int64_t i = (int64_t)blockIdx.x * RB + threadIdx.x;     // NCHW destination index (coalesced writes)
+  if (i >= total) return;
+  const unsigned iu = (unsigned)i, hwu = (unsigned)hw;
+  const unsigned pl = (hwu & (hwu - 1u)) == 0u ? iu >> (__ffs((int)hwu) - 1) : iu / hwu;        // plane = n * c + ch
+  const int64_t yx = iu - pl * hwu;
+  const unsigned nu = c == 1 ? pl : pl / (unsigned)c;
+  const int ch = (int)(pl - nu * (unsigned)c);
+  const int64_t n = nu;
+  // the generator's head: the float32 tanh of bp_unary_forward; then (np.exp((y + k1) * k0) - 1) * sigma in double
+  const double y = (double)tanhf(src[(n * hw + yx) * src_cs + src_co + ch]);
+  dst[i] = (float)((exp((y + xf[3 * n + 1]) * xf[3 * n]) - 1.0) * xf[3 * n + 2]);
 }
 
 // Philox4x32-10 (Salmon et al. 2011): counter (c0..c3), key (k0, k1)
@@ -146,6 +188,31 @@ int bp_paint_store(const bp_view* src, const bp_pointwise* pw, int32_t softplus,
   if (total >= (int64_t)1 << 31) return BP_EUNSUPPORTED;
   hipLaunchKernelGGL(paint_store_kernel, dim3(nblocks(total)), dim3(RB), 0, bp_stream(stream), src->ptr, src->cstride,
                      src->coff, src->c, bp_pw(pw), softplus, k_sigma, dst_nchw, hw, total);
+  BP_CHECK_LAUNCH();
+  return BP_OK;
+}
+
+// A bf16 view is a well-formed view these two have no form for (the CGAN has no bf16 mode): BP_EUNSUPPORTED.
+int bp_paint_load_cam(const float* raw_nchw, int32_t c, const double* xf, const float* aux, int32_t caux,
+                      const bp_view* out, void* stream) {
+  if (!raw_nchw || !xf || !bp_view_ok_any(out) || c <= 0 || caux < 0 || out->c != c + caux || (caux > 0 && !aux))
+    return BP_EINVAL;
+  if (out->dtype != BP_F32) return BP_EUNSUPPORTED;
+  const int64_t hw = (int64_t)out->h * out->w, total = (int64_t)out->n * hw * (c + caux);
+  if (total >= (int64_t)1 << 31) return BP_EUNSUPPORTED;
+  hipLaunchKernelGGL(paint_load_cam_kernel, dim3(nblocks(total)), dim3(RB), 0, bp_stream(stream), raw_nchw, c, xf, aux,
+                     caux, out->ptr, out->cstride, out->coff, hw, total);
+  BP_CHECK_LAUNCH();
+  return BP_OK;
+}
+
+int bp_paint_store_cam(const bp_view* src, const double* xf, float* dst_nchw, void* stream) {
+  if (!bp_view_ok_any(src) || !xf || !dst_nchw) return BP_EINVAL;
+  if (src->dtype != BP_F32) return BP_EUNSUPPORTED;
+  const int64_t hw = (int64_t)src->h * src->w, total = (int64_t)src->n * hw * src->c;
+  if (total >= (int64_t)1 << 31) return BP_EUNSUPPORTED;
+  hipLaunchKernelGGL(paint_store_cam_kernel, dim3(nblocks(total)), dim3(RB), 0, bp_stream(stream), src->ptr,
+                     src->cstride, src->coff, src->c, xf, dst_nchw, hw, total);
   BP_CHECK_LAUNCH();
   return BP_OK;
 }

@@ -3,8 +3,8 @@ the hot path (/root/reference/baryon_painter/process_SLICS.py:68-126, 198-220).
 
 Only the integer tiling, the wrap-around tile cut, the feathering weights and the blend are here;
 the cosmology of ``create_y_map`` (pyccl / astropy) and the SLICS file handling are out of scope.
-Unlike the reference's serial per-tile loop, ``paint_plane`` sends all tiles of a plane through
-``CVAEPainter.paint_batch`` (hipGraph-captured batches).
+Unlike the reference's serial per-tile loop, ``paint_plane`` sends all tiles of a plane through the
+painter's ``paint_stream`` (hipGraph-captured batches; ``CVAEPainter`` or ``CGANPainter``) or ``paint_batch``.
 """
 import numpy as np
 
@@ -72,8 +72,9 @@ def paint_plane(painter, delta, tile_relative_size, n_pixel_tile, z, min_tile_ov
     process_SLICS.py:198-220): tiles are cut with wrap-around, resampled to the network's tile size
     if necessary, painted in batches, weighted by ``make_weight_map`` and accumulated.
 
-    Painters with a ``paint_stream`` (CVAEPainter) paint all tiles of the plane through the pipelined device path;
-    tile (j, k) of the plane draws its prior noise from Philox under the key ``seed`` and the counter
+    Painters with a ``paint_stream`` (CVAEPainter, CGANPainter) paint all tiles of the plane through the pipelined
+    device path.  The CGAN has no latent noise: ``seed`` and ``first_tile_id`` are passed on and do not affect its planes.
+    With a CVAEPainter, tile (j, k) of the plane draws its prior noise from Philox under the key ``seed`` and the counter
     ``first_tile_id + j * n_side + k``.  ``seed=None`` (default) draws a FRESH key from torch's global generator for
     every call: like the reference (fresh ``torch.randn`` per tile, cvae.py:64) two planes never share their latent
     noise unless asked to, and ``torch.manual_seed`` makes a whole light cone reproducible.  Pass an explicit ``seed``
@@ -135,7 +136,7 @@ def _paint_plane_device(painter, delta, tile_relative_size, n_pixel_tile, z, min
                         regularise_std, batch_size, seed, first_tile_id, out):
     if not (hasattr(painter, "_paint_plane_device") and painter.can_paint_stream(z)):
         raise NotImplementedError("paint_plane(on_device=True) needs a painter with a device paint pipeline "
-                                  "(CVAEPainter.can_paint_stream)")
+                                  "(CVAEPainter / CGANPainter .can_paint_stream)")
     geo = plane_geometry(delta.shape[0], tile_relative_size, n_pixel_tile, min_tile_overlap)
     n_plane, cut = geo["n_plane"], geo["cut"]
     if cut != n_pixel_tile and int(round(cut * (n_pixel_tile / cut))) != n_pixel_tile:
@@ -365,6 +366,10 @@ def paint_light_cone(painter, planes, z, delta_size, tile_size, n_pixel_tile, re
     One Philox key serves the whole light cone (``seed``; None draws a fresh one from torch's global generator) and
     every tile has its own counter: a tiled plane takes as many tile ids as it has tiles, a small plane one.
 
+    ``painter``: a ``CVAEPainter`` or a ``CGANPainter`` (the reference's light-cone driver takes either,
+    scripts/create_lightcone.py:43-54); the key and the counters below are the CVAE's latent noise and do not affect a
+    CGAN's planes.
+
     ``on_device=True`` (order 3 and a painter with a device pipeline at every redshift; NotImplementedError otherwise,
     before any random number is drawn): ``paint_plane(on_device=True, out=...)`` leaves each plane in a device buffer
     that ``bp_plane_project`` reads on the same stream and the next plane reuses; only the finished map is downloaded,
@@ -383,7 +388,7 @@ def paint_light_cone(painter, planes, z, delta_size, tile_size, n_pixel_tile, re
             raise NotImplementedError("paint_light_cone(on_device=True) resamples with cubic splines (order=3) only")
         if not (hasattr(painter, "_paint_plane_device") and all(painter.can_paint_stream(zi) for zi in z)):
             raise NotImplementedError("paint_light_cone(on_device=True) needs a painter with a device paint pipeline "
-                                      "(CVAEPainter.can_paint_stream) at every redshift")
+                                      "(CVAEPainter / CGANPainter .can_paint_stream) at every redshift")
         import torch
         dev = torch.device(painter.model.device)
         if out is not None:

@@ -173,6 +173,58 @@ class _GanPlan:
             torch.cuda.current_stream().wait_stream(self.side)     # every weight gradient is written
 
 
+class _GanPaintPlan:
+    """The generator alone, eval mode only: what painting needs of a ``_GanPlan``.  No discriminator units, no
+    ``prepare_backward`` (no gradient buffers, no weight-gradient workspace), no side stream, and the data-gradient
+    images of the packed weights are dropped.  The units are compiled exactly as ``_GanPlan`` compiles its generator
+    (same names, same ``impl``), so the forward launches -- and the bits they produce -- are the same."""
+
+    def __init__(self, model, n):
+        self.model, self.lib, self.device, self.impl, self.sync = model, model._lib, model.device, L.IMPL_AUTO, model.sync
+        self.n, self.ws_bytes, self.ws, self.prof = n, 0, None, None
+        H, W = model.tile_size, model.tile_size
+        self.y2 = Slot.new(n, H, W, 2, self.device)
+        gu, gs, tr = compile_sequential(self, "generator.", model.g_arch, model.generator, self.y2,
+                                        need_input_grad=False)
+        if [t[0] for t in tr] != ["tanh"]:
+            raise NotImplementedError("the generator must end in conv + tanh")
+        if gs.shape() != (n, H, W, 1) or gs.pw is not None:
+            raise ValueError(f"generator output {gs.shape()}")
+        self.g_units, self.g_raw = gu, gs
+        self.units = []
+        for u in gu:
+            self.units += u.body if hasattr(u, "body") else [u]
+        for u in self.units:
+            u.packed_bwd = None                   # (maybe_pack skips a direction that has no image)
+
+    def need_ws(self, nbytes):                    # (the eval forward uses no workspace: batch-norm runs on its running
+        self.ws_bytes = max(self.ws_bytes, int(nbytes))     # statistics; the sizes are recorded and nothing is allocated)
+
+    def impl_of(self, kind, unit=None):
+        return self.impl
+
+    def prof_begin(self):
+        return None
+
+    def prof_end(self, e0, unit, kind, nstreams=1):
+        return
+
+    def forward(self):
+        for u in self.g_units:
+            u.forward(False)
+
+    def generate(self, y, zc, out):
+        """out (n, 1, H, W) = tanh(G(y, zc)): ``_GanPlan.generate`` + ``bp_view_to_nchw`` of the eval mode, the tanh
+        written straight into ``out`` (one channel: NHWC with a stride of one IS NCHW)."""
+        lib, st, n = self.lib, _stream(), self.n
+        self._keep = (y.contiguous(), zc.reshape(n, 1).contiguous())
+        L.check(lib.bp_nchw_to_view(L.ptr(self._keep[0]), 1, L.ptr(self._keep[1]), 1, C.byref(self.y2.view), st),
+                "generator input")
+        self.forward()
+        ov = L.View(out.data_ptr(), n, self.g_raw.h, self.g_raw.w, 1, 1, 0, L.F32)
+        L.check(lib.bp_unary_forward(C.byref(self.g_raw.view), None, 1, C.byref(ov), st), "tanh")
+
+
 class CGAN(torch.nn.Module):
     """Generator + discriminator with their alternating training step."""
 
@@ -198,6 +250,8 @@ class CGAN(torch.nn.Module):
         self.to(self.device)
         self.sn_layers = [m for m in self.discriminator if isinstance(m, SNConv2d)]
         self._plans = {}
+        self._paint_plans = {}          # n -> _GanPaintPlan (eval-mode generate, paint_graph)
+        self._paint_graphs = {}         # n -> the captured paint pipeline of paint_graph
         self._grads = {}
         self._flat = {}
         for name, net in (("d", self.discriminator), ("g", self.generator)):
@@ -264,15 +318,95 @@ class CGAN(torch.nn.Module):
             raise ValueError("one redshift per sample")
         return y, self.z_transform(z)
 
+    def _paint_plan(self, n):
+        if n not in self._paint_plans:
+            self._paint_plans[n] = _GanPaintPlan(self, n)
+        return self._paint_plans[n]
+
+    def release_paint_buffers(self):
+        """Free the inference plans and the captured paint graphs (they are rebuilt on the next use)."""
+        self._paint_graphs.clear()
+        self._paint_plans.clear()
+
     def generate(self, y, z):
-        """G(dm, z) -> pressure in the network's (tanh) domain, (N,1,H,W)."""
+        """G(dm, z) -> pressure in the network's (tanh) domain, (N,1,H,W).  In eval mode through the inference plan
+        (generator units only); in training mode through the training plan, whose discriminator input it fills."""
         with torch.no_grad():
             y, zc = self._inputs(y, z)
+            if not self.training:
+                out = torch.empty((y.shape[0], 1, self.tile_size, self.tile_size), device=self.device)
+                self._paint_plan(y.shape[0]).generate(y, zc, out)
+                return out
             plan = self._plan(y.shape[0])
             plan.generate(y, zc, self.training)
             out = torch.empty((y.shape[0], 1, self.tile_size, self.tile_size), device=self.device)
             L.check(self._lib.bp_view_to_nchw(C.byref(plan.v_fake_x), None, 0, L.ptr(out), _stream()), "fake layout")
             return out
+
+    # ---- hipGraph-captured paint pipeline: raw tiles in, physical tiles out
+    def paint_graph(self, n):
+        """The captured paint pipeline for batches of ``n`` RAW tiles, in the form of ``CVAE.paint_graph``: a dict with
+        ``slots``: TWO input / parameter / output buffer sets, each with its own captured graph over the SAME inference
+        plan (replay them on ONE stream).  A slot holds ``raw`` (n, 1, H, W) untransformed input tiles, ``out``
+        (n, 1, H, W) painted physical tiles, ``block`` one uint8 device buffer with the typed views ``xf_in`` /
+        ``xf_out`` (n, 3) float64 {sigma, k0, k1} / {k0, k1, sigma} of the shift-log-cam transform and its inverse and
+        ``aux`` (n, 1) float32, the conditioning plane's value z - 1 (read by the kernel at run time: one graph serves
+        every redshift), and ``graph``: bp_paint_load_cam -> generator units -> bp_paint_store_cam.  ``tile_ids`` and
+        ``seed`` are part of the block (``block_layout``: name -> (byte offset, dtype, shape)) so that one caller fills
+        either model's block; the generator has no latent noise and nothing reads them."""
+        if self.training:
+            raise RuntimeError("paint_graph is an eval-mode (paint) path: call model.train(False) first")
+        g = self._paint_graphs.get(n)
+        if g is None:
+            g = self._paint_graphs[n] = self._capture_paint_graph(n)
+        for u in g["units"]:
+            u.maybe_pack()                       # eager, a no-op unless the weights changed
+            u.maybe_bn_eval()                    # ... or the running statistics
+        return g
+
+    def _capture_paint_graph(self, n):
+        H = W = self.tile_size
+        dev = self.device
+        plan = self._paint_plan(n)
+        layout, off = {}, 0
+        for name, dt, shape in (("xf_in", torch.float64, (n, 3)), ("xf_out", torch.float64, (n, 3)),
+                                ("tile_ids", torch.int64, (n,)), ("seed", torch.int64, (1,)),
+                                ("aux", torch.float32, (n, 1))):
+            layout[name] = (off, dt, shape)
+            nb = int(torch.tensor([], dtype=dt).element_size()) * int(torch.Size(shape).numel())
+            off += (nb + 7) // 8 * 8
+        st = {"block_layout": layout, "block_bytes": off, "plan": plan, "units": plan.units}
+
+        def new_slot():
+            sl = {"raw": torch.zeros((n, 1, H, W), device=dev), "out": torch.zeros((n, 1, H, W), device=dev),
+                  "block": torch.zeros(off, device=dev, dtype=torch.uint8)}
+            for name, (o, dt, shape) in layout.items():
+                nb = int(torch.tensor([], dtype=dt).element_size()) * int(torch.Size(shape).numel())
+                sl[name] = sl["block"][o:o + nb].view(dt).view(shape)
+            sl["xf_in"].fill_(1.0)
+            sl["xf_out"].fill_(1.0)
+            return sl
+        st["slots"] = [new_slot(), new_slot()]
+
+        def run(sl):
+            lib, sm = self._lib, _stream()
+            L.check(lib.bp_paint_load_cam(L.ptr(sl["raw"]), 1, L.ptr(sl["xf_in"]), L.ptr(sl["aux"]), 1,
+                                          C.byref(plan.y2.view), sm), "paint load")
+            plan.forward()
+            L.check(lib.bp_paint_store_cam(C.byref(plan.g_raw.view), L.ptr(sl["xf_out"]), L.ptr(sl["out"]), sm),
+                    "paint store")
+
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side), torch.no_grad():
+            run(st["slots"][0])                   # warm-up outside capture (packs weights, batch-norm scale / shift)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        for sl in st["slots"]:
+            graph = torch.cuda.CUDAGraph()
+            with torch.no_grad(), torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):
+                run(sl)
+            sl["graph"] = graph
+        return st
 
     def train_step(self, x, y, z, opt_g, opt_d, capture=None):
         """One alternating iteration: D on (real, G(y).detach()), then G through the updated D.

@@ -403,103 +403,9 @@ class CVAEPainter(Painter):
         lo, hi = min(rank * per, N), min((rank + 1) * per, N)
         B = int(batch_size)
         s_in, k_in, k_out, s_out = self._shift_log_parameters(zs[lo:hi])     # (NotImplementedError before any capture)
-        g = model.paint_graph(B)
-        torch_in = isinstance(inputs, torch.Tensor)
-        result = out if out is not None else np.empty((hi - lo, H, W), np.float32)
-        torch_out = isinstance(result, torch.Tensor)
-        main = torch.cuda.current_stream(dev)
-        up, down = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
-        # Two slots = the graph's own two buffer sets (CVAE.paint_graph): uploads land where bp_paint_load reads,
-        # downloads leave from where bp_paint_store writes.  Per slot one pinned parameter block (one copy per batch).
-        layout = g["block_layout"]
-        # pinned host buffers are kept between calls (page-locking 4 x 64 MiB costs tens of milliseconds per call);
-        # release_paint_buffers() frees them; the tile buffers are only allocated for NumPy inputs / outputs
-        cache = self.__dict__.setdefault("_paint_host_buffers", {})
-        key = (B, H, W, g["block_bytes"], str(dev))
-        if key not in cache:
-            cache.clear()
-            cache[key] = [{"h_blk": torch.zeros(g["block_bytes"], dtype=torch.uint8).pin_memory(), "h_in": None,
-                           "h_out": None} for _ in range(2)]
-        slots = []
-        for gs, hb in zip(g["slots"], cache[key]):
-            h_blk = hb["h_blk"]
-            hv = {}
-            for name, (o, dt, shape) in layout.items():
-                nb = torch.tensor([], dtype=dt).element_size() * int(np.prod(shape))
-                hv[name] = h_blk[o:o + nb].view(dt).view(shape).numpy()
-            hv["seed"][0] = np.array(int(seed) & 0xFFFFFFFFFFFFFFFF, dtype=np.uint64).astype(np.int64)
-            if not torch_in and hb["h_in"] is None:
-                hb["h_in"] = torch.empty((B, 1, H, W), dtype=torch.float32).pin_memory()
-            if not torch_out and hb["h_out"] is None:
-                hb["h_out"] = torch.empty((B, 1, H, W), dtype=torch.float32).pin_memory()
-            slots.append({"g": gs, "h_blk": h_blk, "hv": hv, "h_in": hb["h_in"], "h_out": hb["h_out"],
-                          "ev_up": torch.cuda.Event(), "ev_done": torch.cuda.Event(), "ev_down": torch.cuda.Event(),
-                          "pending": None})
-
-        def harvest(sl):
-            if sl["pending"] is None:
-                return
-            a, b = sl["pending"]
-            sl["ev_down"].synchronize()
-            if not torch_out:
-                result[a - lo:b - lo] = sl["h_out"][:b - a, 0].numpy()
-            sl["pending"] = None
-
-        starts = list(range(lo, hi, B))
-
-        def upload(bi):
-            """Fill slot bi % 2's pinned buffers with batch bi and start its host-to-device copies."""
-            a = starts[bi]
-            b = min(a + B, hi)
-            m = b - a
-            sl = slots[bi % 2]
-            gs, hv = sl["g"], sl["hv"]
-            sl["ev_up"].synchronize()                     # the slot's previous upload has left its pinned buffers
-            hv["xf_in"][:m, 0], hv["xf_in"][:m, 1] = s_in[a - lo:b - lo], k_in
-            hv["xf_out"][:m, 0], hv["xf_out"][:m, 1] = k_out, s_out[a - lo:b - lo]
-            hv["aux"][:m, 0] = zs[a:b]
-            hv["tile_ids"][:m] = ids[a:b]
-            if m < B:                                     # a short last batch: pad with its last tile's parameters
-                for k in ("xf_in", "xf_out", "aux", "tile_ids"):
-                    hv[k][m:] = hv[k][m - 1]
-            if torch_in:
-                src = inputs[a:b].reshape(m, 1, H, W)
-            else:
-                sl["h_in"][:m, 0].numpy()[...] = np.asarray(inputs[a:b], dtype=np.float32)
-                src = sl["h_in"][:m]
-            up.wait_event(sl["ev_done"])                  # the slot's previous batch has been painted (inputs read)
-            with torch.cuda.stream(up):
-                gs["raw"][:m].copy_(src, non_blocking=True)
-                gs["block"].copy_(sl["h_blk"], non_blocking=True)
-                sl["ev_up"].record(up)
-
-        with torch.no_grad():
-            if starts:
-                upload(0)
-            for bi, a in enumerate(starts):
-                b = min(a + B, hi)
-                m = b - a
-                sl = slots[bi % 2]
-                gs = sl["g"]
-                # The NEXT batch's upload is enqueued BEFORE this batch's graph: copies enqueued behind a graph launch
-                # only start once that graph has drained (measured: tools/paint_probe.py -- the upload then sits on the
-                # critical path, 1.2 ms per 64 tiles); enqueued ahead of it they run beside it.
-                if bi + 1 < len(starts):
-                    upload(bi + 1)
-                harvest(sl)                                   # this slot's previous batch has left the device
-                main.wait_event(sl["ev_up"])
-                main.wait_event(sl["ev_down"])                # ... and its previous output has been downloaded
-                gs["graph"].replay()
-                sl["ev_done"].record(main)
-                down.wait_event(sl["ev_done"])
-                with torch.cuda.stream(down):
-                    dst = result[a - lo:b - lo].reshape(m, 1, H, W) if torch_out else sl["h_out"][:m]
-                    dst.copy_(gs["out"][:m], non_blocking=True)
-                    sl["ev_down"].record(down)
-                sl["pending"] = (a, b)
-            for sl in slots:
-                harvest(sl)
-            torch.cuda.synchronize(dev)
+        params = {"xf_in": np.stack([s_in, np.full_like(s_in, k_in)], axis=1),
+                  "xf_out": np.stack([np.full_like(s_out, k_out), s_out], axis=1), "aux": zs[lo:hi]}
+        result = _paint_stream_pipeline(self, model, inputs, (H, W), lo, hi, B, params, ids[lo:hi], seed, out)
         return (result, (lo, hi)) if world_size > 1 else result
 
     def _paint_plane_device(self, delta, geo, z, weight_map, batch_size, tile_ids, seed, regularise_std=None, out=None):
@@ -510,13 +416,10 @@ class CVAEPainter(Painter):
         device copy, the graph is replayed, and the slot's ``out`` is blended into float64 accumulators
         (bp_plane_blend); bp_plane_finish divides.  Returns the (n_plane, n_plane) float64 plane, or ``out`` (a CUDA
         float64 tensor of that shape) filled in place."""
-        import ctypes as C
-        from . import _lib as L
         model = self.model
         model.train(False)
-        dev = model.device
         cy, H, W = model.dim_y
-        tile, cut, n_plane = H, geo["cut"], geo["n_plane"]
+        tile = H
         if cy != 1 or H != W:
             raise NotImplementedError("device planes need single-channel square tiles")
         if tuple(weight_map.shape) != (tile, tile):
@@ -525,82 +428,10 @@ class CVAEPainter(Painter):
         B = int(batch_size)
         zs = np.full(n, float(z))
         s_in, k_in, k_out, s_out = self._shift_log_parameters(zs)          # (NotImplementedError before any capture)
-        if isinstance(delta, torch.Tensor):
-            if delta.device != torch.device(dev):
-                raise ValueError(f"delta lives on {delta.device}, the painter on {dev}")
-            d = delta if delta.is_contiguous() else delta.contiguous()
-        else:
-            d = torch.from_numpy(np.ascontiguousarray(delta)).to(dev)
-        if d.dim() != 2 or d.dtype not in (torch.float32, torch.float64):
-            raise TypeError("delta must be a 2-d float32 or float64 plane")
-        if out is not None and (not isinstance(out, torch.Tensor) or out.device != torch.device(dev) or
-                                out.dtype != torch.float64 or tuple(out.shape) != (n_plane, n_plane) or
-                                not out.is_contiguous()):
-            raise ValueError(f"out must be a contiguous float64 ({n_plane}, {n_plane}) tensor on {dev}")
-        g = model.paint_graph(B)
-        # per-plane parameter blocks, one per batch, built like paint_stream's pinned ones and uploaded once: a batch
-        # then costs one device-to-device copy of its block into the slot
-        layout = g["block_layout"]
-        n_batches = (n + B - 1) // B
-        blocks = torch.zeros((n_batches, g["block_bytes"]), dtype=torch.uint8)
-        for bi in range(n_batches):
-            a, b = bi * B, min(bi * B + B, n)
-            m = b - a
-            hv = {}
-            for name, (o, dt, shape) in layout.items():
-                nb = torch.tensor([], dtype=dt).element_size() * int(np.prod(shape))
-                hv[name] = blocks[bi, o:o + nb].view(dt).view(shape).numpy()
-            hv["seed"][0] = np.array(int(seed) & 0xFFFFFFFFFFFFFFFF, dtype=np.uint64).astype(np.int64)
-            hv["xf_in"][:m, 0], hv["xf_in"][:m, 1] = s_in[a:b], k_in
-            hv["xf_out"][:m, 0], hv["xf_out"][:m, 1] = k_out, s_out[a:b]
-            hv["aux"][:m, 0] = zs[a:b]
-            hv["tile_ids"][:m] = tile_ids[a:b]
-            if m < B:                                     # a short last batch: pad with its last tile's parameters
-                for k in ("xf_in", "xf_out", "aux", "tile_ids"):
-                    hv[k][m:] = hv[k][m - 1]
-        lib = L.load()
-        # accumulators and the resampling scratch are kept between calls (release_paint_buffers() frees them)
-        cache = self.__dict__.setdefault("_plane_device_buffers", {})
-        ws = int(lib.bp_plane_cut_workspace(B, cut, tile))
-        key = (n_plane, B, ws, str(dev))
-        if key not in cache:
-            cache.clear()
-            cache[key] = {"acc": torch.empty((n_plane, n_plane), dtype=torch.float64, device=dev),
-                          "wsum": torch.empty((n_plane, n_plane), dtype=torch.float64, device=dev),
-                          "scratch": torch.empty(max(ws // 8, 1), dtype=torch.float64, device=dev),
-                          "stats": torch.empty(2 * B, dtype=torch.float64, device=dev)}
-        buf = cache[key]
-        acc, wsum = buf["acc"], buf["wsum"]
-        result = out if out is not None else torch.empty((n_plane, n_plane), dtype=torch.float64, device=dev)
-        with torch.no_grad():
-            blocks_d = blocks.to(dev)
-            org_d = torch.from_numpy(geo["origins"]).to(dev)
-            dst_d = torch.from_numpy(geo["dst"]).to(dev)
-            w_d = torch.from_numpy(np.ascontiguousarray(weight_map, dtype=np.float64)).to(dev)
-            acc.zero_()
-            wsum.zero_()
-            sm = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            dtype = L.F32 if d.dtype == torch.float32 else L.F64
-            reg = regularise_std is not None
-            rows, cols = d.shape
-            for bi in range(n_batches):
-                a, b = bi * B, min(bi * B + B, n)
-                m = b - a
-                gs = g["slots"][bi % 2]               # (one stream: the slots' reuse is ordered by the stream itself)
-                L.check(lib.bp_plane_cut(L.ptr(d), dtype, rows, cols, C.c_void_p(org_d.data_ptr() + 8 * a), m, cut,
-                                         tile, L.ptr(buf["scratch"]), ws, L.ptr(gs["raw"]), sm), "plane cut")
-                gs["block"].copy_(blocks_d[bi])
-                gs["graph"].replay()
-                box = geo["dst"][a:b]
-                L.check(lib.bp_plane_blend(L.ptr(gs["out"]), m, tile, C.c_void_p(dst_d.data_ptr() + 8 * a),
-                                           int(box[:, 0].min()), int(box[:, 1].min()), int(box[:, 0].max()) + tile,
-                                           int(box[:, 1].max()) + tile, L.ptr(w_d), 1 if reg else 0,
-                                           float(regularise_std) if reg else 0.0, L.ptr(buf["stats"]), L.ptr(acc),
-                                           L.ptr(wsum), n_plane, n_plane, sm), "plane blend")
-            L.check(lib.bp_plane_finish(L.ptr(acc), L.ptr(wsum), n_plane * n_plane, L.ptr(result), sm), "plane finish")
-            if out is not None:
-                return out
-            return result.cpu().numpy()
+        params = {"xf_in": np.stack([s_in, np.full_like(s_in, k_in)], axis=1),
+                  "xf_out": np.stack([np.full_like(s_out, k_out), s_out], axis=1), "aux": zs}
+        return _paint_plane_pipeline(self, model, tile, delta, geo, B, params, tile_ids, seed, weight_map,
+                                     regularise_std, out)
 
     # ------------------------------------------------------------------------------ checkpoints
     def save_state_to_file(self, filename, mode="model_state_dict+metadata"):
@@ -633,6 +464,208 @@ class CVAEPainter(Painter):
             setattr(self, k, d[k])
         self.transform = d.get("transform")
         self.inverse_transform = d.get("inverse_transform")
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The device paint pipelines, shared by the painters whose model has a ``paint_graph(B)`` (models.cvae.CVAE,
+# models.cgan.CGAN): the models differ in what their captured graph does and in the columns of the transform
+# parameters, not in how batches are fed to it.  ``params``: per tile of this call, ``xf_in`` / ``xf_out`` (n, k) float64
+# rows of the graph's ``block_layout`` and ``aux`` (n,) the value of its conditioning plane.
+
+def _block_views(buf, layout):
+    """The typed NumPy views of one host parameter block (uint8 tensor) under ``layout``."""
+    hv = {}
+    for name, (o, dt, shape) in layout.items():
+        nb = torch.tensor([], dtype=dt).element_size() * int(np.prod(shape))
+        hv[name] = buf[o:o + nb].view(dt).view(shape).numpy()
+    return hv
+
+
+def _fill_block(hv, params, ids, a, b, B):
+    """Tiles [a, b) of ``params`` / ``ids`` into the views of one block of ``B`` rows."""
+    m = b - a
+    hv["xf_in"][:m] = params["xf_in"][a:b]
+    hv["xf_out"][:m] = params["xf_out"][a:b]
+    hv["aux"][:m, 0] = params["aux"][a:b]
+    hv["tile_ids"][:m] = ids[a:b]
+    if m < B:                                     # a short last batch: pad with its last tile's parameters
+        for k in ("xf_in", "xf_out", "aux", "tile_ids"):
+            hv[k][m:] = hv[k][m - 1]
+
+
+def _seed_word(seed):
+    return np.array(int(seed) & 0xFFFFFFFFFFFFFFFF, dtype=np.uint64).astype(np.int64)
+
+
+def _paint_stream_pipeline(painter, model, inputs, tile_shape, lo, hi, B, params, ids, seed, out):
+    """Tiles [lo, hi) of ``inputs`` through ``model.paint_graph(B)``: pinned double-buffered upload / replay / download
+    (``CVAEPainter.paint_stream``).  ``params`` and ``ids`` hold those tiles only.  Returns the (hi - lo, H, W) float32
+    result (``out`` if given)."""
+    H, W = tile_shape
+    dev = model.device
+    g = model.paint_graph(B)
+    torch_in = isinstance(inputs, torch.Tensor)
+    result = out if out is not None else np.empty((hi - lo, H, W), np.float32)
+    torch_out = isinstance(result, torch.Tensor)
+    main = torch.cuda.current_stream(dev)
+    up, down = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
+    # Two slots = the graph's own two buffer sets (paint_graph): uploads land where the load kernel reads, downloads
+    # leave from where the store kernel writes.  Per slot one pinned parameter block (one copy per batch).
+    layout = g["block_layout"]
+    # pinned host buffers are kept between calls (page-locking 4 x 64 MiB costs tens of milliseconds per call);
+    # release_paint_buffers() frees them; the tile buffers are only allocated for NumPy inputs / outputs
+    cache = painter.__dict__.setdefault("_paint_host_buffers", {})
+    key = (B, H, W, g["block_bytes"], str(dev))
+    if key not in cache:
+        cache.clear()
+        cache[key] = [{"h_blk": torch.zeros(g["block_bytes"], dtype=torch.uint8).pin_memory(), "h_in": None,
+                       "h_out": None} for _ in range(2)]
+    slots = []
+    for gs, hb in zip(g["slots"], cache[key]):
+        h_blk = hb["h_blk"]
+        hv = _block_views(h_blk, layout)
+        hv["seed"][0] = _seed_word(seed)
+        if not torch_in and hb["h_in"] is None:
+            hb["h_in"] = torch.empty((B, 1, H, W), dtype=torch.float32).pin_memory()
+        if not torch_out and hb["h_out"] is None:
+            hb["h_out"] = torch.empty((B, 1, H, W), dtype=torch.float32).pin_memory()
+        slots.append({"g": gs, "h_blk": h_blk, "hv": hv, "h_in": hb["h_in"], "h_out": hb["h_out"],
+                      "ev_up": torch.cuda.Event(), "ev_done": torch.cuda.Event(), "ev_down": torch.cuda.Event(),
+                      "pending": None})
+
+    def harvest(sl):
+        if sl["pending"] is None:
+            return
+        a, b = sl["pending"]
+        sl["ev_down"].synchronize()
+        if not torch_out:
+            result[a - lo:b - lo] = sl["h_out"][:b - a, 0].numpy()
+        sl["pending"] = None
+
+    starts = list(range(lo, hi, B))
+
+    def upload(bi):
+        """Fill slot bi % 2's pinned buffers with batch bi and start its host-to-device copies."""
+        a = starts[bi]
+        b = min(a + B, hi)
+        m = b - a
+        sl = slots[bi % 2]
+        gs = sl["g"]
+        sl["ev_up"].synchronize()                     # the slot's previous upload has left its pinned buffers
+        _fill_block(sl["hv"], params, ids, a - lo, b - lo, B)
+        if torch_in:
+            src = inputs[a:b].reshape(m, 1, H, W)
+        else:
+            sl["h_in"][:m, 0].numpy()[...] = np.asarray(inputs[a:b], dtype=np.float32)
+            src = sl["h_in"][:m]
+        up.wait_event(sl["ev_done"])                  # the slot's previous batch has been painted (inputs read)
+        with torch.cuda.stream(up):
+            gs["raw"][:m].copy_(src, non_blocking=True)
+            gs["block"].copy_(sl["h_blk"], non_blocking=True)
+            sl["ev_up"].record(up)
+
+    with torch.no_grad():
+        if starts:
+            upload(0)
+        for bi, a in enumerate(starts):
+            b = min(a + B, hi)
+            m = b - a
+            sl = slots[bi % 2]
+            gs = sl["g"]
+            # The NEXT batch's upload is enqueued BEFORE this batch's graph: copies enqueued behind a graph launch
+            # only start once that graph has drained (measured: tools/paint_probe.py -- the upload then sits on the
+            # critical path, 1.2 ms per 64 tiles); enqueued ahead of it they run beside it.
+            if bi + 1 < len(starts):
+                upload(bi + 1)
+            harvest(sl)                                   # this slot's previous batch has left the device
+            main.wait_event(sl["ev_up"])
+            main.wait_event(sl["ev_down"])                # ... and its previous output has been downloaded
+            gs["graph"].replay()
+            sl["ev_done"].record(main)
+            down.wait_event(sl["ev_done"])
+            with torch.cuda.stream(down):
+                dst = result[a - lo:b - lo].reshape(m, 1, H, W) if torch_out else sl["h_out"][:m]
+                dst.copy_(gs["out"][:m], non_blocking=True)
+                sl["ev_down"].record(down)
+            sl["pending"] = (a, b)
+        for sl in slots:
+            harvest(sl)
+        torch.cuda.synchronize(dev)
+    return result
+
+
+def _paint_plane_pipeline(painter, model, tile, delta, geo, B, params, tile_ids, seed, weight_map, regularise_std, out):
+    """One plane through ``model.paint_graph(B)`` on the device (``CVAEPainter._paint_plane_device``): cut, parameter
+    block, replay, blend per batch on ONE stream, then the division."""
+    import ctypes as C
+    from . import _lib as L
+    dev = model.device
+    cut, n_plane = geo["cut"], geo["n_plane"]
+    n = len(geo["origins"])
+    if isinstance(delta, torch.Tensor):
+        if delta.device != torch.device(dev):
+            raise ValueError(f"delta lives on {delta.device}, the painter on {dev}")
+        d = delta if delta.is_contiguous() else delta.contiguous()
+    else:
+        d = torch.from_numpy(np.ascontiguousarray(delta)).to(dev)
+    if d.dim() != 2 or d.dtype not in (torch.float32, torch.float64):
+        raise TypeError("delta must be a 2-d float32 or float64 plane")
+    if out is not None and (not isinstance(out, torch.Tensor) or out.device != torch.device(dev) or
+                            out.dtype != torch.float64 or tuple(out.shape) != (n_plane, n_plane) or
+                            not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous float64 ({n_plane}, {n_plane}) tensor on {dev}")
+    g = model.paint_graph(B)
+    # per-plane parameter blocks, one per batch, built like paint_stream's pinned ones and uploaded once: a batch
+    # then costs one device-to-device copy of its block into the slot
+    layout = g["block_layout"]
+    n_batches = (n + B - 1) // B
+    blocks = torch.zeros((n_batches, g["block_bytes"]), dtype=torch.uint8)
+    for bi in range(n_batches):
+        hv = _block_views(blocks[bi], layout)
+        hv["seed"][0] = _seed_word(seed)
+        _fill_block(hv, params, tile_ids, bi * B, min(bi * B + B, n), B)
+    lib = L.load()
+    # accumulators and the resampling scratch are kept between calls (release_paint_buffers() frees them)
+    cache = painter.__dict__.setdefault("_plane_device_buffers", {})
+    ws = int(lib.bp_plane_cut_workspace(B, cut, tile))
+    key = (n_plane, B, ws, str(dev))
+    if key not in cache:
+        cache.clear()
+        cache[key] = {"acc": torch.empty((n_plane, n_plane), dtype=torch.float64, device=dev),
+                      "wsum": torch.empty((n_plane, n_plane), dtype=torch.float64, device=dev),
+                      "scratch": torch.empty(max(ws // 8, 1), dtype=torch.float64, device=dev),
+                      "stats": torch.empty(2 * B, dtype=torch.float64, device=dev)}
+    buf = cache[key]
+    acc, wsum = buf["acc"], buf["wsum"]
+    result = out if out is not None else torch.empty((n_plane, n_plane), dtype=torch.float64, device=dev)
+    with torch.no_grad():
+        blocks_d = blocks.to(dev)
+        org_d = torch.from_numpy(geo["origins"]).to(dev)
+        dst_d = torch.from_numpy(geo["dst"]).to(dev)
+        w_d = torch.from_numpy(np.ascontiguousarray(weight_map, dtype=np.float64)).to(dev)
+        acc.zero_()
+        wsum.zero_()
+        sm = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        dtype = L.F32 if d.dtype == torch.float32 else L.F64
+        reg = regularise_std is not None
+        rows, cols = d.shape
+        for bi in range(n_batches):
+            a, b = bi * B, min(bi * B + B, n)
+            m = b - a
+            gs = g["slots"][bi % 2]               # (one stream: the slots' reuse is ordered by the stream itself)
+            L.check(lib.bp_plane_cut(L.ptr(d), dtype, rows, cols, C.c_void_p(org_d.data_ptr() + 8 * a), m, cut,
+                                     tile, L.ptr(buf["scratch"]), ws, L.ptr(gs["raw"]), sm), "plane cut")
+            gs["block"].copy_(blocks_d[bi])
+            gs["graph"].replay()
+            box = geo["dst"][a:b]
+            L.check(lib.bp_plane_blend(L.ptr(gs["out"]), m, tile, C.c_void_p(dst_d.data_ptr() + 8 * a),
+                                       int(box[:, 0].min()), int(box[:, 1].min()), int(box[:, 0].max()) + tile,
+                                       int(box[:, 1].max()) + tile, L.ptr(w_d), 1 if reg else 0,
+                                       float(regularise_std) if reg else 0.0, L.ptr(buf["stats"]), L.ptr(acc),
+                                       L.ptr(wsum), n_plane, n_plane, sm), "plane blend")
+        L.check(lib.bp_plane_finish(L.ptr(acc), L.ptr(wsum), n_plane * n_plane, L.ptr(result), sm), "plane finish")
+        if out is not None:
+            return out
+        return result.cpu().numpy()
 
 
 def dataloader_shuffle_order(n):
@@ -746,17 +779,30 @@ class CGANPainter(Painter):
     reference's external ``GAN_Painter`` (scripts/create_lightcone.py:47-54,
     process_SLICS.py:170-172).  Field transform: the reference's CGAN used a "shift-log-cam" map into
     the tanh range (trained_models/CGAN/fiducial/transform.pickle: log(x/sigma+1)/k0 - k1 with
-    k = [4, 1]); it is applied here on top of the dataset's statistics."""
+    k = [4, 1]); it is applied here on top of the dataset's statistics.
+
+    ``paint_batch`` / ``paint_stream`` / ``_paint_plane_device`` have ``CVAEPainter``'s signatures, so every
+    ``lightcone`` entry point takes either painter.  The generator has no latent noise: ``seed`` and ``tile_ids`` are
+    accepted and do not affect the result.
+
+    ``filename``: a state-dict path (the model is built from ``tile_size`` / ``n_res``; the painter has no statistics
+    and cannot transform until ``stats`` is set) or a ``(state, meta)`` pair as written by
+    ``save_state_to_file((state, meta))``: the model is built from the pair's ``tile_size`` / ``n_res`` and the painter
+    transforms with its statistics."""
 
     K = (4.0, 1.0)
+    META_KEYS = ("stats", "K", "tile_size", "n_res", "input_field", "label_fields")
 
     def __init__(self, training_data_set=None, tile_size=512, compute_device="cuda:0", n_res=9, filename=None):
         from .models.cgan import CGAN
         self.compute_device = compute_device
-        self.model = CGAN(tile_size=tile_size, device=compute_device, n_res=n_res)
         self.training_data = training_data_set
         self.stats = None if training_data_set is None else training_data_set.stats
         self.input_field, self.label_fields = "dm", ["pressure"]
+        self.tile_size, self.n_res = tile_size, n_res
+        if isinstance(filename, (tuple, list)):
+            self._apply_meta(self._read_meta(filename[1]))          # (the model's geometry comes from the checkpoint)
+        self.model = CGAN(tile_size=self.tile_size, device=compute_device, n_res=self.n_res)
         if filename is not None:
             self.load_state_from_file(filename, compute_device)
 
@@ -805,6 +851,7 @@ class CGANPainter(Painter):
         z = ds.sample_idx_to_redshift(i)
         return ds.get_input_sample(i, transform=False), ds.get_label_sample(i, transform=False)[0], z
 
+    # ------------------------------------------------------------------------------ inference
     def paint(self, input, z=0.0, transform=True, inverse_transform=True):
         self.model.train(False)
         y = self.transform(input, "dm", z) if transform else np.asarray(input, np.float32)
@@ -816,8 +863,130 @@ class CGANPainter(Painter):
             return self.inverse_transform(pred[0, 0], "pressure", z)
         return pred
 
+    def paint_batch(self, inputs, z, transform=True, inverse_transform=True, batch_size=64, use_graph=True):
+        """Throughput form of ``paint``: many tiles (N, H, W) with redshifts (N,) or one, in batches through the same
+        eval-mode forward, with the host transforms of ``paint``.  Returns (N, H, W) float64 physical tiles, or the
+        (N, 1, H, W) float32 network output with ``inverse_transform=False``.  ``use_graph`` is accepted for
+        ``CVAEPainter.paint_batch``'s signature and has no effect: this forward is launched eagerly (the graph-captured
+        form is ``paint_stream``)."""
+        self.model.train(False)
+        inputs = np.asarray(inputs)
+        t = self.model.tile_size
+        if inputs.ndim != 3 or inputs.shape[1:] != (t, t):
+            raise ValueError(f"Shape mismatch between input and model: {inputs.shape} vs {(1, t, t)}")
+        zs = np.broadcast_to(np.asarray(z, dtype=np.float64), (inputs.shape[0],))
+        out = []
+        for s in range(0, inputs.shape[0], batch_size):
+            chunk, zc = inputs[s:s + batch_size], zs[s:s + batch_size]
+            if transform:
+                y = np.stack([self.transform(x, "dm", float(zz)) for x, zz in zip(chunk, zc)])
+            else:
+                y = np.asarray(chunk, np.float32)
+            pred = self.model.generate(torch.from_numpy(np.ascontiguousarray(y).reshape(-1, 1, t, t)),
+                                       torch.tensor(zc, dtype=torch.float32)).cpu().numpy()
+            if inverse_transform:
+                pred = np.stack([self.inverse_transform(p[0], "pressure", float(zz)) for p, zz in zip(pred, zc)])
+            out.append(pred)
+        if not out:
+            return np.empty((0, t, t)) if inverse_transform else np.empty((0, 1, t, t), np.float32)
+        return np.concatenate(out, axis=0)
+
+    def can_paint_stream(self, z=0.0):
+        """Whether ``paint_stream`` can run: the painter has the statistics of both fields (a painter restored from a
+        bare state dict has none).  No side effects."""
+        st = self.stats
+        return st is not None and all(f in st and len(st[f]) > 0 for f in (self.input_field, self.label_fields[0]))
+
+    def _cam_parameters(self, zs):
+        """``params`` of the shared pipelines for tiles at redshifts ``zs``: the rows {sigma, k0, k1} / {k0, k1, sigma}
+        of the device transforms and the conditioning plane z - 1 as ``CGAN._inputs`` computes it, in float32."""
+        from .utils.data_transforms import interpolate_z_many
+        if not self.can_paint_stream():
+            raise NotImplementedError("paint_stream needs the statistics of both fields (CGANPainter.stats; a "
+                                      "(state, meta) checkpoint carries them)")
+        s_in = np.sqrt(interpolate_z_many(self.stats[self.input_field], zs, "var"))
+        s_out = np.sqrt(interpolate_z_many(self.stats[self.label_fields[0]], zs, "var"))
+        k0, k1 = np.full_like(s_in, self.K[0]), np.full_like(s_in, self.K[1])
+        return {"xf_in": np.stack([s_in, k0, k1], axis=1), "xf_out": np.stack([k0, k1, s_out], axis=1),
+                "aux": np.asarray(zs, np.float64).astype(np.float32) - np.float32(1.0)}
+
+    def release_paint_buffers(self):
+        """Free what the paint paths keep between calls: the pinned staging buffers of ``paint_stream``, the
+        accumulators of ``_paint_plane_device``, and the model's inference plans and captured graphs."""
+        self.__dict__.pop("_paint_host_buffers", None)
+        self.__dict__.pop("_plane_device_buffers", None)
+        self.model.release_paint_buffers()
+
+    def paint_stream(self, inputs, z, batch_size=64, tile_ids=None, seed=0, rank=0, world_size=1, out=None):
+        """Paint MANY raw tiles, as ``CVAEPainter.paint_stream`` does: ``inputs`` (N, H, W) float32 host array (NumPy,
+        memory map, or a pinned torch tensor), redshifts ``z`` (scalar or (N,)) -> (N, H, W) float32 physical tiles.
+        The shift-log-cam transform, the conditioning plane, the generator's tanh and the inverse transform run on the
+        device (``bp_paint_load_cam`` / ``bp_paint_store_cam`` around the generator, one captured hipGraph per batch
+        size on one stream); uploads and downloads go through the same pinned double buffers.  ``rank`` /
+        ``world_size``: this process paints its contiguous share and returns (block, (lo, hi)).  ``tile_ids`` and
+        ``seed`` do not affect the result (no latent noise)."""
+        model = self.model
+        model.train(False)
+        H = W = model.tile_size
+        N = len(inputs)
+        if tuple(inputs.shape[1:]) != (H, W):
+            raise ValueError(f"Shape mismatch between input and model: {tuple(inputs.shape)} vs {(1, H, W)}")
+        zs = np.broadcast_to(np.asarray(z, dtype=np.float64), (N,))
+        ids = np.arange(N, dtype=np.int64) if tile_ids is None else np.asarray(tile_ids, dtype=np.int64)
+        per = (N + world_size - 1) // world_size
+        lo, hi = min(rank * per, N), min((rank + 1) * per, N)
+        params = self._cam_parameters(zs[lo:hi])                       # (NotImplementedError before any capture)
+        result = _paint_stream_pipeline(self, model, inputs, (H, W), lo, hi, int(batch_size), params, ids[lo:hi], seed,
+                                        out)
+        return (result, (lo, hi)) if world_size > 1 else result
+
+    def _paint_plane_device(self, delta, geo, z, weight_map, batch_size, tile_ids, seed, regularise_std=None, out=None):
+        """The device form of ``lightcone.paint_plane`` (on_device=True), as ``CVAEPainter._paint_plane_device``, with
+        the CGAN's graph and parameter block."""
+        model = self.model
+        model.train(False)
+        tile = model.tile_size
+        if tuple(weight_map.shape) != (tile, tile):
+            raise ValueError(f"weight map {weight_map.shape} does not match the model's {tile}^2 tiles")
+        params = self._cam_parameters(np.full(len(geo["origins"]), float(z)))
+        return _paint_plane_pipeline(self, model, tile, delta, geo, int(batch_size), params, tile_ids, seed, weight_map,
+                                     regularise_std, out)
+
+    # ------------------------------------------------------------------------------ checkpoints
+    def _meta(self):
+        """What a painter needs besides the state dict to paint in another process."""
+        return {"stats": self.stats, "K": tuple(self.K), "tile_size": self.tile_size, "n_res": self.n_res,
+                "input_field": self.input_field, "label_fields": list(self.label_fields)}
+
+    def _apply_meta(self, d):
+        missing = [k for k in self.META_KEYS if k not in d]
+        if missing:
+            raise ValueError(f"CGAN checkpoint metadata lacks {missing}")
+        self.stats, self.K = d["stats"], tuple(d["K"])
+        self.tile_size, self.n_res = d["tile_size"], d["n_res"]
+        self.input_field, self.label_fields = d["input_field"], list(d["label_fields"])
+
+    @staticmethod
+    def _read_meta(path):
+        with open(path, "rb") as f:
+            return _pickler.load(f)
+
     def save_state_to_file(self, filename):
-        torch.save({k: v.detach().cpu() for k, v in self.model.state_dict().items()}, filename)
+        """``filename``: one path -> the state dict alone; ``(state_path, meta_path)`` -> the state dict plus the
+        pickled ``_meta()``, from which ``CGANPainter(filename=(state_path, meta_path))`` paints."""
+        state = {k: v.detach().cpu() for k, v in self.model.state_dict().items()}
+        if isinstance(filename, (tuple, list)):
+            with open(filename[1], "wb") as f:
+                _pickler.dump(self._meta(), f)
+            filename = filename[0]
+        torch.save(state, filename)
 
     def load_state_from_file(self, filename, compute_device="cuda:0"):
+        if isinstance(filename, (tuple, list)):
+            d = self._read_meta(filename[1])
+            if (d.get("tile_size"), d.get("n_res")) != (self.model.tile_size, self.n_res):
+                raise ValueError(f"checkpoint is a {d.get('tile_size')}^2 / {d.get('n_res')}-block CGAN, this painter's "
+                                 f"model a {self.model.tile_size}^2 / {self.n_res}-block one")
+            self._apply_meta(d)
+            filename = filename[0]
         self.model.load_state_dict(torch.load(filename, map_location=torch.device(compute_device)))

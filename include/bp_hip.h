@@ -329,6 +329,17 @@ int bp_paint_load2(const float* raw_nchw, int32_t c, const double* sigma_k, cons
                    const bp_view* out, const bp_view* out2, void* stream);
 int bp_paint_store(const bp_view* src, const bp_pointwise* pw, int32_t softplus, const double* k_sigma,
                    float* dst_nchw, void* stream);
+/* The same pair for the conditional GAN (painter.CGANPainter: the "shift-log-cam" transform into the tanh range and
+ * the generator's tanh head), everything after the float32 tanh in double, as the host's NumPy expressions:
+ *   bp_paint_load_cam : out[n,:,:,ch<c] = (float) (log((double) raw / xf[n][0] + 1) / xf[n][1] - xf[n][2]), xf (n,3)
+ *                       double {sigma, k0, k1}; the aux label(s) (n,caux), read from device memory (the caller stores
+ *                       z - 1 there), as constant planes in the next caux channels, as in bp_paint_load
+ *   bp_paint_store_cam: dst = (float) ((exp(((double) tanhf(src) + xf[n][1]) * xf[n][0]) - 1) * xf[n][2]), NCHW, xf
+ *                       (n,3) double {k0, k1, sigma}; tanhf is bp_unary_forward's (kind 1)
+ * fp32 views only: BP_EUNSUPPORTED for a bf16 view; BP_EINVAL (nothing written) as in bp_paint_load / bp_paint_store. */
+int bp_paint_load_cam(const float* raw_nchw, int32_t c, const double* xf, const float* aux, int32_t caux,
+                      const bp_view* out, void* stream);
+int bp_paint_store_cam(const bp_view* src, const double* xf, float* dst_nchw, void* stream);
 /* eps (L, n, per_tile) standard normal for the sampler of cvae.py:64-65 from Philox4x32-10 keyed on `seed`, counter
  * (element group, l, tile id): a tile's noise depends on (seed, its GLOBAL id) only, not on batch, stream or rank
  * (torch.randn on the device in the reference: same distribution, no reproducible stream to match). */
