@@ -120,6 +120,12 @@ SIGNATURES = {
     "bp_paint_store": (C.c_int, [_VP, _PWP, C.c_int32, _P, _P, _P]),
     "bp_paint_load_cam": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _VP, _P]),
     "bp_paint_store_cam": (C.c_int, [_VP, _P, _P, _P]),
+    "bp_split_scale_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "bp_split_scale": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_size_t,
+                                 _VP, _P]),
+    "bp_paint_load_scales2": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_size_t, _VP, _VP,
+                                        _P]),
+    "bp_paint_store_scales": (C.c_int, [_VP, _PWP, C.c_int32, C.c_int32, _P, _P, _P]),
     "bp_philox_normal": (C.c_int, [C.c_uint64, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "bp_philox_normal_dev": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "bp_plane_cut_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),

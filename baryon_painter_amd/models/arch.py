@@ -82,11 +82,17 @@ def conv_up(in_channel, channels, scales, **kw_args):
     return _chain(in_channel, channels, scales, type="transp conv", **kw_args)
 
 
-def fiducial_architecture(tile_size=512, predict_var=False, n_res=4):
+def fiducial_architecture(tile_size=512, predict_var=False, n_res=4, n_scale=1):
     """The "CVAE fiducial" network: trained_models/CVAE/fiducial/architecture.txt
     (mean head only); ``predict_var=True`` gives the two-head superset that
-    scripts/CVAE_single_scale.py:97-138 builds.  dim_z = tile_size/32."""
-    n_scale, n_aux_label, n_x_feature = 1, 1, 1
+    scripts/CVAE_single_scale.py:97-138 builds.  dim_z = tile_size/32.
+
+    ``n_scale``: channels per field of a multi-scale painter (the ``n_feature_per_field`` of its data set: the levels
+    of ``data_transforms.create_split_scale_transform``, the original included where it is kept), from which the
+    script derives dim_y, dim_x = n_x_features (one label field) and the generator's stem
+    (CVAE_single_scale.py:92-95,113); the stems that read y -- prior_z_y, q_y_in -- and q_x_in take that many channels
+    plus the aux label, and the heads end in n_x_features channels."""
+    n_aux_label, n_x_feature = 1, n_scale
     zs = tile_size // 32
     dim_z = (1, zs, zs)
     dim = (n_x_feature, tile_size, tile_size)
@@ -105,11 +111,11 @@ def fiducial_architecture(tile_size=512, predict_var=False, n_res=4):
         "dim_z": dim_z,
         "n_x_features": n_x_feature,
         "aux_label": True,
-        "prior_z_y": (conv_down(in_channel=1 + n_aux_label, channels=[8, 16, 32], scales=[2, 4, 4])
+        "prior_z_y": (conv_down(in_channel=n_scale + n_aux_label, channels=[8, 16, 32], scales=[2, 4, 4])
                       + conv_block(32, 2 * dim_z[0], kernel=5)
                       + [("unflatten", (2, *dim_z))]),
         "q_x_in": conv_down(in_channel=n_x_feature, channels=[8, 16, 32], scales=[2, 4, 4]),
-        "q_y_in": conv_down(in_channel=1 + n_aux_label, channels=[8, 16, 32], scales=[2, 4, 4]),
+        "q_y_in": conv_down(in_channel=n_scale + n_aux_label, channels=[8, 16, 32], scales=[2, 4, 4]),
         "q_x_y_out": conv_block(64, 2 * dim_z[0], kernel=5) + [("unflatten", (2, *dim_z))],
         "p_y_in": None,
         "p_z_in": conv_up(1, channels=[1, 1, 1], scales=[2, 4, 4], bias=False, batchnorm=True),

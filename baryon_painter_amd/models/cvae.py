@@ -900,7 +900,7 @@ class CVAE(torch.nn.Module):
         g["graph"].replay()
         return g["out"].clone()
 
-    def paint_graph(self, n):
+    def paint_graph(self, n, scales=None):
         """The captured paint pipeline for batches of ``n`` RAW tiles (configs[4]).  Returns a dict with ``slots``: TWO
         input / parameter / output buffer sets, each with its own captured graph over the SAME launch plans, so that a
         caller uploads batch b+1 straight into one slot and downloads batch b-1 straight out of it while the other
@@ -911,26 +911,48 @@ class CVAE(torch.nn.Module):
           (1,) int64 Philox key (read by the kernel at run time: one graph serves every seed), ``aux`` (n, 1) float32
           redshifts (``block_layout``: name -> (byte offset, dtype, shape) for a pinned host mirror),
           ``graph``; ``graph.replay()`` leaves the painted tiles of ``raw`` in ``out``.
-        The two graphs share activations: replay them on ONE stream."""
+        The two graphs share activations: replay them on ONE stream.
+
+        ``scales`` (a multi-scale painter): {"n_scale", "step_size", "include_original", "truncate"} of the split-scale
+        transform (data_transforms.create_split_scale_transform) that sits between the shift-log transform and the
+        network, whose dim_y[0] = dim_x[0] = n_scale + include_original channels are the pyramid's levels.  ``raw`` and
+        ``out`` are then (n, 1, H, W): the pyramid is built behind the transform (``bp_paint_load_scales2``) and undone
+        in front of its inverse (``bp_paint_store_scales``); a slot also names the pipeline's ``scratch`` (one per
+        stream of the graph) and the float64 filter ``weights``, which the slots share.  Without it nothing changes."""
         if self.training:
             raise RuntimeError("paint_graph is an eval-mode (paint) path: call model.train(False) first")
         key = (n, "pipeline")
+        if scales is not None:
+            scales = {"n_scale": int(scales["n_scale"]), "step_size": scales["step_size"],
+                      "include_original": bool(scales["include_original"]), "truncate": scales.get("truncate", 3.0)}
+            key = (n, "pipeline", "scales") + tuple(scales.values())
         g = self._graphs.get(key)
         if g is None:
-            g = self._capture_paint_graph(n, pipeline=True)
+            g = self._capture_paint_graph(n, pipeline=True, scales=scales)
             self._graphs[key] = g
         for u in g["units"]:
             u.maybe_pack()
             u.maybe_bn_eval()
         return g
 
-    def _capture_paint_graph(self, n, given_z=False, pipeline=False):
+    def release_scale_buffers(self):
+        """Drop the captured multi-scale paint pipelines (``paint_graph(n, scales=...)``) with their scratch and filter
+        weights; they are captured again on next use."""
+        for key in [k for k in self._graphs if isinstance(k, tuple) and len(k) > 2 and k[2] == "scales"]:
+            del self._graphs[key]
+
+    def _capture_paint_graph(self, n, given_z=False, pipeline=False, scales=None):
         """Eval-mode layers do not couple the tiles of a batch (batch-norm runs on its running statistics), so the
         batch is painted as BP_PAINT_STREAMS (default 4) sub-batches on as many streams inside one graph: kernels of different layers share
         the CUs and fill each other's stalls (the effect the training step gets from its weight-gradient
         stream)."""
         cy, H, W = self.dim_y
         cx = self.dim_x[0]
+        if scales is not None:
+            levels = scales["n_scale"] + int(scales["include_original"])
+            if not pipeline or cy != levels or cx != levels:
+                raise ValueError(f"a {levels}-level split-scale transform needs dim_y[0] = dim_x[0] = {levels}, the "
+                                 f"model has {cy} and {cx}")
         st = {"y": None if pipeline else torch.zeros((n, cy, H, W), device=self.device),
               "aux": torch.zeros((n, self.n_aux), device=self.device) if self.use_aux_label and not pipeline else None,
               "out": None if pipeline else torch.zeros((n, cx, H, W), device=self.device),
@@ -951,8 +973,8 @@ class CVAE(torch.nn.Module):
             st["block_layout"], st["block_bytes"] = layout, off
 
             def new_slot():
-                sl = {"raw": torch.zeros((n, cy, H, W), device=self.device),
-                      "out": torch.zeros((n, cx, H, W), device=self.device),
+                sl = {"raw": torch.zeros((n, 1 if scales is not None else cy, H, W), device=self.device),
+                      "out": torch.zeros((n, 1 if scales is not None else cx, H, W), device=self.device),
                       "block": torch.zeros(off, device=self.device, dtype=torch.uint8)}
                 for name, (o, dt, shape) in layout.items():
                     nb = int(torch.tensor([], dtype=dt).element_size()) * int(torch.Size(shape).numel())
@@ -974,8 +996,45 @@ class CVAE(torch.nn.Module):
                     units += u.body if hasattr(u, "body") else [u]
         st["units"] = units
         others = [torch.cuda.Stream(device=self.device) for _ in range(parts - 1)]
+        if scales is not None:
+            import numpy as np
+            from ..utils import data_transforms as T
+            sig = T.split_scale_sigmas(scales["n_scale"], scales["step_size"])
+            radii = [0] + [T.gaussian_radius(s, scales["truncate"]) for s in sig[1:]]
+            wts = np.concatenate([np.zeros(0)] + [T.gaussian_weights(s, scales["truncate"]) for s in sig[1:]])
+            ws = int(self._lib.bp_split_scale_workspace(h, H, W))
+            sc = {"n_scale": scales["n_scale"], "include_original": int(scales["include_original"]),
+                  "radii": (C.c_int32 * len(radii))(*radii), "ws": ws,
+                  "weights": torch.from_numpy(np.ascontiguousarray(wts, np.float64)).to(self.device)
+                  if len(wts) else torch.zeros(1, dtype=torch.float64, device=self.device),
+                  # one scratch per stream of the graph; the two slots replay on one stream and share them
+                  "scratch": [torch.empty(max(ws // 4, 1), device=self.device) for _ in range(parts)]}
+            st["scales"] = sc
+            for sl in st["slots"]:
+                sl["scratch"], sl["weights"] = sc["scratch"], sc["weights"]
+
+        def paint_pipeline_scales(plan, lo, sl):
+            lib, sm = self._lib, _stream()
+            plan.pack_all()
+            auxp = L.ptr(sl["aux"][lo:lo + h]) if self.use_aux_label else None
+            scratch = sc["scratch"][lo // h]
+            L.check(lib.bp_paint_load_scales2(L.ptr(sl["raw"][lo:lo + h]), L.ptr(sl["xf_in"][lo:lo + h]), auxp,
+                                              plan.caux, sc["n_scale"], sc["include_original"], L.ptr(sc["weights"]),
+                                              sc["radii"], L.ptr(scratch), sc["ws"], C.byref(plan.y2.view),
+                                              C.byref(plan.hy_slot.view), sm), "paint load (scales)")
+            plan.run_prior(False)
+            eps = st["eps"][:, lo:lo + h]
+            L.check(lib.bp_philox_normal_dev(L.ptr(sl["seed"]), L.ptr(sl["tile_ids"][lo:lo + h]), h, 1, eps.shape[-1],
+                                             L.ptr(eps), sm), "philox")
+            plan.run_latent(eps.reshape(1, h, *self.dim_z), use_q=False)
+            plan.run_generator(False)
+            L.check(lib.bp_paint_store_scales(C.byref(plan.mu_head.view), None, 1 if plan.mu_softplus else 0,
+                                              sc["include_original"], L.ptr(sl["xf_out"][lo:lo + h]),
+                                              L.ptr(sl["out"][lo:lo + h]), sm), "paint store (scales)")
 
         def paint_pipeline(plan, lo, sl):
+            if scales is not None:
+                return paint_pipeline_scales(plan, lo, sl)
             lib, sm = self._lib, _stream()
             plan.pack_all()
             auxp = L.ptr(sl["aux"][lo:lo + h]) if self.use_aux_label else None

@@ -284,6 +284,8 @@ class CVAEPainter(Painter):
         if inverse_transform and self.inverse_transform is not None:
             if len(self.label_fields) > 1:
                 raise NotImplementedError("Painting with more than one output field is not supported yet.")
+            if prediction.shape[1] != 1:       # a multi-scale head: the inverse takes one tile's (cx, H, W) channels
+                return self.inverse_transform(prediction[0], field=self.label_fields[0], z=z)
             return self.inverse_transform(prediction, field=self.label_fields[0], z=z)
         return prediction
 
@@ -311,60 +313,120 @@ class CVAEPainter(Painter):
                 sample = self.model.sample_P_graphed if graphed else self.model.sample_P
                 pred = sample(yt, aux_label=aux).cpu().numpy()
                 if inverse_transform and self.inverse_transform is not None:
-                    pred = np.stack([self.inverse_transform(p[None], field=self.label_fields[0], z=float(zz))
+                    pred = np.stack([self.inverse_transform(p[None] if p.shape[0] == 1 else p,
+                                                            field=self.label_fields[0], z=float(zz))
                                      for p, zz in zip(pred, zc)])
                 out.append(pred)
         return np.concatenate(out, axis=0)
 
     # ---- throughput pipeline (BASELINE.json configs[4]) ---------------------------------------------------------
     def _shift_log_parameters(self, zs):
-        """(sigma_in, k_in, k_out, sigma_out) per tile for the device-side transforms, read out of the compiled host
-        transforms (the reference's "shift-log" range compression, data_transforms.py:72-97); anything else has no
-        device form."""
+        """(sigma_in, k_in, k_out, sigma_out, scales) for the device-side transforms, read out of the compiled host
+        transforms: per tile the parameters of the reference's "shift-log" range compression
+        (data_transforms.py:72-97), and the description of a multi-scale painter's split-scale transform
+        (``CVAE.paint_graph``'s ``scales``) or None; anything else has no device form.  The chains with one:
+          single scale   any order of ONE shift-log range compression and the shape-only steps;
+          multi scale    forward  [shift-log, as_float32 (optional), split-scale, shape-only steps ...]
+                         inverse  [inverse split-scale, inverse shift-log, shape-only steps ...]
+                         with the same split-scale parameters on both sides -- exactly these orders: the kernels
+                         filter the transformed tile and sum in front of the inverse transform."""
         from .utils import data_transforms as T
 
         def shape_only(st):          # (by name: a transform chain restored from a checkpoint holds re-imported functions)
             return getattr(st, "__module__", None) == T.__name__ and \
                 getattr(st, "__name__", None) in ("atleast_3d", "squeeze", "as_float32")
 
-        def find(compiled, direction, field):
+        def steps_of(compiled):
             if compiled is None:
                 raise NotImplementedError("paint_stream needs the painter's transforms (transform=None has no device form)")
             func = getattr(compiled, "func", None)
-            steps = getattr(func, "steps", None) or [func]
+            return getattr(func, "steps", None) or [func]
+
+        def range_compress(st, compiled, direction, field):
+            if st.modes[field].lower() != "shift-log":
+                raise NotImplementedError("device-side transforms implement the 'shift-log' mode only")
+            return (float(st.k_values[field]), compiled.stats[field])
+
+        def find(compiled, direction, field):
             found = None
-            for st in steps:
+            for st in steps_of(compiled):
                 if isinstance(st, T._RangeCompress) and st.direction == direction and found is None:
-                    if st.modes[field].lower() != "shift-log":
-                        raise NotImplementedError("device-side transforms implement the 'shift-log' mode only")
-                    found = (float(st.k_values[field]), compiled.stats[field])
+                    found = range_compress(st, compiled, direction, field)
                 elif not shape_only(st):
                     # a custom scaling step in the chain would be silently dropped on the device path
                     raise NotImplementedError(f"transform step {st!r} has no device form")
             if found is None:
                 raise NotImplementedError("paint_stream(transform=True) needs the painter's shift-log range compression")
             return found
+
+        def find_scales(compiled, direction, field):
+            """The strict multi-scale orders; returns (range compression, split-scale step)."""
+            steps = list(steps_of(compiled))
+            if direction == 0:
+                head = [lambda st: isinstance(st, T._RangeCompress) and st.direction == 0]
+                if len(steps) > 1 and getattr(steps[1], "__name__", None) == "as_float32" and shape_only(steps[1]):
+                    head.append(shape_only)
+                head.append(lambda st: isinstance(st, T._SplitScale) and st.direction == 0)
+            else:
+                head = [lambda st: isinstance(st, T._SplitScale) and st.direction == 1,
+                        lambda st: isinstance(st, T._RangeCompress) and st.direction == 1]
+            if len(steps) < len(head) or not all(ok(st) for ok, st in zip(head, steps)) or \
+                    not all(shape_only(st) for st in steps[len(head):]):
+                raise NotImplementedError(
+                    "a split-scale chain has a device form only as [shift-log, as_float32 (optional), split-scale, "
+                    "shape-only steps] / [inverse split-scale, inverse shift-log, shape-only steps]; got "
+                    f"{[getattr(st, '__name__', type(st).__name__) for st in steps]}")
+            rc = next(st for st in steps if isinstance(st, T._RangeCompress))
+            return range_compress(rc, compiled, direction, field), next(st for st in steps if isinstance(st, T._SplitScale))
+
+        def has_split(compiled):
+            return compiled is not None and any(isinstance(st, T._SplitScale) for st in steps_of(compiled))
         if len(self.label_fields) != 1:
             raise NotImplementedError("Painting with more than one output field is not supported yet.")
-        k_in, st_in = find(self.transform, 0, self.input_field)
-        k_out, st_out = find(self.inverse_transform, 1, self.label_fields[0])
+        scales = None
+        if has_split(self.transform) or has_split(self.inverse_transform):
+            (k_in, st_in), fs = find_scales(self.transform, 0, self.input_field)
+            (k_out, st_out), bs = find_scales(self.inverse_transform, 1, self.label_fields[0])
+            if (fs.n_scale, fs.include_original) != (bs.n_scale, bs.include_original):
+                raise NotImplementedError("the split-scale transform and its inverse differ in n_scale / include_original")
+            scales = {"n_scale": fs.n_scale, "step_size": fs.step_size, "include_original": fs.include_original,
+                      "truncate": fs.truncate}
+        else:
+            k_in, st_in = find(self.transform, 0, self.input_field)
+            k_out, st_out = find(self.inverse_transform, 1, self.label_fields[0])
         s_in = np.sqrt(T.interpolate_z_many(st_in, zs, "var"))          # (vectorised: no Python call per tile)
         s_out = np.sqrt(T.interpolate_z_many(st_out, zs, "var"))
-        return s_in, k_in, k_out, s_out
+        return s_in, k_in, k_out, s_out, scales
 
     def can_paint_stream(self, z=0.0):
-        """Whether ``paint_stream`` has a device form for this painter (single-channel tiles, one label field, the
-        'shift-log' range compression on both sides, L = 1 and a prior network) -- WITHOUT side effects: nothing is
+        """Whether ``paint_stream`` has a device form for this painter (one label field, the 'shift-log' range compression
+        on both sides, L = 1 and a prior network; single-channel tiles, or a split-scale transform in the orders
+        ``_shift_log_parameters`` names whose levels are the model's dim_y[0] = dim_x[0]) -- WITHOUT side effects: nothing is
         captured, no random number is drawn.  ``lightcone.paint_plane`` asks this before it draws a plane's seed, so that
         a NotImplementedError raised later, from inside a capture, is an error and not a silent fall-back."""
         model = self.model
-        if model.dim_y[0] != 1 or getattr(model, "L", 1) != 1 or getattr(model, "prior_network", None) is None:
+        if getattr(model, "L", 1) != 1 or getattr(model, "prior_network", None) is None:
             return False
         try:
-            self._shift_log_parameters(np.atleast_1d(np.asarray(z, dtype=np.float64))[:1])
+            scales = self._shift_log_parameters(np.atleast_1d(np.asarray(z, dtype=np.float64))[:1])[4]
         except NotImplementedError:
             return False
-        return True
+        if scales is None:
+            return model.dim_y[0] == 1
+        levels = scales["n_scale"] + int(scales["include_original"])
+        return model.dim_y[0] == levels and model.dim_x[0] == levels
+
+    def _check_channels(self, scales, what):
+        """NotImplementedError unless the model's channels are what the device transforms feed (before any capture)."""
+        cy, cx = self.model.dim_y[0], self.model.dim_x[0]
+        if scales is None:
+            if cy != 1:
+                raise NotImplementedError(f"{what} single-channel input tiles (or a split-scale transform's levels)")
+        else:
+            levels = scales["n_scale"] + int(scales["include_original"])
+            if cy != levels or cx != levels:
+                raise NotImplementedError(f"{what} dim_y[0] = dim_x[0] = {levels} for this split-scale transform, the "
+                                          f"model has {cy} and {cx}")
 
     def release_paint_buffers(self):
         """Free the page-locked host staging buffers ``paint_stream`` keeps between calls: two parameter blocks plus up to
@@ -372,6 +434,8 @@ class CVAEPainter(Painter):
         as long as the painter (page-locking them costs tens of milliseconds per call, hence the cache)."""
         self.__dict__.pop("_paint_host_buffers", None)
         self.__dict__.pop("_plane_device_buffers", None)      # (and _paint_plane_device's accumulators and scratch)
+        if hasattr(self.model, "release_scale_buffers"):      # (and a multi-scale pipeline's pyramid scratch)
+            self.model.release_scale_buffers()
 
     def paint_stream(self, inputs, z, batch_size=64, tile_ids=None, seed=0, rank=0, world_size=1, out=None):
         """Paint MANY raw tiles: ``inputs`` (N, H, W) float32 host array (NumPy, memory map, or a pinned torch tensor),
@@ -392,8 +456,6 @@ class CVAEPainter(Painter):
         model.train(False)
         dev = model.device
         cy, H, W = model.dim_y
-        if cy != 1:
-            raise NotImplementedError("paint_stream paints single-channel input tiles")
         N = len(inputs)
         if tuple(inputs.shape[1:]) != (H, W):
             raise ValueError(f"Shape mismatch between input and model: {tuple(inputs.shape)} vs {model.dim_y}")
@@ -402,10 +464,11 @@ class CVAEPainter(Painter):
         per = (N + world_size - 1) // world_size
         lo, hi = min(rank * per, N), min((rank + 1) * per, N)
         B = int(batch_size)
-        s_in, k_in, k_out, s_out = self._shift_log_parameters(zs[lo:hi])     # (NotImplementedError before any capture)
+        s_in, k_in, k_out, s_out, scales = self._shift_log_parameters(zs[lo:hi])     # (NotImplementedError before any capture)
+        self._check_channels(scales, "paint_stream paints")
         params = {"xf_in": np.stack([s_in, np.full_like(s_in, k_in)], axis=1),
                   "xf_out": np.stack([np.full_like(s_out, k_out), s_out], axis=1), "aux": zs[lo:hi]}
-        result = _paint_stream_pipeline(self, model, inputs, (H, W), lo, hi, B, params, ids[lo:hi], seed, out)
+        result = _paint_stream_pipeline(self, model, inputs, (H, W), lo, hi, B, params, ids[lo:hi], seed, out, scales)
         return (result, (lo, hi)) if world_size > 1 else result
 
     def _paint_plane_device(self, delta, geo, z, weight_map, batch_size, tile_ids, seed, regularise_std=None, out=None):
@@ -420,18 +483,19 @@ class CVAEPainter(Painter):
         model.train(False)
         cy, H, W = model.dim_y
         tile = H
-        if cy != 1 or H != W:
-            raise NotImplementedError("device planes need single-channel square tiles")
+        if H != W:
+            raise NotImplementedError("device planes need square tiles")
         if tuple(weight_map.shape) != (tile, tile):
             raise ValueError(f"weight map {weight_map.shape} does not match the model's {tile}^2 tiles")
         n = len(geo["origins"])
         B = int(batch_size)
         zs = np.full(n, float(z))
-        s_in, k_in, k_out, s_out = self._shift_log_parameters(zs)          # (NotImplementedError before any capture)
+        s_in, k_in, k_out, s_out, scales = self._shift_log_parameters(zs)     # (NotImplementedError before any capture)
+        self._check_channels(scales, "device planes need")
         params = {"xf_in": np.stack([s_in, np.full_like(s_in, k_in)], axis=1),
                   "xf_out": np.stack([np.full_like(s_out, k_out), s_out], axis=1), "aux": zs}
         return _paint_plane_pipeline(self, model, tile, delta, geo, B, params, tile_ids, seed, weight_map,
-                                     regularise_std, out)
+                                     regularise_std, out, scales)
 
     # ------------------------------------------------------------------------------ checkpoints
     def save_state_to_file(self, filename, mode="model_state_dict+metadata"):
@@ -496,13 +560,14 @@ def _seed_word(seed):
     return np.array(int(seed) & 0xFFFFFFFFFFFFFFFF, dtype=np.uint64).astype(np.int64)
 
 
-def _paint_stream_pipeline(painter, model, inputs, tile_shape, lo, hi, B, params, ids, seed, out):
+def _paint_stream_pipeline(painter, model, inputs, tile_shape, lo, hi, B, params, ids, seed, out, scales=None):
     """Tiles [lo, hi) of ``inputs`` through ``model.paint_graph(B)``: pinned double-buffered upload / replay / download
     (``CVAEPainter.paint_stream``).  ``params`` and ``ids`` hold those tiles only.  Returns the (hi - lo, H, W) float32
-    result (``out`` if given)."""
+    result (``out`` if given).  ``scales``: a multi-scale CVAE painter's split-scale description (``CVAE.paint_graph``);
+    raw tiles and painted tiles are single-channel either way."""
     H, W = tile_shape
     dev = model.device
-    g = model.paint_graph(B)
+    g = model.paint_graph(B) if scales is None else model.paint_graph(B, scales=scales)
     torch_in = isinstance(inputs, torch.Tensor)
     result = out if out is not None else np.empty((hi - lo, H, W), np.float32)
     torch_out = isinstance(result, torch.Tensor)
@@ -593,7 +658,8 @@ def _paint_stream_pipeline(painter, model, inputs, tile_shape, lo, hi, B, params
     return result
 
 
-def _paint_plane_pipeline(painter, model, tile, delta, geo, B, params, tile_ids, seed, weight_map, regularise_std, out):
+def _paint_plane_pipeline(painter, model, tile, delta, geo, B, params, tile_ids, seed, weight_map, regularise_std, out,
+                          scales=None):
     """One plane through ``model.paint_graph(B)`` on the device (``CVAEPainter._paint_plane_device``): cut, parameter
     block, replay, blend per batch on ONE stream, then the division."""
     import ctypes as C
@@ -613,7 +679,7 @@ def _paint_plane_pipeline(painter, model, tile, delta, geo, B, params, tile_ids,
                             out.dtype != torch.float64 or tuple(out.shape) != (n_plane, n_plane) or
                             not out.is_contiguous()):
         raise ValueError(f"out must be a contiguous float64 ({n_plane}, {n_plane}) tensor on {dev}")
-    g = model.paint_graph(B)
+    g = model.paint_graph(B) if scales is None else model.paint_graph(B, scales=scales)
     # per-plane parameter blocks, one per batch, built like paint_stream's pinned ones and uploaded once: a batch
     # then costs one device-to-device copy of its block into the slot
     layout = g["block_layout"]

@@ -1,8 +1,8 @@
 """Field transforms applied before / after the network (NumPy, host side).
 
 Same call signature ``f(x, field, z, stats)`` and the same mode names as the reference
-(/root/reference/baryon_painter/utils/data_transforms.py:44-119); the split-scale (Gaussian
-pyramid) transform of data_transforms.py:14-42 is not part of the CVAE hot path and is omitted.
+(/root/reference/baryon_painter/utils/data_transforms.py:14-119), the split-scale (Gaussian
+pyramid) transform of data_transforms.py:14-42 included (its device form: csrc/scales.hip).
 ``stats[field][z] -> {"mean", "var"}`` is tabulated per training redshift and linearly
 interpolated in z (clamped at both ends), data_transforms.py:52-64.
 """
@@ -93,6 +93,75 @@ def create_range_compress_transforms(k_values, modes={}, eps=1e-3, sqrt_of_mean=
     (data_transforms.py:51-110): "log", "shift-log", "shift-log-2p", "log-tanh", "x/(1+x)", "1/x"."""
     return (_RangeCompress(k_values, modes, eps, sqrt_of_mean, 0),
             _RangeCompress(k_values, modes, eps, sqrt_of_mean, 1))
+
+
+def gaussian_radius(sigma, truncate=3.0):
+    """Half width of scipy.ndimage.gaussian_filter1d's kernel."""
+    return int(truncate * float(sigma) + 0.5)
+
+
+def gaussian_weights(sigma, truncate=3.0):
+    """The float64 weights scipy.ndimage.gaussian_filter1d(order=0) correlates with: exp(-0.5 / sigma^2 * k^2) for
+    k = -r .. r, divided by their float64 sum (``csrc/scales.hip`` reads these from device memory)."""
+    r = gaussian_radius(sigma, truncate)
+    sigma2 = float(sigma) * float(sigma)
+    k = np.arange(-r, r + 1)
+    phi = np.exp(-0.5 / sigma2 * k ** 2)
+    return phi / phi.sum()
+
+
+def split_scale_sigmas(n_scale, step_size):
+    """sigma of level i = 1 .. n_scale-1 (index 0 is unused: level 0 is the residual)."""
+    return [0.0] + [step_size ** i / 2 for i in range(1, n_scale)]
+
+
+class _SplitScale:
+    """One direction of the split-scale (Gaussian pyramid) transform (data_transforms.py:14-42); a picklable
+    callable ``f(x, field, z, stats)``.
+
+    Forward: d = x.copy(); for i = n_scale-1 .. 1: g = gaussian_filter(d, sigma=step_size**i / 2, truncate); scale i
+    = g; d -= g.  Scale 0 is what is left of d.  ``include_original`` puts x itself in a leading extra channel.  What
+    SciPy's filter does on a float32 tile is part of the result: axis 0 first, then axis 1; each axis accumulates in
+    float64 over the weights of ``gaussian_weights`` and is rounded to float32 once; boundary "reflect"
+    (d c b a | a b c d, folded with period 2n when the radius exceeds the line); the subtraction is the array's own
+    (float32 for a float32 tile).
+    Inverse: channel 0 with ``include_original``, the sum over the channels otherwise; RuntimeError on a wrong channel
+    count."""
+
+    def __init__(self, n_scale, step_size, include_original, truncate, direction):
+        self.n_scale, self.step_size = int(n_scale), step_size
+        self.include_original, self.truncate, self.direction = bool(include_original), truncate, direction
+
+    @property
+    def levels(self):
+        return self.n_scale + int(self.include_original)
+
+    def __call__(self, x, field, z, stats):
+        return self._inverse(x) if self.direction else self._forward(x)
+
+    def _forward(self, x):
+        from scipy.ndimage import gaussian_filter
+        inc = int(self.include_original)
+        d_in = x.copy()
+        d_out = np.zeros((self.n_scale + inc, *x.shape[-2:]), dtype=x.dtype)
+        if inc:
+            d_out[0] = x
+        for i in range(self.n_scale - 1, 0, -1):
+            d_out[i + inc] = gaussian_filter(d_in, sigma=self.step_size ** i / 2, truncate=self.truncate)
+            d_in -= d_out[i + inc]
+        d_out[inc] = d_in
+        return d_out
+
+    def _inverse(self, x):
+        if x.shape[0] != self.levels:
+            raise RuntimeError(f"Invalid shape of input. Expected x.shape[0] == {self.levels} but got {x.shape[0]}.")
+        return x[0] if self.include_original else x.sum(axis=0)
+
+
+def create_split_scale_transform(n_scale=3, step_size=4, include_original=True, truncate=3.0):
+    """(transform, inverse) pair of the reference's split-scale transform (data_transforms.py:14-42)."""
+    return (_SplitScale(n_scale, step_size, include_original, truncate, 0),
+            _SplitScale(n_scale, step_size, include_original, truncate, 1))
 
 
 def atleast_3d(x, field, z, stats):

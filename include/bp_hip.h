@@ -340,6 +340,38 @@ int bp_paint_store(const bp_view* src, const bp_pointwise* pw, int32_t softplus,
 int bp_paint_load_cam(const float* raw_nchw, int32_t c, const double* xf, const float* aux, int32_t caux,
                       const bp_view* out, void* stream);
 int bp_paint_store_cam(const bp_view* src, const double* xf, float* dst_nchw, void* stream);
+/* ---- split-scale (Gaussian pyramid) transform (utils/data_transforms.py: create_split_scale_transform) ----------
+ * The pyramid of a float32 tile x: d = x; for i = n_scale-1 .. 1: g = gaussian_filter(d, sigma_i); scale i = g;
+ * d -= g; scale 0 = d.  Channel order: [x if include_original] scale 0 .. scale n_scale-1, `levels` = n_scale +
+ * include_original channels.  The filter is scipy.ndimage.gaussian_filter's on float32 input: weights
+ * exp(-0.5 k^2 / sigma^2), k = -r .. r, divided by their float64 sum, r = int(truncate * sigma + 0.5); axis 0 first,
+ * then axis 1; each axis accumulates in float64 and is rounded to float32 once; boundary "reflect" (d c b a | a b c d),
+ * folded with period 2n when r exceeds the line; d -= g is a float32 subtraction.
+ *   weights : device, float64: the 2 r_i + 1 weights of level 1, then those of level 2, ... (computed on the host
+ *             with SciPy's expression: data_transforms.gaussian_weights); radii: HOST array of n_scale int32, entry
+ *             i = r_i (entry 0 is not read).  Both may be NULL for n_scale = 1.
+ *   scratch : bp_split_scale_workspace(n, h, w) bytes (three float32 planes of the batch), BP_EWORKSPACE if shorter
+ *   bp_split_scale       : tiles (n, h, w) float32 (rectangular tiles allowed) -> channels [coff, coff + levels) of
+ *                          `out` (out->c == levels, out->n/h/w == n/h/w); other channels of the buffer are not touched
+ *   bp_paint_load_scales2: bp_paint_load2 with the pyramid between the transform and the layout: raw (n, 1, H, W) ->
+ *                          the float32 shift-log value of bp_paint_load -> its pyramid in the first `levels` channels
+ *                          of BOTH views, the aux planes in the next caux (out->c == levels + caux)
+ *   bp_paint_store_scales: bp_paint_store for a `levels`-channel head (src->c == levels): activation and softplus per
+ *                          channel, then channel 0 (include_original) or the float32 sum ((c0 + c1) + c2) ... in
+ *                          channel order (NumPy's sum(axis=0)), then bp_paint_store's inverse shift-log expression
+ *                          unchanged; dst (n, 1, H, W)
+ * fp32 views only (BP_EUNSUPPORTED for a bf16 view, for radii whose halo does not fit the 64 KiB of LDS a launch may
+ * ask for -- r <= 96 -- and for more than 16 scales); BP_EINVAL / BP_EUNSUPPORTED / BP_EWORKSPACE are returned before
+ * anything is written.  No atomics (the same inputs give the same bits), no host synchronisation. */
+size_t bp_split_scale_workspace(int32_t n, int32_t h, int32_t w);
+int bp_split_scale(const float* tiles, int32_t n, int32_t h, int32_t w, int32_t n_scale, int32_t include_original,
+                   const double* weights, const int32_t* radii, void* scratch, size_t scratch_bytes,
+                   const bp_view* out, void* stream);
+int bp_paint_load_scales2(const float* raw_nchw, const double* sigma_k, const float* aux, int32_t caux,
+                          int32_t n_scale, int32_t include_original, const double* weights, const int32_t* radii,
+                          void* scratch, size_t scratch_bytes, const bp_view* out, const bp_view* out2, void* stream);
+int bp_paint_store_scales(const bp_view* src, const bp_pointwise* pw, int32_t softplus, int32_t include_original,
+                          const double* k_sigma, float* dst_nchw, void* stream);
 /* eps (L, n, per_tile) standard normal for the sampler of cvae.py:64-65 from Philox4x32-10 keyed on `seed`, counter
  * (element group, l, tile id): a tile's noise depends on (seed, its GLOBAL id) only, not on batch, stream or rank
  * (torch.randn on the device in the reference: same distribution, no reproducible stream to match). */
