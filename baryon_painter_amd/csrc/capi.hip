@@ -1,45 +1,9 @@
-// C ABI of the convolution entry points (include/bp_hip.h): shape validation on the host, then
-// dispatch to the MFMA kernels (conv_igemm.hip / conv_wgrad.hip) or the direct ones.
+// C ABI of the convolution entry points (include/bp_hip.h): shape validation on the host, then the dispatchers
+// declared in kernels.hpp -- conv_dispatch.hip (fp32 forward / data gradient: one table of kernel families),
+// conv_wgrad.hip (weight gradient), conv_bf16.hip (bf16) -- or the direct kernels of conv_direct.hip.
 #include "common.hpp"
+#include "kernels.hpp"
 #include <cstring>
-
-int64_t bp_igemm_packed_floats(const ConvGeom& g);
-int bp_igemm_kernel_id(const ConvGeom& g);
-int bp_igemm_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, float* packed, hipStream_t st);
-size_t bp_igemm_pack_job_bytes();
-int bp_igemm_pack_job(const ConvGeom& g, const WeightMap& wm, const float* w_torch, float* packed, void* job,
-                      int64_t* nblocks);
-int bp_igemm_pack_jobs(const void* jobs_dev, const int64_t* first_block_dev, int njobs, int64_t total_blocks,
-                       hipStream_t st);
-int bp_igemm_run(const ConvGeom& g, const bp_view* in, const PW& pw, const float* packed, const float* bias,
-                 const bp_view* out, hipStream_t st, const IgemmStatsReq* stats = nullptr);
-size_t bp_igemm_stats_workspace(const ConvGeom& g, const bp_view* in, const bp_view* out, int mode);
-int bp_direct_gather(const ConvGeom& g, const WeightMap& wm, const bp_view* in, const PW& pw, const float* w_torch,
-                     const float* bias, const bp_view* out, hipStream_t st);
-int bp_direct_wgrad(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* dst,
-                    hipStream_t st);
-size_t bp_wgrad_mfma_workspace(const bp_conv* cv, const bp_view* X, const bp_view* Y);
-int bp_wgrad_mfma(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* dst,
-                  void* workspace, size_t workspace_bytes, hipStream_t st, bool shared);
-extern "C" int bp_sums_to_float(const double* sums, int32_t c, float* dst, void* stream);
-// conv_bf16.hip
-bool bp_bf16_igemm_ok(const ConvGeom& g, const bp_view* in, const bp_view* out);
-int64_t bp_bf16_packed_elems(const ConvGeom& g);
-int bp_bf16_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, void* packed, hipStream_t st);
-int bp_bf16_igemm_run(const ConvGeom& g, const bp_view* in, const PW& pw, const void* packed, const float* bias,
-                      const bp_view* out, hipStream_t st, const IgemmStatsReq* stats = nullptr);
-size_t bp_bf16_stats_workspace(const ConvGeom& g, const bp_view* in, const bp_view* out, int mode);
-size_t bp_wgrad_bf16_workspace(const bp_conv* cv, const bp_view* X, const bp_view* Y);
-int bp_wgrad_bf16_run(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* dst,
-                      void* workspace, size_t workspace_bytes, hipStream_t st);
-
-void bp_f32_ws_set(int v);        // conv_ws_f32.hip
-void bp_f32_wgrad_ws_set(int v);  // conv_wgrad_ws_f32.hip
-void bp_bf16_wgrad_ws_set(int v); // conv_wgrad_ws_bf16.hip
-bool bp_f32_ws_ok(const ConvGeom& g, const bp_view* in, const bp_view* out, const float* bias, int stats_mode);
-void bp_bf16_ws_set(int v);       // conv_bf16_ws.hip
-int bp_bf16_ws_kind(const ConvGeom& g);
-bool bp_bf16_ws_ok(const ConvGeom& g, const bp_view* in, const bp_view* out, const float* bias, int mode);
 
 namespace {
 
@@ -60,13 +24,10 @@ size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace
 
-void bp_wgrad_private_ws(bool on);
 struct WgradPrivateWs {
   explicit WgradPrivateWs(bool on) { bp_wgrad_private_ws(on); }
   ~WgradPrivateWs() { bp_wgrad_private_ws(false); }
 };
-int bp_wgrad_defer_begin_impl();
-int bp_wgrad_defer_flush_impl(hipStream_t st, int end);
 
 extern "C" {
 

@@ -65,11 +65,6 @@ struct IgemmStatsReq {
   size_t ws_bytes;
   const BnFin* fin;         // mode 1 only; nullptr: sums only
 };
-int bp_sum_partials(const double* partial, int nblk, int n, double* out, hipStream_t st);
-int bp_sum_partials_strided(const double* partial, int nblk, int stride, int n, double* out, hipStream_t st);
-// the last stage of a statistics request: partial[nblk][n] -> sr->sums (and, with sr->fin, the finalize)
-int bp_sum_partials_req(const double* partial, int nblk, int n, const IgemmStatsReq* sr, hipStream_t st);
-
 __device__ __forceinline__ float pw_apply(const PW& pw, int ch, float x) {
   if (pw.scale == nullptr) return x;
   float t = fmaf(x, pw.scale[ch], pw.shift[ch]);

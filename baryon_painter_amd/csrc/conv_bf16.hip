@@ -4,35 +4,6 @@
 
 using namespace bpbf16;
 
-int bp_bf16_launch_cc4(const BConfig& c, const BArgs& a, bool in_bf16, bool out_bf16, dim3 grid, hipStream_t st);
-int bp_bf16_launch_cc8(const BConfig& c, const BArgs& a, bool in_bf16, bool out_bf16, dim3 grid, hipStream_t st);
-int bp_bf16_launch_cc16(const BConfig& c, const BArgs& a, bool in_bf16, bool out_bf16, dim3 grid, hipStream_t st);
-int bp_bf16_launch_cc32(const BConfig& c, const BArgs& a, bool in_bf16, bool out_bf16, dim3 grid, hipStream_t st);
-
-// conv_bf16_flat.hip: flattened-K kernel for the unit-stride k7 head layers; its weight image follows the generic one
-int64_t bp_bf16_flat_packed_elems(const ConvGeom& g);
-int bp_bf16_flat_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, u16* dst, hipStream_t st);
-bool bp_bf16_flat_ok(const ConvGeom& g, const bp_view* in, const bp_view* out, const float* bias, int stats);
-size_t bp_bf16_flat_stats_workspace(const ConvGeom& g, const bp_view* in, const bp_view* out, int mode);
-int bp_bf16_flat_run(const ConvGeom& g, const bp_view* in, const PW& pw, const u16* packed_flat, const bp_view* out,
-                     hipStream_t st, const IgemmStatsReq* sr);
-
-// conv_bf16_ws.hip: weights-stationary kernel of the 128 -> 128 k3 trunk; its weight image follows the other two
-int64_t bp_bf16_ws_packed_elems(const ConvGeom& g);
-int bp_bf16_ws_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, u16* dst, hipStream_t st);
-bool bp_bf16_ws_ok(const ConvGeom& g, const bp_view* in, const bp_view* out, const float* bias, int mode);
-size_t bp_bf16_ws_stats_workspace(const ConvGeom& g, const bp_view* in, const bp_view* out);
-int bp_bf16_ws_run(const ConvGeom& g, const bp_view* in, const PW& pw, const u16* packed_ws, const bp_view* out,
-                   hipStream_t st, const IgemmStatsReq* sr);
-
-// conv_bf16_head.hip: data gradient (+ activation backward) of the heads' 8 -> 1 k5 layer; its weight image comes last
-int64_t bp_bf16_head_packed_elems(const ConvGeom& g);
-int bp_bf16_head_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, u16* dst, hipStream_t st);
-bool bp_bf16_head_ok(const ConvGeom& g, const bp_view* in, const bp_view* out, const float* bias, int mode);
-size_t bp_bf16_head_stats_workspace(const ConvGeom& g, const bp_view* in, const bp_view* out, int mode);
-int bp_bf16_head_run(const ConvGeom& g, const bp_view* in, const u16* packed_head, const bp_view* out, hipStream_t st,
-                     const IgemmStatsReq* sr);
-
 namespace {
 
 struct BPackArgs {
@@ -76,7 +47,6 @@ __global__ __launch_bounds__(256) void pack_bf16_kernel(BPackArgs a) {
   a.dst[i] = f2bf(v);
 }
 
-
 }  // namespace
 
 // ---- entry points used by capi.hip
@@ -97,16 +67,23 @@ bool bp_bf16_igemm_ok(const ConvGeom& g, const bp_view* in, const bp_view* out) 
   return true;
 }
 
-static int64_t generic_packed_elems(const ConvGeom& g, const BConfig& c) {
-  return (int64_t)g.nphase * g.nphase * g.taps * c.nrun * c.nchunk * c.cout_padP * 32;
+// The packed image: [generic | flattened-K (conv_bf16_flat.hip) | weights-stationary (conv_bf16_ws.hip) | head
+// (conv_bf16_head.hip)], the last three where those kernels apply.  Offsets in elements; the generic image starts at 0
+// and ends where the flattened-K one starts.
+struct BLayout { int64_t generic, flat, ws, head, total; };
+static BLayout bf16_layout(const ConvGeom& g, const BConfig& c) {
+  BLayout l;
+  l.generic = 0;
+  l.flat = (int64_t)g.nphase * g.nphase * g.taps * c.nrun * c.nchunk * c.cout_padP * 32;
+  l.ws = l.flat + bp_bf16_flat_packed_elems(g);
+  l.head = l.ws + bp_bf16_ws_packed_elems(g);
+  l.total = l.head + bp_bf16_head_packed_elems(g);
+  return l;
 }
 
-// [generic image | flattened-K image (conv_bf16_flat.hip) | weights-stationary image (conv_bf16_ws.hip) | head image
-// (conv_bf16_head.hip)], the last three where those kernels apply
 int64_t bp_bf16_packed_elems(const ConvGeom& g) {
   const BConfig c = b_config(g);
-  if (!c.ok) return -1;
-  return generic_packed_elems(g, c) + bp_bf16_flat_packed_elems(g) + bp_bf16_ws_packed_elems(g) + bp_bf16_head_packed_elems(g);
+  return c.ok ? bf16_layout(g, c).total : -1;
 }
 
 int bp_bf16_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, void* packed, hipStream_t st) {
@@ -118,25 +95,24 @@ int bp_bf16_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, v
   a.transposed = g.gather_transposed; a.IS = g.IS; a.cin_g = g.cin_g; a.cout_g = g.cout_g;
   a.CC = c.CC; a.nchunk = c.nchunk; a.cout_padP = c.cout_padP; a.COB = c.COB; a.NT = c.NT; a.nrun = c.nrun;
   for (int s = 0; s < c.nrun; ++s) { a.run_xm[s] = c.run_xm[s]; a.run_xq[s] = c.run_xq[s]; }
-  a.total = generic_packed_elems(g, c);
+  const BLayout l = bf16_layout(g, c);
+  a.total = l.flat;
   hipLaunchKernelGGL(pack_bf16_kernel, dim3((unsigned)((a.total + 255) / 256)), dim3(256), 0, st, a);
   BP_CHECK_LAUNCH();
-  if (bp_bf16_flat_packed_elems(g) > 0) {
-    const int rc = bp_bf16_flat_pack(g, wm, w_torch, a.dst + a.total, st);
-    if (rc != BP_OK) return rc;
-  }
-  if (bp_bf16_ws_packed_elems(g) > 0) {
-    const int rc = bp_bf16_ws_pack(g, wm, w_torch, a.dst + a.total + bp_bf16_flat_packed_elems(g), st);
-    if (rc != BP_OK) return rc;
-  }
-  if (bp_bf16_head_packed_elems(g) > 0)
-    return bp_bf16_head_pack(g, wm, w_torch, a.dst + a.total + bp_bf16_flat_packed_elems(g) + bp_bf16_ws_packed_elems(g), st);
-  return BP_OK;
+  int rc = BP_OK;
+  if (l.ws > l.flat) rc = bp_bf16_flat_pack(g, wm, w_torch, a.dst + l.flat, st);
+  if (rc == BP_OK && l.head > l.ws) rc = bp_bf16_ws_pack(g, wm, w_torch, a.dst + l.ws, st);
+  if (rc == BP_OK && l.total > l.head) rc = bp_bf16_head_pack(g, wm, w_torch, a.dst + l.head, st);
+  return rc;
 }
 
-// conv_igemm.hip: partial rows of epilogue statistics -> sums
-size_t bp_stats_rows_bytes(int64_t rows, int C);
-int bp_stats_rows_finish(double* ws, int64_t rows, int C, const IgemmStatsReq* sr, hipStream_t st);
+// The order in which the kernels are offered a layer.  bp_bf16_stats_workspace and bp_bf16_igemm_run both walk it; what
+// each asks of a kernel differs (the run takes the head kernel only without a pending activation, the workspace asks it
+// in mode 3 only), so each walk keeps its own guards: every case holds what belongs to that kernel alone, and the one
+// gate that is not a kernel's own -- all but the head kernel need views that bp_bf16_igemm_ok accepts -- stands in front
+// of the switch.
+enum BKernel { B_HEAD, B_FLAT, B_WS, B_GENERIC };
+static const BKernel B_ORDER[] = {B_HEAD, B_FLAT, B_WS, B_GENERIC};
 
 static int64_t bf16_stat_rows(const ConvGeom& g, const BConfig& c, const bp_view* in, const bp_view* out) {
   const int qh = bp_ceil_div(out->h, g.OS), qw = bp_ceil_div(out->w, g.OS);
@@ -147,36 +123,57 @@ static int64_t bf16_stat_rows(const ConvGeom& g, const BConfig& c, const bp_view
 size_t bp_bf16_stats_workspace(const ConvGeom& g, const bp_view* in, const bp_view* out, int mode) {
   const BConfig c = b_config(g);
   if (!c.ok) return 0;
-  if (mode == 3) return bp_bf16_head_stats_workspace(g, in, out, mode);      // (activation backward: the head kernel only)
-  if (!bp_bf16_igemm_ok(g, in, out)) return 0;
-  if (bp_bf16_flat_ok(g, in, out, nullptr, mode)) return bp_bf16_flat_stats_workspace(g, in, out, mode);
-  if (mode != 1) return 0;                                    // (mode 2: the flattened-K kernels only)
-  const size_t generic = bp_stats_rows_bytes(bf16_stat_rows(g, c, in, out), g.cout_g);
-  if (bp_bf16_ws_ok(g, in, out, nullptr, mode)) {        // (the larger of the two: bp_set_option may switch kernels later)
-    const size_t ws = bp_bf16_ws_stats_workspace(g, in, out);
-    return ws > generic ? ws : generic;
+  const bool views_ok = bp_bf16_igemm_ok(g, in, out);
+  for (const BKernel k : B_ORDER) {
+    if (k != B_HEAD && !views_ok) return 0;
+    switch (k) {
+      case B_HEAD:       // (activation backward: this kernel only)
+        if (mode == 3) return bp_bf16_head_stats_workspace(g, in, out, mode);
+        break;
+      case B_FLAT:
+        if (bp_bf16_flat_ok(g, in, out, nullptr, mode)) return bp_bf16_flat_stats_workspace(g, in, out, mode);
+        break;
+      case B_WS:         // (mode 1 only; the larger of the two: bp_set_option may switch kernels later)
+        if (mode == 1 && bp_bf16_ws_ok(g, in, out, nullptr, mode)) {
+          const size_t ws = bp_bf16_ws_stats_workspace(g, in, out);
+          const size_t generic = bp_stats_rows_bytes(bf16_stat_rows(g, c, in, out), g.cout_g);
+          return ws > generic ? ws : generic;
+        }
+        break;
+      case B_GENERIC:    // (mode 1 only)
+        return mode == 1 ? bp_stats_rows_bytes(bf16_stat_rows(g, c, in, out), g.cout_g) : 0;
+    }
   }
-  return generic;
+  return 0;
 }
 
 int bp_bf16_igemm_run(const ConvGeom& g, const bp_view* in, const PW& pw, const void* packed, const float* bias,
                       const bp_view* out, hipStream_t st, const IgemmStatsReq* sr) {
   const BConfig c = b_config(g);
   if (!c.ok) return BP_EUNSUPPORTED;
-  // (the head kernel reads its one gathered channel with scalar loads: any channel stride)
-  if (!pw.scale && bp_bf16_head_ok(g, in, out, bias, sr ? sr->mode : 0))
-    return bp_bf16_head_run(g, in, reinterpret_cast<const u16*>(packed) + generic_packed_elems(g, c) +
-                            bp_bf16_flat_packed_elems(g) + bp_bf16_ws_packed_elems(g), out, st, sr);
-  if (!bp_bf16_igemm_ok(g, in, out)) return BP_EUNSUPPORTED;
-  if (bp_bf16_flat_ok(g, in, out, bias, sr ? sr->mode : 0))
-    return bp_bf16_flat_run(g, in, pw, reinterpret_cast<const u16*>(packed) + generic_packed_elems(g, c), out, st, sr);
-  if (bp_bf16_ws_ok(g, in, out, bias, sr ? sr->mode : 0))
-    return bp_bf16_ws_run(g, in, pw, reinterpret_cast<const u16*>(packed) + generic_packed_elems(g, c) +
-                          bp_bf16_flat_packed_elems(g), out, st, sr);
+  const u16* image = reinterpret_cast<const u16*>(packed);
+  const BLayout l = bf16_layout(g, c);
+  const int mode = sr ? sr->mode : 0;
+  const bool views_ok = bp_bf16_igemm_ok(g, in, out);
+  for (const BKernel k : B_ORDER) {
+    if (k != B_HEAD && !views_ok) return BP_EUNSUPPORTED;
+    switch (k) {
+      case B_HEAD:      // (it reads its one gathered channel with scalar loads: any channel stride)
+        if (!pw.scale && bp_bf16_head_ok(g, in, out, bias, mode)) return bp_bf16_head_run(g, in, image + l.head, out, st, sr);
+        break;
+      case B_FLAT:
+        if (bp_bf16_flat_ok(g, in, out, bias, mode)) return bp_bf16_flat_run(g, in, pw, image + l.flat, out, st, sr);
+        break;
+      case B_WS:
+        if (bp_bf16_ws_ok(g, in, out, bias, mode)) return bp_bf16_ws_run(g, in, pw, image + l.ws, out, st, sr);
+        break;
+      case B_GENERIC: break;      // (below)
+    }
+  }
   BArgs a{};
   a.in = in->ptr; a.in_h = in->h; a.in_w = in->w; a.in_cs = in->cstride; a.in_co = in->coff; a.cin = g.cin_g;
   a.out = out->ptr; a.out_h = out->h; a.out_w = out->w; a.out_cs = out->cstride; a.out_co = out->coff;
-  a.cout = g.cout_g; a.wp = reinterpret_cast<const u16*>(packed); a.bias = bias; a.pw = pw;
+  a.cout = g.cout_g; a.wp = image + l.generic; a.bias = bias; a.pw = pw;
   a.tapsy = g.taps; a.ISy = g.IS; a.ISx = g.IS; a.OS = g.OS; a.nphase = g.nphase;
   a.transposed = g.gather_transposed; a.stride = g.stride; a.pad = g.pad;
   a.nrun = c.nrun;

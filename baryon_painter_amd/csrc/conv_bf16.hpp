@@ -26,6 +26,7 @@
 // the configuration, the weight packing and the entry points, conv_wgrad_bf16.hip the weight gradient.
 #pragma once
 #include "common.hpp"
+#include "kernels.hpp"
 #include <cstdlib>
 
 namespace bpbf16 {
@@ -880,3 +881,9 @@ int b_launch_cc(const BConfig& c, const BArgs& a, bool ib, bool ob, dim3 grid, h
 }
 
 }  // namespace bpbf16
+
+// conv_bf16_cc*.hip: the kernels above instantiated per channel-chunk width
+int bp_bf16_launch_cc4(const bpbf16::BConfig& c, const bpbf16::BArgs& a, bool in_bf16, bool out_bf16, dim3 grid, hipStream_t st);
+int bp_bf16_launch_cc8(const bpbf16::BConfig& c, const bpbf16::BArgs& a, bool in_bf16, bool out_bf16, dim3 grid, hipStream_t st);
+int bp_bf16_launch_cc16(const bpbf16::BConfig& c, const bpbf16::BArgs& a, bool in_bf16, bool out_bf16, dim3 grid, hipStream_t st);
+int bp_bf16_launch_cc32(const bpbf16::BConfig& c, const bpbf16::BArgs& a, bool in_bf16, bool out_bf16, dim3 grid, hipStream_t st);

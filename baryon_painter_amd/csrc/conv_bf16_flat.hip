@@ -30,10 +30,6 @@
 
 using namespace bpbf16;
 
-// conv_igemm.hip: partial rows of epilogue statistics -> sums (+ the fused batch-norm finalize)
-size_t bp_stats_rows_bytes(int64_t rows, int C);
-int bp_stats_rows_finish(double* ws, int64_t rows, int C, const IgemmStatsReq* sr, hipStream_t st);
-
 namespace {
 
 struct FbArgs {

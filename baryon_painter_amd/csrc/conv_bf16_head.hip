@@ -18,11 +18,6 @@
 
 using namespace bpbf16;
 
-// conv_igemm.hip: rows of n epilogue sums per workgroup -> sr->sums
-int bp_stats_row_stride(int n);
-size_t bp_stats_rows_bytes_n(int64_t rows, int n);
-int bp_stats_rows_finish_n(double* ws, int64_t rows, int n, const IgemmStatsReq* sr, hipStream_t st);
-
 namespace {
 
 constexpr int HD_K = 5, HD_C = 8, HD_TW = 64, HD_TH = 16, HD_LW = HD_TW + 8, HD_LH = HD_TH + HD_K - 1;

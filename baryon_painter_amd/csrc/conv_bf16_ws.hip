@@ -26,9 +26,6 @@
 #include "conv_bf16.hpp"
 #include <type_traits>
 
-size_t bp_stats_rows_bytes(int64_t rows, int C);
-int bp_stats_rows_finish(double* ws, int64_t rows, int C, const IgemmStatsReq* sr, hipStream_t st);
-
 namespace {
 using namespace bpbf16;
 

@@ -3,6 +3,7 @@
 // as wave-uniform scalars.  They serve as an on-device second opinion for the MFMA kernels and
 // for shapes the MFMA kernels do not cover; the hot path uses conv_igemm.hip / conv_wgrad.hip.
 #include "common.hpp"
+#include "kernels.hpp"
 
 namespace {
 

@@ -18,6 +18,7 @@
 // K = (jy, jx, co) = 64, columns 16 neighbouring coarse positions q.  The 2 x 3 dY pixels a coarse position needs
 // are read once (16-byte reads, pixel pitch 20 floats: conflict-free) and feed both pairs.  No cross-wave sums.
 #include "common.hpp"
+#include "kernels.hpp"
 #include <cstdlib>
 
 namespace {
@@ -621,20 +622,17 @@ bool bp_enc0_fwd_ok(const ConvGeom& g) {
   return !enc_off() && !off0 && !g.gather_transposed && g.k == 4 && g.stride == 2 && g.pad == 1 &&
          (g.cin_g == 1 || g.cin_g == 2) && g.cout_g == 8;
 }
-bool bp_enc_ok(const ConvGeom& g) { return bp_enc_fwd_ok(g) || bp_enc_dgrad_ok(g) || bp_enc0_fwd_ok(g); }
-int bp_enc_kernel_id(const ConvGeom& g) { return bp_enc0_fwd_ok(g) ? 780000 + g.cin_g : (g.gather_transposed ? 770000 : 760000); }
-int64_t bp_enc_packed_floats(const ConvGeom& g) { return bp_enc0_fwd_ok(g) ? 4 * g.cin_g * 64 : 8192; }
+static bool bp_enc_ok(const ConvGeom& g) { return bp_enc_fwd_ok(g) || bp_enc_dgrad_ok(g) || bp_enc0_fwd_ok(g); }
+static int bp_enc_kernel_id(const ConvGeom& g) { return bp_enc0_fwd_ok(g) ? 780000 + g.cin_g : (g.gather_transposed ? 770000 : 760000); }
+static int64_t bp_enc_packed_floats(const ConvGeom& g) { return bp_enc0_fwd_ok(g) ? 4 * g.cin_g * 64 : 8192; }
 
-int bp_enc_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, float* packed, hipStream_t st) {
+static int bp_enc_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, float* packed, hipStream_t st) {
   if (bp_enc0_fwd_ok(g)) hipLaunchKernelGGL(enc0_fwd_pack_kernel, dim3(2), dim3(256), 0, st, w_torch, wm.sa, wm.sb, g.cin_g, packed);
   else if (bp_enc_fwd_ok(g)) hipLaunchKernelGGL(enc_fwd_pack_kernel, dim3(32), dim3(256), 0, st, w_torch, wm.sa, wm.sb, packed);
   else hipLaunchKernelGGL(enc_dgrad_pack_kernel, dim3(32), dim3(256), 0, st, w_torch, wm.sa, wm.sb, packed);
   BP_CHECK_LAUNCH();
   return BP_OK;
 }
-
-size_t bp_stats_rows_bytes(int64_t rows, int C);
-int bp_stats_rows_finish(double* ws, int64_t rows, int C, const IgemmStatsReq* sr, hipStream_t st);
 
 static int enc_fwd_grid(const bp_view* in, const bp_view* out, int* tiles_x, int* tiles_y, int* ntiles) {
   static const int per_cu = getenv("BP_ENC_WGS") ? atoi(getenv("BP_ENC_WGS")) : 2;   // (188 VGPRs: two waves per SIMD)
@@ -657,7 +655,7 @@ static int enc0_fwd_grid(const bp_view* in, const bp_view* out, int* tiles_x, in
 }
 
 // forward only: {sum y, sum y^2} per produced channel (mode 1), one row per workgroup
-size_t bp_enc_stats_workspace(const ConvGeom& g, const bp_view* in, const bp_view* out, int mode) {
+static size_t bp_enc_stats_workspace(const ConvGeom& g, const bp_view* in, const bp_view* out, int mode) {
   if (bp_enc0_fwd_ok(g) && mode == 1) {
     int tx, ty, nt;
     const int grid = enc0_fwd_grid(in, out, &tx, &ty, &nt);
@@ -669,7 +667,7 @@ size_t bp_enc_stats_workspace(const ConvGeom& g, const bp_view* in, const bp_vie
   return grid > 0 ? bp_stats_rows_bytes(grid, 16) : 0;
 }
 
-int bp_enc_run(const ConvGeom& g, const bp_view* in, const PW& pw, const float* packed, const float* bias,
+static int bp_enc_run(const ConvGeom& g, const bp_view* in, const PW& pw, const float* packed, const float* bias,
                const bp_view* out, hipStream_t st, const IgemmStatsReq* sr) {
   EncArgs a{};
   a.bias = bias;
@@ -716,6 +714,12 @@ int bp_enc_run(const ConvGeom& g, const bp_view* in, const PW& pw, const float* 
   }
   BP_CHECK_LAUNCH();
   return BP_OK;
+}
+
+const ConvFamily& bp_family_enc() {
+  static const ConvFamily f = {  "enc", bp_enc_ok, bp_enc_kernel_id, bp_enc_packed_floats, bp_enc_pack,
+                                    bp_enc_stats_workspace, bp_enc_run, false};
+  return f;
 }
 
 // Weight gradient of the same layer (either orientation: X is the 8-channel tensor at 4x the resolution of the

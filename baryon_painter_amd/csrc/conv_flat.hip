@@ -10,6 +10,7 @@
 // (pixel lm, channel kq of quad g % 2, tap column g / 2) touch 256 contiguous bytes.  Workgroups walk the tile
 // sequence with a grid stride, the next tile in flight in registers (unconditional loads from clamped coordinates).
 #include "common.hpp"
+#include "kernels.hpp"
 #include <cstdlib>
 
 namespace {
@@ -203,14 +204,14 @@ int flat_grid(int ntiles) {
 
 }  // namespace
 
-bool bp_flat_ok(const ConvGeom& g) {
+static bool bp_flat_ok(const ConvGeom& g) {
   static const bool off = getenv("BP_NOFLAT") != nullptr;
   return !off && g.k == K && g.stride == 1 && g.pad == (K - 1) / 2 && g.cin_g == CG && g.cout_g == CO && g.nphase == 1;
 }
 
-int64_t bp_flat_packed_floats() { return (int64_t)K * NG * 4 * CO; }
+static int64_t bp_flat_packed_floats(const ConvGeom&) { return (int64_t)K * NG * 4 * CO; }
 
-int bp_flat_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, float* packed, hipStream_t st) {
+static int bp_flat_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, float* packed, hipStream_t st) {
   FlatPackArgs a{w_torch, packed, wm.sa, wm.sb, g.gather_transposed};
   hipLaunchKernelGGL(flat_pack_kernel, dim3((K * NG * 4 * CO + 255) / 256), dim3(256), 0, st, a);
   BP_CHECK_LAUNCH();
@@ -220,12 +221,12 @@ int bp_flat_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, f
 static int flat_k7_tiles(const bp_view* out) { return bp_ceil_div(out->w, TW) * bp_ceil_div(out->h, TH) * out->n; }
 
 // mode-2 statistics are offered where the raw tensor (same grid as `out`) can be read 16 bytes at a time
-size_t bp_flat_stats_workspace(const bp_view* out, int mode) {
+static size_t bp_flat_stats_workspace(const bp_view* out, int mode) {
   if (mode != 2 || !bp_view_vec4(out)) return 0;
   return (size_t)flat_grid(flat_k7_tiles(out)) * 2 * CO * sizeof(double);
 }
 
-int bp_flat_run(const ConvGeom& g, const bp_view* in, const PW& pw, const float* packed, const float* bias,
+static int bp_flat_run(const ConvGeom& g, const bp_view* in, const PW& pw, const float* packed, const float* bias,
                 const bp_view* out, hipStream_t st, const IgemmStatsReq* sr) {
   FlatArgs a{};
   if (sr) {
@@ -435,15 +436,15 @@ __global__ void flat_t4_pack_kernel(FlatTPackArgs a) {
 
 }  // namespace
 
-bool bp_flat_t4_ok(const ConvGeom& g) {
+static bool bp_flat_t4_ok(const ConvGeom& g) {
   static const bool off = getenv("BP_NOFLAT") != nullptr;
   return !off && g.gather_transposed && g.k == TK && g.stride == TS && g.pad == TPAD && g.cin_g == TCG && g.cout_g == TCO &&
          g.nphase == 2;
 }
 
-int64_t bp_flat_t4_packed_floats() { return (int64_t)4 * TT * TNG * 4 * TCO; }
+static int64_t bp_flat_t4_packed_floats(const ConvGeom&) { return (int64_t)4 * TT * TNG * 4 * TCO; }
 
-int bp_flat_t4_pack(const WeightMap& wm, const float* w_torch, float* packed, hipStream_t st) {
+static int bp_flat_t4_pack(const ConvGeom&, const WeightMap& wm, const float* w_torch, float* packed, hipStream_t st) {
   FlatTPackArgs a{w_torch, packed, wm.sa, wm.sb};
   hipLaunchKernelGGL(flat_t4_pack_kernel, dim3((4 * TT * TNG * 4 * TCO + 255) / 256), dim3(256), 0, st, a);
   BP_CHECK_LAUNCH();
@@ -454,12 +455,12 @@ static int flat_t4_tiles(const bp_view* out) {
   return bp_ceil_div(bp_ceil_div(out->w, 2), TTW) * bp_ceil_div(bp_ceil_div(out->h, 2), TTH) * out->n;
 }
 
-size_t bp_flat_t4_stats_workspace(const bp_view* out) {
+static size_t bp_flat_t4_stats_workspace(const bp_view* out) {
   return (size_t)flat_grid(flat_t4_tiles(out)) * 2 * TCO * sizeof(double);
 }
 
-int bp_flat_t4_run(const bp_view* in, const PW& pw, const float* packed, const float* bias, const bp_view* out,
-                   hipStream_t st, const IgemmStatsReq* sr) {
+static int bp_flat_t4_run(const ConvGeom&, const bp_view* in, const PW& pw, const float* packed, const float* bias,
+                          const bp_view* out, hipStream_t st, const IgemmStatsReq* sr) {
   if ((sr && (bias || sr->mode != 1)) || !bp_view_vec4(out)) return BP_EUNSUPPORTED;
   FlatTArgs a{};
   a.bias = bias;
@@ -694,16 +695,16 @@ int flat_g4_grid(int ntiles) {
 
 }  // namespace
 
-bool bp_flat_g4_ok(const ConvGeom& g) {
+static bool bp_flat_g4_ok(const ConvGeom& g) {
   static const bool off = getenv("BP_NOFLAT") != nullptr || getenv("BP_NOFLATG") != nullptr;
   static const bool thin = getenv("BP_FLATG_THIN") != nullptr;     // (16 -> 32: no faster than the weights-resident igemm)
   return !off && !g.gather_transposed && g.k == GK && g.stride == GS && g.pad == GPAD && g.nphase == 1 && g.IS == GS &&
          ((g.cin_g == 32 && g.cout_g == 64) || (thin && g.cin_g == 16 && g.cout_g == 32));
 }
 
-int64_t bp_flat_g4_packed_floats(const ConvGeom& g) { return (int64_t)g.cin_g * g.cout_g * GK * GK; }
+static int64_t bp_flat_g4_packed_floats(const ConvGeom& g) { return (int64_t)g.cin_g * g.cout_g * GK * GK; }
 
-int bp_flat_g4_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, float* packed, hipStream_t st) {
+static int bp_flat_g4_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, float* packed, hipStream_t st) {
   FlatGPackArgs a{w_torch, packed, wm.sa, wm.sb, g.cin_g, g.cout_g};
   hipLaunchKernelGGL(flat_g4_pack_kernel, dim3((g.cin_g * g.cout_g * GK * GK + 255) / 256), dim3(256), 0, st, a);
   BP_CHECK_LAUNCH();
@@ -715,11 +716,11 @@ static int flat_g4_tiles(const bp_view* out) {
   return bp_ceil_div(out->w, GTW) * bp_ceil_div(out->h, flat_g4_th(out)) * out->n;
 }
 
-size_t bp_flat_g4_stats_workspace(const bp_view* out) {
+static size_t bp_flat_g4_stats_workspace(const bp_view* out) {
   return (size_t)flat_g4_grid(flat_g4_tiles(out)) * 2 * out->c * sizeof(double);
 }
 
-int bp_flat_g4_run(const ConvGeom& g, const bp_view* in, const PW& pw, const float* packed, const float* bias,
+static int bp_flat_g4_run(const ConvGeom& g, const bp_view* in, const PW& pw, const float* packed, const float* bias,
                    const bp_view* out, hipStream_t st, const IgemmStatsReq* sr) {
   if ((sr && (bias || sr->mode != 1)) || !bp_view_vec4(out)) return BP_EUNSUPPORTED;
   FlatGArgs a{};
@@ -959,16 +960,16 @@ __global__ void flat_t64_pack_kernel(FlatWPackArgs a) {
 
 static bool flat_t64_wide(const ConvGeom& g) { return g.cin_g == 64; }
 
-bool bp_flat_t64_ok(const ConvGeom& g) {
+static bool bp_flat_t64_ok(const ConvGeom& g) {
   static const bool off = getenv("BP_NOFLAT") != nullptr || getenv("BP_NOFLATW") != nullptr;
   static const bool thin = getenv("BP_FLATW_THIN") != nullptr;       // (32 -> 16 through this kernel instead of flat_t4)
   return !off && g.gather_transposed && g.k == TK && g.stride == TS && g.pad == TPAD && g.nphase == 2 &&
          ((g.cin_g == 64 && g.cout_g == 32) || (thin && g.cin_g == 32 && g.cout_g == 16));
 }
 
-int64_t bp_flat_t64_packed_floats(const ConvGeom& g) { return (int64_t)g.cin_g * g.cout_g * 16; }
+static int64_t bp_flat_t64_packed_floats(const ConvGeom& g) { return (int64_t)g.cin_g * g.cout_g * 16; }
 
-int bp_flat_t64_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, float* packed, hipStream_t st) {
+static int bp_flat_t64_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, float* packed, hipStream_t st) {
   FlatWPackArgs a{w_torch, packed, wm.sa, wm.sb, g.cin_g, g.cout_g};
   hipLaunchKernelGGL(flat_t64_pack_kernel, dim3((g.cin_g * g.cout_g * 16 + 255) / 256), dim3(256), 0, st, a);
   BP_CHECK_LAUNCH();
@@ -979,11 +980,11 @@ static int flat_t64_tiles(const bp_view* out) {
   return bp_ceil_div(bp_ceil_div(out->w, 2), WTW) * bp_ceil_div(bp_ceil_div(out->h, 2), WTH) * out->n;
 }
 
-size_t bp_flat_t64_stats_workspace(const bp_view* out) {
+static size_t bp_flat_t64_stats_workspace(const bp_view* out) {
   return (size_t)flat_g4_grid(flat_t64_tiles(out)) * 2 * out->c * sizeof(double);
 }
 
-int bp_flat_t64_run(const ConvGeom& g, const bp_view* in, const PW& pw, const float* packed, const float* bias,
+static int bp_flat_t64_run(const ConvGeom& g, const bp_view* in, const PW& pw, const float* packed, const float* bias,
                     const bp_view* out, hipStream_t st, const IgemmStatsReq* sr) {
   if ((sr && (bias || sr->mode != 1)) || !bp_view_vec4(out)) return BP_EUNSUPPORTED;
   FlatWArgs a{};
@@ -1219,23 +1220,23 @@ __global__ void flat_h7_pack_kernel(FlatHPackArgs a) {
 
 }  // namespace
 
-bool bp_flat_h7_ok(const ConvGeom& g) {
+static bool bp_flat_h7_ok(const ConvGeom& g) {
   static const bool off = getenv("BP_NOFLAT") != nullptr || getenv("BP_NOFLATH") != nullptr;
   return !off && g.k == HK && g.stride == 1 && g.pad == HPAD && g.cin_g == HCG && g.cout_g == HCO && g.nphase == 1;
 }
 
-int64_t bp_flat_h7_packed_floats() { return (int64_t)HKS * 64; }
+static int64_t bp_flat_h7_packed_floats(const ConvGeom&) { return (int64_t)HKS * 64; }
 
-int bp_flat_h7_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, float* packed, hipStream_t st) {
+static int bp_flat_h7_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, float* packed, hipStream_t st) {
   FlatHPackArgs a{w_torch, packed, wm.sa, wm.sb, g.gather_transposed};
   hipLaunchKernelGGL(flat_h7_pack_kernel, dim3((HKS * 64 + 255) / 256), dim3(256), 0, st, a);
   BP_CHECK_LAUNCH();
   return BP_OK;
 }
 
-int bp_flat_h7_run(const bp_view* in, const PW& pw, const float* packed, const float* bias, const bp_view* out,
-                   hipStream_t st) {
-  if (!bp_view_vec4(out)) return BP_EUNSUPPORTED;
+static int bp_flat_h7_run(const ConvGeom&, const bp_view* in, const PW& pw, const float* packed, const float* bias,
+                          const bp_view* out, hipStream_t st, const IgemmStatsReq* sr) {
+  if (sr || !bp_view_vec4(out)) return BP_EUNSUPPORTED;
   FlatHArgs a{};
   a.bias = bias;
   a.in = in->ptr; a.h = in->h; a.w = in->w; a.in_cs = in->cstride; a.in_co = in->coff;
@@ -1247,4 +1248,34 @@ int bp_flat_h7_run(const bp_view* in, const PW& pw, const float* packed, const f
   hipLaunchKernelGGL(flat_h7_kernel, dim3(flat_g4_grid((int)ntiles)), dim3(GNT), 0, st, a);
   BP_CHECK_LAUNCH();
   return BP_OK;
+}
+
+// ---- The five families' records (kernels.hpp)
+const ConvFamily& bp_family_flat() {
+  static const ConvFamily f = {
+      "flat", bp_flat_ok, bp_family_id<710000>, bp_flat_packed_floats, bp_flat_pack,
+      [](const ConvGeom&, const bp_view*, const bp_view* out, int mode) { return bp_flat_stats_workspace(out, mode); },
+      bp_flat_run, false};
+  return f;
+}
+const ConvFamily& bp_family_flat_t4() {
+  static const ConvFamily f = {  "flat_t4", bp_flat_t4_ok, bp_family_id<720000>, bp_flat_t4_packed_floats, bp_flat_t4_pack,
+                                  bp_family_stats_mode1<bp_flat_t4_stats_workspace>, bp_flat_t4_run, false};
+  return f;
+}
+const ConvFamily& bp_family_flat_g4() {
+  static const ConvFamily f = {  "flat_g4", bp_flat_g4_ok, bp_family_id<730000>, bp_flat_g4_packed_floats, bp_flat_g4_pack,
+                                  bp_family_stats_mode1<bp_flat_g4_stats_workspace>, bp_flat_g4_run, false};
+  return f;
+}
+const ConvFamily& bp_family_flat_t64() {
+  static const ConvFamily f = {  "flat_t64", bp_flat_t64_ok, bp_family_id<740000>, bp_flat_t64_packed_floats,
+                                   bp_flat_t64_pack, bp_family_stats_mode1<bp_flat_t64_stats_workspace>, bp_flat_t64_run, false};
+  return f;
+}
+const ConvFamily& bp_family_flat_h7() {
+  static const ConvFamily f = {          // (no statistics epilogue: a request is refused)
+      "flat_h7", bp_flat_h7_ok, bp_family_id<750000>, bp_flat_h7_packed_floats, bp_flat_h7_pack,
+      [](const ConvGeom&, const bp_view*, const bp_view*, int) { return (size_t)0; }, bp_flat_h7_run, false};
+  return f;
 }

@@ -21,6 +21,7 @@
 //                      staged tile; layers with <= 32 produced channels
 // Workgroups are mapped to tiles XCD-aware (igemm_tile_of_block); the channel block is the slowest grid dimension.
 #include "common.hpp"
+#include "kernels.hpp"
 #include <cstdlib>
 
 namespace {
@@ -1435,92 +1436,14 @@ int launch_mt(const IgemmConfig& c, const IgemmArgs& a, dim3 grid, hipStream_t s
 
 }  // namespace
 
-// conv_small.hip: vector-ALU kernel for unit-stride layers with cin*cout <= 8
-bool bp_small_ok(const ConvGeom& g);
-int64_t bp_small_packed_floats(const ConvGeom& g);
-int bp_small_kernel_id(const ConvGeom& g);
-int bp_small_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, float* packed, hipStream_t st);
-size_t bp_small_stats_workspace(const ConvGeom& g, const bp_view* in, const bp_view* out, int mode);
-int bp_small_run(const ConvGeom& g, const bp_view* in, const PW& pw, const float* packed, const float* bias,
-                 const bp_view* out, hipStream_t st, const IgemmStatsReq* sr);
-
-// conv_stem.hip: the 3 -> 16 k5 stem (flattened (tap column, channel) K, weights in registers)
-bool bp_stem_ok(const ConvGeom& g);
-int64_t bp_stem_packed_floats();
-int bp_stem_pack(const WeightMap& wm, const float* w_torch, float* packed, hipStream_t st);
-size_t bp_stem_stats_workspace(const bp_view* out);
-int bp_stem_run(const bp_view* in, const PW& pw, const float* packed, const float* bias, const bp_view* out,
-                hipStream_t st, const IgemmStatsReq* sr);
-
-// conv_flat.hip: unit-stride k7, 8 gathered -> 16 produced channels (weights in registers, flattened K)
-bool bp_flat_ok(const ConvGeom& g);
-int64_t bp_flat_packed_floats();
-int bp_flat_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, float* packed, hipStream_t st);
-size_t bp_flat_stats_workspace(const bp_view* out, int mode);
-int bp_flat_run(const ConvGeom& g, const bp_view* in, const PW& pw, const float* packed, const float* bias,
-                const bp_view* out, hipStream_t st, const IgemmStatsReq* sr);
-// ... and the stride-2 k4 transposed form 32 -> 16 (four phases, all weights in registers)
-bool bp_flat_t4_ok(const ConvGeom& g);
-int64_t bp_flat_t4_packed_floats();
-int bp_flat_t4_pack(const WeightMap& wm, const float* w_torch, float* packed, hipStream_t st);
-size_t bp_flat_t4_stats_workspace(const bp_view* out);
-int bp_flat_t4_run(const bp_view* in, const PW& pw, const float* packed, const float* bias, const bp_view* out,
-                   hipStream_t st, const IgemmStatsReq* sr);
-// ... and the stride-2 k4 conv form 32 -> 64 (eight waves: four blocks of 16 produced channels, weights in registers)
-bool bp_flat_g4_ok(const ConvGeom& g);
-int64_t bp_flat_g4_packed_floats(const ConvGeom& g);
-int bp_flat_g4_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, float* packed, hipStream_t st);
-size_t bp_flat_g4_stats_workspace(const bp_view* out);
-int bp_flat_g4_run(const ConvGeom& g, const bp_view* in, const PW& pw, const float* packed, const float* bias,
-                   const bp_view* out, hipStream_t st, const IgemmStatsReq* sr);
-
-// ... and the stride-2 k4 transposed form 64 -> 32 (eight waves: four phases x two blocks of 16 produced channels)
-bool bp_flat_t64_ok(const ConvGeom& g);
-int64_t bp_flat_t64_packed_floats(const ConvGeom& g);
-int bp_flat_t64_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, float* packed, hipStream_t st);
-size_t bp_flat_t64_stats_workspace(const bp_view* out);
-int bp_flat_t64_run(const ConvGeom& g, const bp_view* in, const PW& pw, const float* packed, const float* bias,
-                    const bp_view* out, hipStream_t st, const IgemmStatsReq* sr);
-
-// ... and unit-stride k7 16 -> 8 (the head's first layer forward: K split over two waves, pixel pairs per MFMA column)
-bool bp_flat_h7_ok(const ConvGeom& g);
-int64_t bp_flat_h7_packed_floats();
-int bp_flat_h7_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, float* packed, hipStream_t st);
-int bp_flat_h7_run(const bp_view* in, const PW& pw, const float* packed, const float* bias, const bp_view* out,
-                   hipStream_t st);
-
-// ... and the k8 stride-4 layer 8 -> 16 of the recognition / prior networks, forward and data gradient (conv_enc.hip)
-bool bp_enc_ok(const ConvGeom& g);
-int bp_enc_kernel_id(const ConvGeom& g);
-int64_t bp_enc_packed_floats(const ConvGeom& g);
-int bp_enc_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, float* packed, hipStream_t st);
-size_t bp_enc_stats_workspace(const ConvGeom& g, const bp_view* in, const bp_view* out, int mode);
-int bp_enc_run(const ConvGeom& g, const bp_view* in, const PW& pw, const float* packed, const float* bias,
-               const bp_view* out, hipStream_t st, const IgemmStatsReq* sr);
-
-int bp_igemm_kernel_id(const ConvGeom& g) {
-  if (bp_enc_ok(g)) return bp_enc_kernel_id(g);
-  if (bp_stem_ok(g)) return 700000;
-  if (bp_flat_ok(g)) return 710000;
-  if (bp_flat_t4_ok(g) && !bp_flat_t64_ok(g)) return 720000;
-  if (bp_flat_g4_ok(g)) return 730000;
-  if (bp_flat_t64_ok(g)) return 740000;
-  if (bp_flat_h7_ok(g)) return 750000;
-  if (bp_small_ok(g)) return bp_small_kernel_id(g);
+// ---- The tiled kernels as a family (kernels.hpp): the last one of conv_dispatch.hip's table.
+static int tiled_kernel_id(const ConvGeom& g) {
   const IgemmConfig c = igemm_config(g);
   if (c.ok && c.wres) return 400000 + c.CC * 1000 + c.NT * 100 + (c.w_NW / 4) * 10 + 2;
   return c.ok ? (c.dma ? 100000 * (c.dmaf ? 3 : c.NW / 4) : 0) + c.CC * 1000 + c.NT * 100 + c.WN * 10 + c.MT : -1;
 }
 
-int64_t bp_igemm_packed_floats(const ConvGeom& g) {
-  if (bp_enc_ok(g)) return bp_enc_packed_floats(g);
-  if (bp_stem_ok(g)) return bp_stem_packed_floats();
-  if (bp_flat_ok(g)) return bp_flat_packed_floats();
-  if (bp_flat_t4_ok(g) && !bp_flat_t64_ok(g)) return bp_flat_t4_packed_floats();
-  if (bp_flat_g4_ok(g)) return bp_flat_g4_packed_floats(g);
-  if (bp_flat_t64_ok(g)) return bp_flat_t64_packed_floats(g);
-  if (bp_flat_h7_ok(g)) return bp_flat_h7_packed_floats();
-  if (bp_small_ok(g)) return bp_small_packed_floats(g);
+static int64_t tiled_packed_floats(const ConvGeom& g) {
   const IgemmConfig c = igemm_config(g);
   if (!c.ok) return -1;
   return (int64_t)g.nphase * g.nphase * g.taps * c.tapsx * c.nchunk * c.cout_padP * c.CC;
@@ -1534,20 +1457,11 @@ static bool igemm_pack_args(const ConvGeom& g, const WeightMap& wm, const float*
   a.k = g.k; a.stride = g.stride; a.pad = g.pad; a.tapsy = g.taps; a.tapsx = c.tapsx; a.nphase = g.nphase;
   a.transposed = g.gather_transposed; a.cin_g = g.cin_g; a.cout_g = g.cout_g;
   a.CC = c.CC; a.nchunk = c.nchunk; a.cout_padP = c.cout_padP; a.PP = c.PP; a.COP = c.COP;
-  a.total = bp_igemm_packed_floats(g);
+  a.total = tiled_packed_floats(g);
   return true;
 }
 
-int bp_igemm_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, float* packed,
-                  hipStream_t st) {
-  if (bp_enc_ok(g)) return bp_enc_pack(g, wm, w_torch, packed, st);
-  if (bp_stem_ok(g)) return bp_stem_pack(wm, w_torch, packed, st);
-  if (bp_flat_ok(g)) return bp_flat_pack(g, wm, w_torch, packed, st);
-  if (bp_flat_t4_ok(g) && !bp_flat_t64_ok(g)) return bp_flat_t4_pack(wm, w_torch, packed, st);
-  if (bp_flat_g4_ok(g)) return bp_flat_g4_pack(g, wm, w_torch, packed, st);
-  if (bp_flat_t64_ok(g)) return bp_flat_t64_pack(g, wm, w_torch, packed, st);
-  if (bp_flat_h7_ok(g)) return bp_flat_h7_pack(g, wm, w_torch, packed, st);
-  if (bp_small_ok(g)) return bp_small_pack(g, wm, w_torch, packed, st);
+static int tiled_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, float* packed, hipStream_t st) {
   PackArgs a;
   if (!igemm_pack_args(g, wm, w_torch, packed, a)) return BP_EUNSUPPORTED;
   hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((a.total + 255) / 256)), dim3(256), 0, st, a);
@@ -1558,9 +1472,8 @@ int bp_igemm_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, 
 // Batched packing (bp_conv_pack_job / bp_conv_pack_jobs): the job record is the kernel's own argument block.
 size_t bp_igemm_pack_job_bytes() { return sizeof(PackArgs); }
 
-int bp_igemm_pack_job(const ConvGeom& g, const WeightMap& wm, const float* w_torch, float* packed, void* job,
-                      int64_t* nblocks) {
-  if (bp_enc_ok(g) || bp_stem_ok(g) || bp_flat_ok(g) || bp_flat_t4_ok(g) || bp_flat_g4_ok(g) || bp_flat_t64_ok(g) || bp_flat_h7_ok(g) || bp_small_ok(g)) return BP_EUNSUPPORTED;       // (their own tiny pack kernels: packed by bp_conv_pack)
+int bp_igemm_tiled_pack_job(const ConvGeom& g, const WeightMap& wm, const float* w_torch, float* packed, void* job,
+                            int64_t* nblocks) {
   PackArgs a;
   if (!igemm_pack_args(g, wm, w_torch, packed, a)) return BP_EUNSUPPORTED;
   *reinterpret_cast<PackArgs*>(job) = a;
@@ -1629,26 +1542,39 @@ static bool stats_plan(const ConvGeom& g, const IgemmConfig& c, const IgemmLaunc
   stats_fold_plan(p);
   return true;
 }
+// The first fold of partial rows ws[sp.rows][sp.n], where the plan has one: the *nrows rows at *rows are what the last
+// stage (one of the bp_sum_partials_* of pointwise.hip) adds up.
+static int stats_fold(const StatsPlan& sp, double* ws, hipStream_t st, const double** rows, int* nrows) {
+  *rows = ws; *nrows = (int)sp.rows;
+  if (!sp.nfold) return BP_OK;
+  double* folded = ws + sp.rows * sp.n;
+  hipLaunchKernelGGL(stats_fold_kernel, dim3((unsigned)sp.nfold), dim3(256), 0, st, ws, sp.rows, sp.R, sp.n, folded);
+  BP_CHECK_LAUNCH();
+  *rows = folded; *nrows = sp.nfold;
+  return BP_OK;
+}
+// ... and the whole row through the request's last stage (sr->fin rides on it)
 static int stats_finish(const StatsPlan& sp, double* ws, const IgemmStatsReq* sr, hipStream_t st) {
-  const double* rows = ws;
-  int64_t nrows = sp.rows;
-  if (sp.nfold) {
-    double* folded = ws + sp.rows * sp.n;
-    hipLaunchKernelGGL(stats_fold_kernel, dim3((unsigned)sp.nfold), dim3(256), 0, st, rows, sp.rows, sp.R, sp.n, folded);
-    BP_CHECK_LAUNCH();
-    rows = folded; nrows = sp.nfold;
-  }
-  return bp_sum_partials_req(rows, (int)nrows, sp.n, sr, st);
+  const double* rows;
+  int nrows;
+  const int rc = stats_fold(sp, ws, st, &rows, &nrows);
+  return rc != BP_OK ? rc : bp_sum_partials_req(rows, nrows, sp.n, sr, st);
 }
 
-// Partial rows [rows][2*C] written by some kernel's epilogue -> sums[2*C] (used by the bf16 kernels too):
-// bytes of workspace for the rows and their first fold, and the fold itself.
+// Partial rows written by some other kernel's epilogue (the bf16 kernels' too): `rows` rows of n doubles.
+static StatsPlan rows_plan(int64_t rows, int n) {
+  StatsPlan p{};
+  p.rows = rows; p.n = n;
+  stats_fold_plan(p);
+  return p;
+}
+// ... rows [rows][2*C]: bytes of workspace for the rows and their first fold, and the fold itself
 size_t bp_stats_rows_bytes(int64_t rows, int C) {
   if (C <= 0 || (C & (C - 1)) != 0 || C > 512) return 0;
-  StatsPlan p{};
-  p.rows = rows; p.n = 2 * C;
-  stats_fold_plan(p);
-  return p.bytes;
+  return rows_plan(rows, 2 * C).bytes;
+}
+int bp_stats_rows_finish(double* ws, int64_t rows, int C, const IgemmStatsReq* sr, hipStream_t st) {
+  return stats_finish(rows_plan(rows, 2 * C), ws, sr, st);
 }
 // ... the same for rows of which n doubles are wanted (the three sums of an activation backward: n = 3 C).  The fold
 // needs a power-of-two row: the kernel writes rows of bp_stats_row_stride(n) doubles, zero beyond n.
@@ -1657,75 +1583,33 @@ int bp_stats_row_stride(int n) {
   while (s < n) s <<= 1;
   return s;
 }
-size_t bp_stats_rows_bytes_n(int64_t rows, int n) {
-  StatsPlan p{};
-  p.rows = rows; p.n = bp_stats_row_stride(n);
-  stats_fold_plan(p);
-  return p.bytes;
-}
+size_t bp_stats_rows_bytes_n(int64_t rows, int n) { return rows_plan(rows, bp_stats_row_stride(n)).bytes; }
 int bp_stats_rows_finish_n(double* ws, int64_t rows, int n, const IgemmStatsReq* sr, hipStream_t st) {
-  StatsPlan p{};
-  p.rows = rows; p.n = bp_stats_row_stride(n);
-  stats_fold_plan(p);
-  const double* src = ws;
-  int64_t nrows = p.rows;
-  if (p.nfold) {
-    double* folded = ws + p.rows * p.n;
-    hipLaunchKernelGGL(stats_fold_kernel, dim3((unsigned)p.nfold), dim3(256), 0, st, src, p.rows, p.R, p.n, folded);
-    BP_CHECK_LAUNCH();
-    src = folded; nrows = p.nfold;
-  }
-  return bp_sum_partials_strided(src, (int)nrows, p.n, n, sr->sums, st);
-}
-int bp_stats_rows_finish(double* ws, int64_t rows, int C, const IgemmStatsReq* sr, hipStream_t st) {
-  StatsPlan p{};
-  p.rows = rows; p.n = 2 * C;
-  stats_fold_plan(p);
-  return stats_finish(p, ws, sr, st);
+  const StatsPlan p = rows_plan(rows, bp_stats_row_stride(n));
+  const double* src;
+  int nrows;
+  const int rc = stats_fold(p, ws, st, &src, &nrows);
+  return rc != BP_OK ? rc : bp_sum_partials_strided(src, nrows, p.n, n, sr->sums, st);
 }
 
-// conv_ws_f32.hip: weights-stationary kernel of the 128 -> 128 k3 trunk layers (reads the tiled image packed above)
-bool bp_f32_ws_ok(const ConvGeom& g, const bp_view* in, const bp_view* out, const float* bias, int stats_mode);
-size_t bp_f32_ws_stats_workspace(const ConvGeom& g, const bp_view* out);
-int bp_f32_ws_run(const ConvGeom& g, const bp_view* in, const PW& pw, const float* packed_tiled, const bp_view* out,
-                  hipStream_t st, const IgemmStatsReq* sr);
-
-size_t bp_igemm_stats_workspace(const ConvGeom& g, const bp_view* in, const bp_view* out, int mode) {
-  if (bp_f32_ws_ok(g, in, out, nullptr, mode)) {        // (the larger of the two: bp_set_option may switch kernels later)
-    const IgemmConfig c = igemm_config(g);
-    IgemmLaunch l;
-    StatsPlan p;
-    const size_t tiled = (c.ok && igemm_launch_of(g, c, in, out, l) && stats_plan(g, c, l, p)) ? p.bytes : 0;
-    const size_t ws = bp_f32_ws_stats_workspace(g, out);
-    return ws > tiled ? ws : tiled;
-  }
-  if (bp_enc_ok(g)) return bp_enc_stats_workspace(g, in, out, mode);
-  if (bp_stem_ok(g)) return mode == 1 ? bp_stem_stats_workspace(out) : 0;
-  if (bp_flat_ok(g)) return bp_flat_stats_workspace(out, mode);
-  if (bp_flat_t4_ok(g) && !bp_flat_t64_ok(g)) return mode == 1 ? bp_flat_t4_stats_workspace(out) : 0;
-  if (bp_flat_g4_ok(g)) return mode == 1 ? bp_flat_g4_stats_workspace(out) : 0;
-  if (bp_flat_t64_ok(g)) return mode == 1 ? bp_flat_t64_stats_workspace(out) : 0;
-  if (bp_flat_h7_ok(g)) return 0;
-  if (bp_small_ok(g)) return bp_small_stats_workspace(g, in, out, mode);
-  if (mode != 1 && mode != 2) return 0;
+static size_t tiled_stats_workspace(const ConvGeom& g, const bp_view* in, const bp_view* out, int mode) {
+  // The weights-stationary kernel is asked here, after every other family has declined the layer: it wants 128 -> 128 k3,
+  // which none of them accepts.  A family that does accept such a layer must keep the rule below itself.
+  const bool ws_f32 = bp_f32_ws_ok(g, in, out, nullptr, mode);
+  if (!ws_f32 && mode != 1 && mode != 2) return 0;
   const IgemmConfig c = igemm_config(g);
   IgemmLaunch l;
   StatsPlan p;
-  if (!c.ok || !igemm_launch_of(g, c, in, out, l) || !stats_plan(g, c, l, p)) return 0;
-  if (l.wres && mode != 1) return 0;
-  return p.bytes;
+  const bool has = c.ok && igemm_launch_of(g, c, in, out, l) && stats_plan(g, c, l, p);
+  if (ws_f32) {        // (the larger of the two: bp_set_option may switch kernels later)
+    const size_t ws = bp_f32_ws_stats_workspace(g, out), tiled = has ? p.bytes : 0;
+    return ws > tiled ? ws : tiled;
+  }
+  return has && !(l.wres && mode != 1) ? p.bytes : 0;
 }
 
-int bp_igemm_run(const ConvGeom& g, const bp_view* in, const PW& pw, const float* packed,
-                 const float* bias, const bp_view* out, hipStream_t st, const IgemmStatsReq* sr) {
-  if (bp_enc_ok(g)) return bp_enc_run(g, in, pw, packed, bias, out, st, sr);
-  if (bp_stem_ok(g)) return bp_stem_run(in, pw, packed, bias, out, st, sr);
-  if (bp_flat_ok(g)) return bp_flat_run(g, in, pw, packed, bias, out, st, sr);
-  if (bp_flat_t4_ok(g) && !bp_flat_t64_ok(g)) return bp_flat_t4_run(in, pw, packed, bias, out, st, sr);
-  if (bp_flat_g4_ok(g)) return bp_flat_g4_run(g, in, pw, packed, bias, out, st, sr);
-  if (bp_flat_t64_ok(g)) return bp_flat_t64_run(g, in, pw, packed, bias, out, st, sr);
-  if (bp_flat_h7_ok(g)) return sr ? BP_EUNSUPPORTED : bp_flat_h7_run(in, pw, packed, bias, out, st);
-  if (bp_small_ok(g)) return bp_small_run(g, in, pw, packed, bias, out, st, sr);
+static int tiled_run(const ConvGeom& g, const bp_view* in, const PW& pw, const float* packed, const float* bias,
+                     const bp_view* out, hipStream_t st, const IgemmStatsReq* sr) {
   const IgemmConfig c = igemm_config(g);
   if (!c.ok) return BP_EUNSUPPORTED;
   if (c.CC == 16 && c.PP == 1 && c.cout_padP == 128 && bp_f32_ws_ok(g, in, out, bias, sr ? sr->mode : 0))
@@ -1768,4 +1652,10 @@ int bp_igemm_run(const ConvGeom& g, const bp_view* in, const PW& pw, const float
   else rc = launch_mt<1>(c, a, grid, st);
   if (rc != BP_OK || !sr) return rc;
   return stats_finish(sp, a.stat, sr, st);
+}
+
+const ConvFamily& bp_family_tiled() {
+  static const ConvFamily f = {  "tiled", [](const ConvGeom&) { return true; }, tiled_kernel_id, tiled_packed_floats,
+                                      tiled_pack, tiled_stats_workspace, tiled_run, true};
+  return f;
 }

@@ -13,14 +13,8 @@
 // The same kernel serves the forward of a Conv2d (taps ascending, origin -pad) and the data gradient of a
 // unit-stride Conv2d (taps reversed by the packing, origin pad-(K-1)).
 #include "common.hpp"
+#include "kernels.hpp"
 #include <cstdlib>
-
-// conv_igemm.hip: fold of per-workgroup rows of n doubles into sr->sums
-size_t bp_stats_rows_bytes(int64_t rows, int C);
-int bp_stats_rows_finish(double* ws, int64_t rows, int C, const IgemmStatsReq* sr, hipStream_t st);
-int bp_stats_row_stride(int n);
-size_t bp_stats_rows_bytes_n(int64_t rows, int n);
-int bp_stats_rows_finish_n(double* ws, int64_t rows, int n, const IgemmStatsReq* sr, hipStream_t st);
 
 namespace {
 
@@ -491,7 +485,7 @@ int64_t act_rows(const bp_view* out) { return (int64_t)bp_ceil_div(out->w, 64) *
 }  // namespace
 
 // Does (k, gathered channels, produced channels) of this unit-stride correlation have an instantiation?
-bool bp_small_ok(const ConvGeom& g) {
+static bool bp_small_ok(const ConvGeom& g) {
   static const bool off = getenv("BP_NOSMALL") != nullptr;
   if (!off && tiny_ok(g)) return true;
   if (off || g.IS != 1 || g.OS != 1 || g.nphase != 1 || g.stride != 1) return false;
@@ -501,14 +495,14 @@ bool bp_small_ok(const ConvGeom& g) {
          (g.k == 4 && g.cin_g % 8 == 0 && g.cin_g <= 1024 && g.cout_g == 1);   // PatchGAN logits (512 -> 1)
 }
 
-int64_t bp_small_packed_floats(const ConvGeom& g) { return (int64_t)g.k * g.k * g.cin_g * g.cout_g; }
+static int64_t bp_small_packed_floats(const ConvGeom& g) { return (int64_t)g.k * g.k * g.cin_g * g.cout_g; }
 
-int bp_small_kernel_id(const ConvGeom& g) {
+static int bp_small_kernel_id(const ConvGeom& g) {
   if (tiny_ok(g)) return 800000 + g.k * 10000 + g.stride * 1000 + g.cin_g * 100 + g.cout_g * 10 + g.gather_transposed;
   return 900000 + g.k * 1000 + g.cin_g * 10 + g.cout_g;
 }
 
-int bp_small_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, float* packed, hipStream_t st) {
+static int bp_small_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, float* packed, hipStream_t st) {
   SmallPackArgs a{};
   a.w = w_torch; a.dst = packed; a.sa = wm.sa; a.sb = wm.sb;
   a.k = g.k; a.ci = g.cin_g; a.co = g.cout_g;
@@ -520,13 +514,13 @@ int bp_small_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, 
 }
 
 // mode 3 (IgemmStatsReq): activation backward of the produced slot in the epilogue; 0 = this layer has none
-size_t bp_small_stats_workspace(const ConvGeom& g, const bp_view* in, const bp_view* out, int mode) {
+static size_t bp_small_stats_workspace(const ConvGeom& g, const bp_view* in, const bp_view* out, int mode) {
   if (mode == 1 && tiny_stats_geom(g)) return bp_stats_rows_bytes(tiny_rows(out), 1);
   if (mode != 3 || tiny_ok(g) || !act_geom(g)) return 0;
   return bp_stats_rows_bytes_n(act_rows(out), 3 * g.cout_g);
 }
 
-int bp_small_run(const ConvGeom& g, const bp_view* in, const PW& pw, const float* packed, const float* bias,
+static int bp_small_run(const ConvGeom& g, const bp_view* in, const PW& pw, const float* packed, const float* bias,
                  const bp_view* out, hipStream_t st, const IgemmStatsReq* sr) {
   if (tiny_ok(g)) return tiny_run(g, in, pw, packed, bias, out, st, sr);
   if (sr && (sr->mode != 3 || !act_geom(g) || bias)) return BP_EUNSUPPORTED;
@@ -558,4 +552,10 @@ int bp_small_run(const ConvGeom& g, const bp_view* in, const PW& pw, const float
   if (g.k == 9 && g.cout_g == 1) return launch<9, 8, 1, 8, true>(a, out, in->n, st);
   if (g.k == 9 && g.cout_g == 2) return launch<9, 8, 2, 8, true>(a, out, in->n, st);
   return BP_EUNSUPPORTED;
+}
+
+const ConvFamily& bp_family_small() {
+  static const ConvFamily f = {  "small", bp_small_ok, bp_small_kernel_id, bp_small_packed_floats, bp_small_pack,
+                                      bp_small_stats_workspace, bp_small_run, false};
+  return f;
 }

@@ -13,6 +13,7 @@
 // one's MFMAs and written to the other LDS buffer after them: one barrier per tile.  Training-mode batch-norm sums
 // ({sum y, sum y^2} per channel, in double) are taken from the accumulators and reduced once per workgroup.
 #include "common.hpp"
+#include "kernels.hpp"
 #include <cstdlib>
 
 namespace {
@@ -327,27 +328,27 @@ int stem_grid(int ntiles) {
 
 }  // namespace
 
-bool bp_stem_ok(const ConvGeom& g) {
+static bool bp_stem_ok(const ConvGeom& g) {
   static const bool off = getenv("BP_NOSTEM") != nullptr;
   return !off && !g.gather_transposed && g.k == K5 && g.stride == 1 && g.pad == 2 && g.cin_g == CI3 && g.cout_g == CO16;
 }
 
-int64_t bp_stem_packed_floats() { return K5 * 16 * CO16; }
+static int64_t bp_stem_packed_floats(const ConvGeom&) { return K5 * 16 * CO16; }
 
-int bp_stem_pack(const WeightMap& wm, const float* w_torch, float* packed, hipStream_t st) {
+static int bp_stem_pack(const ConvGeom&, const WeightMap& wm, const float* w_torch, float* packed, hipStream_t st) {
   StemPackArgs a{w_torch, packed, wm.sa, wm.sb};
   hipLaunchKernelGGL(stem_pack_kernel, dim3((K5 * 16 * CO16 + 255) / 256), dim3(256), 0, st, a);
   BP_CHECK_LAUNCH();
   return BP_OK;
 }
 
-size_t bp_stem_stats_workspace(const bp_view* out) {
+static size_t bp_stem_stats_workspace(const bp_view* out) {
   const int ntiles = bp_ceil_div(out->w, TW) * bp_ceil_div(out->h, TH) * out->n;
   return (size_t)stem_grid(ntiles) * 2 * CO16 * sizeof(double);
 }
 
-int bp_stem_run(const bp_view* in, const PW& pw, const float* packed, const float* bias, const bp_view* out,
-                hipStream_t st, const IgemmStatsReq* sr) {
+static int bp_stem_run(const ConvGeom&, const bp_view* in, const PW& pw, const float* packed, const float* bias,
+                       const bp_view* out, hipStream_t st, const IgemmStatsReq* sr) {
   if (sr && (bias || sr->mode != 1)) return BP_EUNSUPPORTED;
   StemArgs a{};
   a.in = in->ptr; a.in_h = in->h; a.in_w = in->w; a.in_cs = in->cstride; a.in_co = in->coff;
@@ -368,6 +369,12 @@ int bp_stem_run(const bp_view* in, const PW& pw, const float* packed, const floa
   BP_CHECK_LAUNCH();
   if (sr) return bp_sum_partials_req(a.stat, grid, 2 * CO16, sr, st);
   return BP_OK;
+}
+
+const ConvFamily& bp_family_stem() {
+  static const ConvFamily f = {  "stem", bp_stem_ok, bp_family_id<700000>, bp_stem_packed_floats, bp_stem_pack,
+                               bp_family_stats_mode1<bp_stem_stats_workspace>, bp_stem_run, false};
+  return f;
 }
 
 // ---- weight gradient

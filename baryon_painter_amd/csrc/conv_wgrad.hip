@@ -10,6 +10,7 @@
 // are summed through LDS at the end.  Partial results per split go to a workspace and a second
 // kernel adds them in a fixed order, so the gradient is bitwise reproducible (no float atomics).
 #include "common.hpp"
+#include "kernels.hpp"
 #include <cstdlib>
 #include <vector>
 
@@ -239,18 +240,6 @@ WgradPlan wgrad_plan(const bp_conv* cv, const bp_view* X, const bp_view* Y) {
 
 }  // namespace
 
-int bp_wgrad_tiles(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* ws,
-                   size_t ws_bytes, size_t* need, int* nsplit, int* cxp, int* cyp, hipStream_t st, bool dry);
-int bp_wgrad_small(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* ws,
-                   size_t ws_bytes, size_t* need, int* nsplit, int* cxp, int* cyp, hipStream_t st, bool dry);
-
-int bp_wgrad_enc(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* ws,
-                 size_t ws_bytes, size_t* need, int* nsplit, int* cxp, int* cyp, hipStream_t st, bool dry);
-int bp_wgrad_thin(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* ws,
-                  size_t ws_bytes, size_t* need, int* nsplit, int* cxp, int* cyp, hipStream_t st, bool dry);
-int bp_wgrad_ws_f32(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* ws,
-                    size_t ws_bytes, size_t* need, int* nsplit, int* cxp, int* cyp, hipStream_t st, bool dry);
-
 // the k8 stride-4 encoder layer (conv_enc.hip), one-channel tails (conv_wgrad_thin.hip), the tap-packed few-channel
 // kernel, then the tap-blocked one;
 // BP_EUNSUPPORTED -> generic kernel
@@ -389,10 +378,7 @@ static int wgrad_chunked(const bp_conv* cv, const bp_view* X, const PW& pwx, con
   return BP_OK;
 }
 
-// bf16 matrix-core weight gradient (conv_bf16.hip) + the same fixed-order reduction; operands may be fp32 or bf16
-int bp_wgrad_bf16(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* ws,
-                  size_t ws_bytes, size_t* need, int* nsplit, int* cxp, int* cyp, hipStream_t st, bool dry);
-
+// bf16 matrix-core weight gradient (conv_wgrad_bf16.hip) + the same fixed-order reduction; operands may be fp32 or bf16
 size_t bp_wgrad_bf16_workspace(const bp_conv* cv, const bp_view* X, const bp_view* Y) {
   size_t need = 0;
   int ns, cxp, cyp;
@@ -410,21 +396,6 @@ int bp_wgrad_bf16_run(const bp_conv* cv, const bp_view* X, const PW& pwx, const 
   return wgrad_reduce(reinterpret_cast<const float*>(workspace), dst, cv->k, X->c, Y->c, cxp, cyp, ns, st);
 }
 
-// conv_stem.hip: weight gradient of the 3 -> 16 k5 stem
-bool bp_stem_wgrad_ok(const bp_conv* cv, const bp_view* X, const bp_view* Y, const PW& pwy, const float* dbias);
-size_t bp_stem_wgrad_workspace(const bp_view* X);
-int bp_stem_wgrad(const bp_view* X, const PW& pwx, const bp_view* Y, float* dst, void* workspace, size_t workspace_bytes,
-                  hipStream_t st);
-// conv_wgrad_flat.hip: weight gradient of the 16 -> 8 k7 head layer
-bool bp_wgrad_flat_ok(const bp_conv* cv, const bp_view* X, const bp_view* Y, const PW& pwy);
-size_t bp_wgrad_flat_workspace(const bp_view* X);
-int bp_wgrad_flat(const bp_view* X, const PW& pwx, const bp_view* Y, float* dst, void* workspace, size_t workspace_bytes,
-                  hipStream_t st, bool shared);
-// ... and of the thin stride-2 k4 layers (16 channels at full resolution, 32 at half)
-bool bp_wgrad_flat_s2_ok(const bp_conv* cv, const bp_view* X, const bp_view* Y, const PW& pwx, const PW& pwy);
-size_t bp_wgrad_flat_s2_workspace(const bp_view* Y);
-int bp_wgrad_flat_s2(const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* dst, void* workspace,
-                     size_t workspace_bytes, hipStream_t st, bool shared);
 static size_t wgrad_general_workspace(const bp_conv* cv, const bp_view* X, const bp_view* Y);
 
 size_t bp_wgrad_mfma_workspace(const bp_conv* cv, const bp_view* X, const bp_view* Y) {
@@ -457,7 +428,6 @@ static size_t wgrad_general_workspace(const bp_conv* cv, const bp_view* X, const
   return p.ok ? p.ws_bytes : 0;
 }
 
-void bp_wgrad_tiles_target(int target);      // conv_wgrad_tiles.hip
 namespace {
 struct SharedTarget {                        // for the duration of one bp_wgrad_mfma call on this thread
   explicit SharedTarget(bool shared) {

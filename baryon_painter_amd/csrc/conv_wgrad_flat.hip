@@ -12,6 +12,7 @@
 //     and zero padded; dY with its 6 halo columns) in flight in registers; waves, then workgroups, are folded in a
 //     fixed order (deterministic).
 #include "common.hpp"
+#include "kernels.hpp"
 #include <cstdlib>
 
 namespace {

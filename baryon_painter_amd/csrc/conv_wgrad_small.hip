@@ -16,6 +16,7 @@
 // Workgroup = 4 waves splitting the k-steps of a BH x 32 pixel tile; pixel tiles are split over
 // workgroups; partials go to the workspace layout of conv_wgrad.hip and are reduced there.
 #include "common.hpp"
+#include "kernels.hpp"
 #include <cstdlib>
 
 namespace {

@@ -17,6 +17,7 @@
 // Partials go to the workspace layout of conv_wgrad.hip ([split][ky][kx][cy][cx]) and are reduced there in fixed
 // order.
 #include "common.hpp"
+#include "kernels.hpp"
 #include <cstdlib>
 
 namespace {

@@ -17,6 +17,7 @@
 // Partials per pixel split go to a workspace; wgrad_reduce_kernel (conv_wgrad.hip) sums them in a
 // fixed order (bitwise reproducible).
 #include "common.hpp"
+#include "kernels.hpp"
 #include <cstdlib>
 
 // Workgroup-count target of the next launches on this thread (0: the default).  bp_wgrad_mfma sets it for a launch that

@@ -14,6 +14,7 @@
 // (wave w: channels {4 i + w}).  Per k-step: ten 16-byte LDS reads for 36 MFMAs.  Partial sums per (image, band) go to the
 // split-K workspace in the layout wgrad_reduce expects; a lane's 16 values of a tap are 16 consecutive ci: float4 stores.
 #include "common.hpp"
+#include "kernels.hpp"
 #include <cstdlib>
 
 namespace {

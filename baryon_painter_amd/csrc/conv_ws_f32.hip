@@ -12,11 +12,9 @@
 // k-steps of a chunk are one float4), so nothing else changes in the plan.  Numerics: the same exact-fp32 FMA chains
 // (another summation order over K than the tiled kernel: taps outermost), batch-norm sums in double per lane.
 #include "common.hpp"
+#include "kernels.hpp"
 #include <cstdlib>
 #include <type_traits>
-
-size_t bp_stats_rows_bytes(int64_t rows, int C);
-int bp_stats_rows_finish(double* ws, int64_t rows, int C, const IgemmStatsReq* sr, hipStream_t st);
 
 namespace {
 

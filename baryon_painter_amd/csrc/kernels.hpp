@@ -1,0 +1,179 @@
+// Every host function that crosses a translation unit, declared once and grouped by the file that defines it, and the
+// records through which the dispatchers reach the kernel families.  Include after common.hpp.  Default arguments live
+// here only.
+#pragma once
+#include "common.hpp"
+
+// ---- fp32 forward / data gradient: one record per kernel family (conv_dispatch.hip walks them in priority order).
+// A family answers six questions about a geometry it accepts; the adapters that give its kernels' own entry points
+// these signatures sit next to the kernels.
+struct ConvFamily {
+  const char* name;
+  bool (*ok)(const ConvGeom& g);
+  int (*kernel_id)(const ConvGeom& g);
+  int64_t (*packed_floats)(const ConvGeom& g);
+  int (*pack)(const ConvGeom& g, const WeightMap& wm, const float* w_torch, float* packed, hipStream_t st);
+  // 0: this layer's kernel has no epilogue for `mode` (IgemmStatsReq) on these views
+  size_t (*stats_workspace)(const ConvGeom& g, const bp_view* in, const bp_view* out, int mode);
+  int (*run)(const ConvGeom& g, const bp_view* in, const PW& pw, const float* packed, const float* bias,
+             const bp_view* out, hipStream_t st, const IgemmStatsReq* sr);
+  bool batched_pack;      // bp_conv_pack_job may take it (false: its own tiny pack kernel, packed by bp_conv_pack)
+};
+// (Each record is a function-local static const behind an accessor: a const variable at namespace scope would be emitted
+// into the device code object as well, where the host functions it points to do not exist.)
+// adapters most families share: one kernel id; statistics of the produced tensor (mode 1) only
+template <int ID>
+int bp_family_id(const ConvGeom&) { return ID; }
+template <size_t (*WS)(const bp_view* out)>
+size_t bp_family_stats_mode1(const ConvGeom&, const bp_view*, const bp_view* out, int mode) { return mode == 1 ? WS(out) : 0; }
+
+// conv_enc.hip: the k8 stride-4 layer 8 -> 16 of the recognition / prior networks, forward and data gradient, and k4 s2
+// {1, 2} -> 8
+const ConvFamily& bp_family_enc();
+// conv_stem.hip: the 3 -> 16 k5 stem (flattened (tap column, channel) K, weights in registers)
+const ConvFamily& bp_family_stem();
+// conv_flat.hip: unit-stride k7, 8 gathered -> 16 produced channels (weights in registers, flattened K)
+const ConvFamily& bp_family_flat();
+// ... the stride-2 k4 transposed form 64 -> 32 (eight waves: four phases x two blocks of 16 produced channels)
+const ConvFamily& bp_family_flat_t64();
+// ... the stride-2 k4 transposed form 32 -> 16 (four phases, all weights in registers)
+const ConvFamily& bp_family_flat_t4();
+// ... the stride-2 k4 conv form 32 -> 64 (eight waves: four blocks of 16 produced channels, weights in registers)
+const ConvFamily& bp_family_flat_g4();
+// ... and unit-stride k7 16 -> 8 (the head's first layer forward: K split over two waves, pixel pairs per MFMA column)
+const ConvFamily& bp_family_flat_h7();
+// conv_small.hip: vector-ALU kernel for unit-stride layers with cin*cout <= 8, and the one-channel strided kernels
+const ConvFamily& bp_family_small();
+// conv_igemm.hip: the tiled implicit-GEMM kernels (takes every geometry: it refuses the ones it has no configuration
+// for) and, by views, their hand-off to the weights-stationary kernel of conv_ws_f32.hip
+const ConvFamily& bp_family_tiled();
+
+// conv_dispatch.hip: the fp32 gather entry points behind capi.hip
+int64_t bp_igemm_packed_floats(const ConvGeom& g);
+int bp_igemm_kernel_id(const ConvGeom& g);
+int bp_igemm_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, float* packed, hipStream_t st);
+int bp_igemm_pack_job(const ConvGeom& g, const WeightMap& wm, const float* w_torch, float* packed, void* job,
+                      int64_t* nblocks);
+int bp_igemm_run(const ConvGeom& g, const bp_view* in, const PW& pw, const float* packed, const float* bias,
+                 const bp_view* out, hipStream_t st, const IgemmStatsReq* stats = nullptr);
+size_t bp_igemm_stats_workspace(const ConvGeom& g, const bp_view* in, const bp_view* out, int mode);
+
+// conv_igemm.hip: batched packing of the tiled kernels' images (the job record is the pack kernel's argument block)
+size_t bp_igemm_pack_job_bytes();
+int bp_igemm_tiled_pack_job(const ConvGeom& g, const WeightMap& wm, const float* w_torch, float* packed, void* job,
+                            int64_t* nblocks);
+int bp_igemm_pack_jobs(const void* jobs_dev, const int64_t* first_block_dev, int njobs, int64_t total_blocks,
+                       hipStream_t st);
+// conv_igemm.hip: partial rows [rows][2*C] of epilogue statistics -> sr->sums (bytes of workspace for the rows and their
+// first fold, and the fold itself), and the same for rows of which n doubles are wanted, written with a stride of
+// bp_stats_row_stride(n)
+size_t bp_stats_rows_bytes(int64_t rows, int C);
+int bp_stats_rows_finish(double* ws, int64_t rows, int C, const IgemmStatsReq* sr, hipStream_t st);
+int bp_stats_row_stride(int n);
+size_t bp_stats_rows_bytes_n(int64_t rows, int n);
+int bp_stats_rows_finish_n(double* ws, int64_t rows, int n, const IgemmStatsReq* sr, hipStream_t st);
+
+// conv_ws_f32.hip: weights-stationary kernel of the 128 -> 128 k3 trunk layers (reads the tiled kernels' packed image)
+void bp_f32_ws_set(int v);
+bool bp_f32_ws_ok(const ConvGeom& g, const bp_view* in, const bp_view* out, const float* bias, int stats_mode);
+size_t bp_f32_ws_stats_workspace(const ConvGeom& g, const bp_view* out);
+int bp_f32_ws_run(const ConvGeom& g, const bp_view* in, const PW& pw, const float* packed_tiled, const bp_view* out,
+                  hipStream_t st, const IgemmStatsReq* sr);
+
+// conv_direct.hip
+int bp_direct_gather(const ConvGeom& g, const WeightMap& wm, const bp_view* in, const PW& pw, const float* w_torch,
+                     const float* bias, const bp_view* out, hipStream_t st);
+int bp_direct_wgrad(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* dst,
+                    hipStream_t st);
+
+// conv_wgrad.hip: the fp32 / bf16 weight gradient behind capi.hip, and its deferred reductions
+size_t bp_wgrad_mfma_workspace(const bp_conv* cv, const bp_view* X, const bp_view* Y);
+int bp_wgrad_mfma(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* dst,
+                  void* workspace, size_t workspace_bytes, hipStream_t st, bool shared);
+size_t bp_wgrad_bf16_workspace(const bp_conv* cv, const bp_view* X, const bp_view* Y);
+int bp_wgrad_bf16_run(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* dst,
+                      void* workspace, size_t workspace_bytes, hipStream_t st);
+void bp_wgrad_private_ws(bool on);
+int bp_wgrad_defer_begin_impl();
+int bp_wgrad_defer_flush_impl(hipStream_t st, int end);
+
+// Weight-gradient kernels that write partial sums ws[split][ky][kx][cy][cx] for conv_wgrad.hip to reduce in fixed order
+// share one signature: *need bytes of ws, *nsplit partial images of padded channel counts *cxp x *cyp; `dry`: fill those,
+// launch nothing; BP_EUNSUPPORTED: not this kernel's layer.  Each is defined in the file of its name (bp_wgrad_enc:
+// conv_enc.hip, bp_wgrad_bf16: conv_wgrad_bf16.hip).
+using WgradPartialFn = int(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* ws,
+                           size_t ws_bytes, size_t* need, int* nsplit, int* cxp, int* cyp, hipStream_t st, bool dry);
+WgradPartialFn bp_wgrad_ws_f32, bp_wgrad_enc, bp_wgrad_thin, bp_wgrad_small, bp_wgrad_tiles, bp_wgrad_bf16, bp_wgrad_ws_bf16;
+void bp_f32_wgrad_ws_set(int v);        // conv_wgrad_ws_f32.hip
+void bp_bf16_wgrad_ws_set(int v);       // conv_wgrad_ws_bf16.hip
+void bp_wgrad_tiles_target(int target); // conv_wgrad_tiles.hip
+
+// Weight-gradient kernels that reduce their own partial sums.
+// conv_stem.hip: weight gradient of the 3 -> 16 k5 stem
+bool bp_stem_wgrad_ok(const bp_conv* cv, const bp_view* X, const bp_view* Y, const PW& pwy, const float* dbias);
+size_t bp_stem_wgrad_workspace(const bp_view* X);
+int bp_stem_wgrad(const bp_view* X, const PW& pwx, const bp_view* Y, float* dst, void* workspace, size_t workspace_bytes,
+                  hipStream_t st);
+// conv_wgrad_flat.hip: weight gradient of the 16 -> 8 k7 head layer
+bool bp_wgrad_flat_ok(const bp_conv* cv, const bp_view* X, const bp_view* Y, const PW& pwy);
+size_t bp_wgrad_flat_workspace(const bp_view* X);
+int bp_wgrad_flat(const bp_view* X, const PW& pwx, const bp_view* Y, float* dst, void* workspace, size_t workspace_bytes,
+                  hipStream_t st, bool shared);
+// ... and of the thin stride-2 k4 layers (16 channels at full resolution, 32 at half)
+bool bp_wgrad_flat_s2_ok(const bp_conv* cv, const bp_view* X, const bp_view* Y, const PW& pwx, const PW& pwy);
+size_t bp_wgrad_flat_s2_workspace(const bp_view* Y);
+int bp_wgrad_flat_s2(const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* dst, void* workspace,
+                     size_t workspace_bytes, hipStream_t st, bool shared);
+
+// conv_bf16.hip: the bf16 gather entry points behind capi.hip
+bool bp_bf16_igemm_ok(const ConvGeom& g, const bp_view* in, const bp_view* out);
+int64_t bp_bf16_packed_elems(const ConvGeom& g);
+int bp_bf16_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, void* packed, hipStream_t st);
+int bp_bf16_igemm_run(const ConvGeom& g, const bp_view* in, const PW& pw, const void* packed, const float* bias,
+                      const bp_view* out, hipStream_t st, const IgemmStatsReq* stats = nullptr);
+size_t bp_bf16_stats_workspace(const ConvGeom& g, const bp_view* in, const bp_view* out, int mode);
+
+// conv_bf16_flat.hip: flattened-K kernel for the unit-stride k7 head layers; its weight image follows the generic one
+int64_t bp_bf16_flat_packed_elems(const ConvGeom& g);
+int bp_bf16_flat_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, uint16_t* dst, hipStream_t st);
+bool bp_bf16_flat_ok(const ConvGeom& g, const bp_view* in, const bp_view* out, const float* bias, int stats);
+size_t bp_bf16_flat_stats_workspace(const ConvGeom& g, const bp_view* in, const bp_view* out, int mode);
+int bp_bf16_flat_run(const ConvGeom& g, const bp_view* in, const PW& pw, const uint16_t* packed_flat, const bp_view* out,
+                     hipStream_t st, const IgemmStatsReq* sr);
+
+// conv_bf16_ws.hip: weights-stationary kernel of the 128 -> 128 k3 trunk; its weight image follows the other two
+void bp_bf16_ws_set(int v);
+int bp_bf16_ws_kind(const ConvGeom& g);
+int64_t bp_bf16_ws_packed_elems(const ConvGeom& g);
+int bp_bf16_ws_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, uint16_t* dst, hipStream_t st);
+bool bp_bf16_ws_ok(const ConvGeom& g, const bp_view* in, const bp_view* out, const float* bias, int mode);
+size_t bp_bf16_ws_stats_workspace(const ConvGeom& g, const bp_view* in, const bp_view* out);
+int bp_bf16_ws_run(const ConvGeom& g, const bp_view* in, const PW& pw, const uint16_t* packed_ws, const bp_view* out,
+                   hipStream_t st, const IgemmStatsReq* sr);
+
+// conv_bf16_head.hip: data gradient (+ activation backward) of the heads' 8 -> 1 k5 layer; its weight image comes last
+int64_t bp_bf16_head_packed_elems(const ConvGeom& g);
+int bp_bf16_head_pack(const ConvGeom& g, const WeightMap& wm, const float* w_torch, uint16_t* dst, hipStream_t st);
+bool bp_bf16_head_ok(const ConvGeom& g, const bp_view* in, const bp_view* out, const float* bias, int mode);
+size_t bp_bf16_head_stats_workspace(const ConvGeom& g, const bp_view* in, const bp_view* out, int mode);
+int bp_bf16_head_run(const ConvGeom& g, const bp_view* in, const uint16_t* packed_head, const bp_view* out,
+                     hipStream_t st, const IgemmStatsReq* sr);
+
+// pointwise.hip: sums of partial rows (the last stage of every statistics request)
+int bp_sum_partials(const double* partial, int nblk, int n, double* out, hipStream_t st);
+int bp_sum_partials_strided(const double* partial, int nblk, int stride, int n, double* out, hipStream_t st);
+// ... partial[nblk][n] -> sr->sums (and, with sr->fin, the batch-norm finalize)
+int bp_sum_partials_req(const double* partial, int nblk, int n, const IgemmStatsReq* sr, hipStream_t st);
+int bp_sum_partials3(const double* partial, int nblk, int c, double* sums, hipStream_t st);
+
+// pointwise_bf16.hip: the streaming kernels on dense bf16 views
+bool bp_bf16_dense_ok(const bp_view* v);
+size_t bp_bf16_reduce_workspace(const bp_view* x, int nsums);
+int bp_bf16_channel_sums(const bp_view* x, double* sums, void* workspace, hipStream_t st);
+int bp_bf16_act_backward(const bp_view* dout, const bp_view* dout2, const bp_view* raw, const PW& pw,
+                         const bp_view* act_out, const bp_view* g, double* sums, void* workspace, hipStream_t st);
+int bp_bf16_bn_backward_apply(const bp_view* dout, const bp_view* dout2, const bp_view* raw, const PW& pw,
+                              const bp_view* act_out, const double* abc, const bp_view* out, bool recompute_g,
+                              hipStream_t st);
+int bp_bf16_residual_forward(const bp_view* raw, const PW& pw, const bp_view* skip, const PW& spw, float slope,
+                             const bp_view* out, hipStream_t st);

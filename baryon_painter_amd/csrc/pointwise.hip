@@ -3,6 +3,7 @@
 // log-likelihood head and Adam.  All reductions are two-stage (per-block partials in a caller
 // workspace, then a fixed-order sum in double), so results are bitwise reproducible.
 #include "common.hpp"
+#include "kernels.hpp"
 #include "peer_dev.hpp"
 #include <math.h>
 
@@ -1011,18 +1012,6 @@ int bp_sum_partials(const double* partial, int nblk, int n, double* out, hipStre
   BP_CHECK_LAUNCH();
   return BP_OK;
 }
-
-// pointwise_bf16.hip: the same passes over dense bf16 views
-bool bp_bf16_dense_ok(const bp_view* v);
-size_t bp_bf16_reduce_workspace(const bp_view* x, int nsums);
-int bp_bf16_channel_sums(const bp_view* x, double* sums, void* workspace, hipStream_t st);
-int bp_bf16_act_backward(const bp_view* dout, const bp_view* dout2, const bp_view* raw, const PW& pw,
-                         const bp_view* act_out, const bp_view* g, double* sums, void* workspace, hipStream_t st);
-int bp_bf16_bn_backward_apply(const bp_view* dout, const bp_view* dout2, const bp_view* raw, const PW& pw,
-                              const bp_view* act_out, const double* abc, const bp_view* out, bool recompute_g,
-                              hipStream_t st);
-int bp_bf16_residual_forward(const bp_view* raw, const PW& pw, const bp_view* skip, const PW& spw, float slope,
-                             const bp_view* out, hipStream_t st);
 
 // A call whose views are bf16: every view must be a dense bf16 view of the same grid (the layouts the launch
 // plan produces for the generator trunk); anything else has no bf16 form.

@@ -6,6 +6,7 @@
 // Arithmetic is fp32 per element (inputs are 8-bit-mantissa values; the reference's double evaluation of the
 // batch-norm backward map would be rounded away by the bf16 store), sums are double.
 #include "common.hpp"
+#include "kernels.hpp"
 #include <cstdlib>
 
 namespace {
@@ -263,10 +264,6 @@ static inline unsigned stream_blocks(int64_t total8) {
 }
 
 }  // namespace
-
-// pointwise.hip
-int bp_sum_partials(const double* partial, int nblk, int n, double* out, hipStream_t st);
-int bp_sum_partials3(const double* partial, int nblk, int c, double* sums, hipStream_t st);
 
 bool bp_bf16_dense_ok(const bp_view* v) {
   return v && v->dtype == BP_BF16 && v->cstride == v->c && v->coff == 0 && v->c >= 8 && v->c <= 1024 &&
