@@ -23,6 +23,14 @@
 //   * epilogue per row from the accumulators: 16-byte bf16 stores (a lane holds 8 consecutive channels of a pixel: the
 //     A-fragment rows are ordered so), training-mode batch-norm sums {sum y, sum y^2} of the values AS STORED per lane
 //     in fp32 over the band (<= 256 terms), folded in double through LDS once per workgroup: one row per workgroup.
+//   * images wider than 64 pixels (multiples of 64 up to 256: the CGAN generator's 128-pixel trunk) are cut into 64-pixel column
+//     strips, one work item per image x band x strip (STRIPS instantiation of the k3 kernel only).  The two pad columns
+//     of a ring row then hold the neighbouring strips' pixels and are written WITH every row -- zeros where the image
+//     ends -- by the same side-work slots that stage the row; nothing fills them separately (a separate
+//     zero fill raced with the halo commit in the fp32 twin).  Every wave writes the same 32 halo slots with the same
+//     values (lane = (side, octet), the upper half of the wave repeats the lower): no wave or lane predicate, so the
+//     K-steps keep one scheduling region.  The eight octet planes a store group touches share a bank quad (plane stride
+//     = 0 mod 16 slots): an 8-way conflict on ONE ds_write_b128 per row and wave, against 288 MFMAs.
 #include "conv_bf16.hpp"
 #include <type_traits>
 
@@ -42,6 +50,7 @@ struct WsArgs {
   PW pw;
   int BR, bands;
   double* stat;                      // rows [workgroup][2][128]
+  int iw, strips;                    // k3 with column strips: image width and strips of W pixels per row (iw = W * strips)
 };
 
 template <int G> struct WsGeom {
@@ -76,7 +85,7 @@ __global__ __launch_bounds__(256) void ws_pack_kernel(WsPackArgs a) {
 #define WS_SGB(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
 constexpr int SG_VALU = 0x2, SG_MFMA = 0x8, SG_DSR = 0x100;
 
-template <int G, bool ACT, bool STATS>
+template <int G, bool ACT, bool STATS, bool STRIPS = false>
 __global__ __launch_bounds__(256) void ws3_bf16_kernel(WsArgs a) {
   using GM = WsGeom<G>;
   constexpr int W = GM::W, RP = GM::RP, PS = GM::PS;
@@ -87,9 +96,13 @@ __global__ __launch_bounds__(256) void ws3_bf16_kernel(WsArgs a) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lm = lane & 15, kq = lane >> 4;
-  const int n = blockIdx.x / a.bands, band = blockIdx.x % a.bands;
+  // work item = image x band (x strip: the strip index runs fastest, neighbouring strips share their halo columns in L2)
+  const int nb = STRIPS ? (int)(blockIdx.x / (unsigned)a.strips) : (int)blockIdx.x;
+  const int n = nb / a.bands, band = nb % a.bands;
   const int y0 = band * a.BR;
   const int y1 = min(y0 + a.BR, a.h);
+  const int x0 = STRIPS ? (int)(blockIdx.x % (unsigned)a.strips) * W : 0;      // first column of the strip
+  const int iw = STRIPS ? a.iw : W;                                            // image width
 
   // staging units of this thread: unit i = 8 pixels x 8 octets per wave instruction
   //   octet = (lane >> 3) + 8 * (ub & 1), pixel = (lane & 7) + 8 * (ub >> 1), ub = wave + 4 i
@@ -104,12 +117,22 @@ __global__ __launch_bounds__(256) void ws3_bf16_kernel(WsArgs a) {
     s_slot[i] = s_oc[i] * PS + 1 + px;
     s_off[i] = (unsigned)(px * a.in_cs + s_oc[i] * 8) * 2u;
   }
-  const char* in_img = reinterpret_cast<const char*>(a.in + (int64_t)n * a.h * W * a.in_cs + a.in_co);
-  const unsigned in_row = (unsigned)(W * a.in_cs) * 2u;
+  const char* in_img = reinterpret_cast<const char*>(a.in + ((int64_t)n * a.h * iw + x0) * a.in_cs + a.in_co);
+  const unsigned in_row = (unsigned)(iw * a.in_cs) * 2u;
   auto load_row = [&](int r, uint4 (&raw)[G]) {        // (r inside the image)
     const char* rowp = in_img + (size_t)((unsigned)r * in_row);           // wave-uniform: a scalar base + a lane offset
 #pragma unroll
     for (int i = 0; i < G; ++i) raw[i] = *reinterpret_cast<const uint4*>(rowp + s_off[i]);
+  };
+  // STRIPS: halo columns x0 - 1 and x0 + W, lane = (side, octet); beyond the image's edge the lane reads its strip's own
+  // edge pixel (an address inside the view) and the value is masked to zero
+  const int h_oc = lane & 15, h_side = (lane >> 4) & 1;
+  const bool h_in = h_side ? x0 + W < iw : x0 > 0;
+  const int h_slot = h_oc * PS + (h_side ? RP - 1 : 0);
+  const unsigned h_keep = h_in ? 0xffffffffu : 0u;
+  const int h_off = ((h_side ? (h_in ? W : W - 1) : (h_in ? -1 : 0)) * a.in_cs + h_oc * 8) * 2;
+  auto load_halo = [&](int r, uint4& hraw) {
+    if constexpr (STRIPS) hraw = *reinterpret_cast<const uint4*>(in_img + ((int64_t)((unsigned)r * in_row) + h_off));
   };
   // one half (4 channels: words 2h, 2h + 1) of a unit through the pending activation, in two phases that the row loop
   // places in different K-steps: (A) parameters + unpack + affine, (B) leaky ReLU + rounding
@@ -139,18 +162,30 @@ __global__ __launch_bounds__(256) void ws3_bf16_kernel(WsArgs a) {
     if (!inside) v = make_uint4(0u, 0u, 0u, 0u);
     img[s_slot[i] + rr * RP] = v;
   };
-  auto commit_row = [&](int r, bool inside, const uint4 (&raw)[G]) {
+  auto commit_row = [&](int r, bool inside, const uint4 (&raw)[G], uint4 hv) {
     const int rr = (r + 1) & (WS_R - 1);
 #pragma unroll
     for (int i = 0; i < G; ++i) commit_unit(i, rr, inside, raw[i]);
+    if constexpr (STRIPS) {
+      if constexpr (ACT) {
+        act_half(h_oc, 0, hv.x, hv.y, hv.x, hv.y);
+        act_half(h_oc, 1, hv.z, hv.w, hv.z, hv.w);
+      }
+      const unsigned k = inside ? h_keep : 0u;
+      img[h_slot + rr * RP] = make_uint4(hv.x & k, hv.y & k, hv.z & k, hv.w & k);
+    }
   };
 
   // ---- prologue: first three input rows requested, then the weights; zero columns; activation parameters
   uint4 raw0[G], raw1[G], raw2[G];
   const bool in0 = y0 - 1 >= 0, in2 = y0 + 1 < a.h;
+  uint4 hraw0 = make_uint4(0u, 0u, 0u, 0u), hraw1 = hraw0, hraw2 = hraw0;
   load_row(in0 ? y0 - 1 : y0, raw0);
   load_row(y0, raw1);
   load_row(in2 ? y0 + 1 : y0, raw2);
+  load_halo(in0 ? y0 - 1 : y0, hraw0);
+  load_halo(y0, hraw1);
+  load_halo(in2 ? y0 + 1 : y0, hraw2);
   bf8 wf[WS_NF];
   {
     const uint4* wsrc = reinterpret_cast<const uint4*>(a.wp) + (size_t)wave * WS_NF * 64 + lane;
@@ -165,25 +200,29 @@ __global__ __launch_bounds__(256) void ws3_bf16_kernel(WsArgs a) {
       else asm volatile("" : "+a"(wf[f]));
     }
   }
-  if (tid < 128) {
-    const int plane = tid >> 3, rr = (tid >> 1) & 3, side = tid & 1;
-    img[plane * PS + rr * RP + (side ? RP - 1 : 0)] = make_uint4(0u, 0u, 0u, 0u);
+  // (with strips the pad columns are the halo, written with every row -- zeros where the image ends: no fill here, it
+  //  would race with those writes)
+  if constexpr (!STRIPS) {
+    if (tid < 128) {
+      const int plane = tid >> 3, rr = (tid >> 1) & 3, side = tid & 1;
+      img[plane * PS + rr * RP + (side ? RP - 1 : 0)] = make_uint4(0u, 0u, 0u, 0u);
+    }
   }
   if constexpr (ACT) {
     for (int i = tid; i < WS_C; i += 256) { lpw[i] = a.pw.scale[i]; lpw[WS_C + i] = a.pw.shift[i]; lpw[2 * WS_C + i] = a.pw.slope[i]; }
     __syncthreads();
   }
-  commit_row(y0 - 1, in0, raw0);
-  commit_row(y0, true, raw1);
-  commit_row(y0 + 1, in2, raw2);
+  commit_row(y0 - 1, in0, raw0, hraw0);
+  commit_row(y0, true, raw1, hraw1);
+  commit_row(y0 + 1, in2, raw2, hraw2);
   __syncthreads();
 
   float s1[8], s2[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
   const int lbase = kq * PS + lm;                       // slot of (plane kq, pixel lm) in ring row 0
-  char* out_img = reinterpret_cast<char*>(a.out + (int64_t)n * a.h * W * a.out_cs + a.out_co);
-  const unsigned out_row = (unsigned)(W * a.out_cs) * 2u;
+  char* out_img = reinterpret_cast<char*>(a.out + ((int64_t)n * a.h * iw + x0) * a.out_cs + a.out_co);
+  const unsigned out_row = (unsigned)(iw * a.out_cs) * 2u;
   const unsigned o_off = (unsigned)(lm * a.out_cs + 32 * wave + 8 * kq) * 2u, o_g = (unsigned)(16 * a.out_cs) * 2u;
 
   // Software pipeline over rows: while row y is multiplied into acc[P], the accumulators of row y - 1 (acc[P ^ 1]) are
@@ -222,6 +261,7 @@ __global__ __launch_bounds__(256) void ws3_bf16_kernel(WsArgs a) {
     constexpr bool PREV = decltype(PREV_)::value;
     const bool in_next = y + 2 < a.h;
     load_row(in_next ? y + 2 : a.h - 1, raw0);          // (always: beyond the band's last row it lands in a free slot)
+    load_halo(in_next ? y + 2 : a.h - 1, hraw0);
     const int rr_next = (y + 3) & (WS_R - 1);
     const unsigned keep = in_next ? 0xffffffffu : 0u;   // rows below the image are zero
     int rbase[3];
@@ -244,6 +284,7 @@ __global__ __launch_bounds__(256) void ws3_bf16_kernel(WsArgs a) {
       //    SIMD's issue port for 8 of its 16 cycles, a vector instruction for 4)
       //    steps 1 .. 3G: previous row, group g: round + store | sums of channels 0-3 | of channels 4-7
       //    steps 13 .. 13 + 4G: input row y + 2, unit i: half 0 affine | half 0 ReLU | half 1 affine | half 1 ReLU + write
+      //    steps 13 + 4G .. 17 + 4G (STRIPS, G = 4: steps 29 .. 32): the row's two halo columns, as one more unit
       if constexpr (PREV) {
         if (s >= 1 && s < 1 + 3 * G) {
           const int g = (s - 1) / 3, part = (s - 1) % 3;
@@ -263,6 +304,24 @@ __global__ __launch_bounds__(256) void ws3_bf16_kernel(WsArgs a) {
         }
         if (ph == 3) {          // (a mask, not a branch: a branch would cut the K-step's scheduling region in two)
           img[s_slot[i] + rr_next * RP] = make_uint4(cv.x & keep, cv.y & keep, cv.z & keep, cv.w & keep);
+        }
+      }
+      if constexpr (STRIPS) {
+        static_assert(!STRIPS || 17 + 4 * G <= 36, "the halo unit needs four K-steps after the staging units");
+        if (s >= 13 + 4 * G && s < 17 + 4 * G) {
+          const int ph = s - (13 + 4 * G);
+          if constexpr (ACT) {
+            if (ph == 0) { cv = hraw0; act_a(h_oc, 0, cv.x, cv.y, ct, csl); }
+            else if (ph == 1) act_b(ct, csl, cv.x, cv.y);
+            else if (ph == 2) act_a(h_oc, 1, cv.z, cv.w, ct, csl);
+            else act_b(ct, csl, cv.z, cv.w);
+          } else {
+            if (ph == 0) cv = hraw0;
+          }
+          if (ph == 3) {
+            const unsigned k = keep & h_keep;
+            img[h_slot + rr_next * RP] = make_uint4(cv.x & k, cv.y & k, cv.z & k, cv.w & k);
+          }
         }
       }
       // -- the step's MFMAs
@@ -866,22 +925,32 @@ bool ws_enabled() {
 int g_ws_override = -1;       // bp_set_option("bf16_ws", v)
 
 int ws_G(int w) { return w == 64 ? 4 : w == 32 ? 2 : w == 16 ? 1 : 0; }
+// k3 only: 64-pixel column strips of an image wider than 64 pixels (multiples of 64 up to WS_MAX_W), else one strip: the
+// image itself.  The cap is the widest 128-channel trunk a model here has use for (tile / 4 of a 1024^2 tile); a wider
+// layer -- 128 channels at the full 512-pixel resolution of a tile, which no model runs -- stays on the tiled kernel, as
+// tests/golden/dispatch_table.json records it.
+constexpr int WS_MAX_W = 256;
+int ws_strips(int kind, int w) { return kind == 3 && w > 64 && w <= WS_MAX_W && w % 64 == 0 ? w / 64 : 1; }
+// pixel groups of 16 per work item: the strip's with strips, else the image's (0: a width the kernels do not take)
+int ws_G_of(int kind, int w) { return ws_strips(kind, w) > 1 ? 4 : ws_G(w); }
 
-// rows per band: whole image per workgroup when there are many images, else bands of >= 4 rows so that ~256 workgroups exist
-void ws_bands(int n, int h, int* BR, int* bands) {
+// rows per band: whole image per workgroup when there are many images, else bands of >= 4 rows so that ~256 workgroups
+// exist (counting strips).  Bands only deal rows to workgroups: a pixel's 36 K-steps run in the same order in every band.
+void ws_bands(int n, int h, int strips, int* BR, int* bands) {
   int br = h;
-  while (br > 4 && (int64_t)n * bp_ceil_div(h, br) < 256) br = bp_ceil_div(br, 2);
+  while (br > 4 && (int64_t)n * strips * bp_ceil_div(h, br) < 256) br = bp_ceil_div(br, 2);
   *BR = br;
   *bands = bp_ceil_div(h, br);
 }
 
-template <int KIND, int G, bool ACT, bool STATS>
+template <int KIND, int G, bool ACT, bool STATS, bool STRIPS>
 int ws_launch(const WsArgs& a, unsigned grid, hipStream_t st) {
+  static_assert(!STRIPS || (KIND == 3 && G == 4), "column strips: the k3 kernel at 64-pixel strips only");
   // (the transposed kernel folds its statistics through 32 KB of LDS: more than the image at W = 16)
   constexpr size_t lds = KIND == 3 ? WsGeom<G>::lds_bytes : KIND == 4 ? W4Geom<G>::lds_bytes
                          : (WsGeom<G>::lds_bytes > 32768 ? WsGeom<G>::lds_bytes : 32768);
   auto kern = [] {
-    if constexpr (KIND == 3) return &ws3_bf16_kernel<G, ACT, STATS>;
+    if constexpr (KIND == 3) return &ws3_bf16_kernel<G, ACT, STATS, STRIPS>;
     else if constexpr (KIND == 4) return &ws4_bf16_kernel<G, ACT, STATS>;
     else return &wst_bf16_kernel<G, ACT, STATS>;
   }();
@@ -892,10 +961,10 @@ int ws_launch(const WsArgs& a, unsigned grid, hipStream_t st) {
   BP_CHECK_LAUNCH();
   return BP_OK;
 }
-template <int KIND, int G>
+template <int KIND, int G, bool STRIPS = false>
 int ws_launch_g(const WsArgs& a, bool act, bool stats, unsigned grid, hipStream_t st) {
-  if (act) return stats ? ws_launch<KIND, G, true, true>(a, grid, st) : ws_launch<KIND, G, true, false>(a, grid, st);
-  return stats ? ws_launch<KIND, G, false, true>(a, grid, st) : ws_launch<KIND, G, false, false>(a, grid, st);
+  if (act) return stats ? ws_launch<KIND, G, true, true, STRIPS>(a, grid, st) : ws_launch<KIND, G, true, false, STRIPS>(a, grid, st);
+  return stats ? ws_launch<KIND, G, false, true, STRIPS>(a, grid, st) : ws_launch<KIND, G, false, false, STRIPS>(a, grid, st);
 }
 template <int KIND>
 int ws_launch_k(int G, const WsArgs& a, bool act, bool stats, unsigned grid, hipStream_t st) {
@@ -910,7 +979,8 @@ int ws_launch_k(int G, const WsArgs& a, bool act, bool stats, unsigned grid, hip
 
 void bp_bf16_ws_set(int v) { g_ws_override = v; }
 
-// 3: the k3 s1 p1 128 -> 128 trunk layer (either direction); 4: the strided gather k4 s2 p1 64 -> 128; 5: the transposed
+// 3: the k3 s1 p1 128 -> 128 trunk layer (either direction; widths 16, 32, 64 and, in 64-pixel column strips, 128, 192
+// and 256); 4: the strided gather k4 s2 p1 64 -> 128; 5: the transposed
 // form k4 s2 p1 128 -> 64; 0: none
 int bp_bf16_ws_kind(const ConvGeom& g) {
   if (g.gather_transposed && g.k == 4 && g.stride == 2 && g.pad == 1 && g.nphase == 2 && g.taps == 2 && g.IS == 1 && g.OS == 2 &&
@@ -947,7 +1017,8 @@ bool bp_bf16_ws_ok(const ConvGeom& g, const bp_view* in, const bp_view* out, con
   if (!k || !in || !out || bias || (mode != 0 && mode != 1)) return false;
   if (in->dtype != BP_BF16 || out->dtype != BP_BF16 || in->c != g.cin_g || out->c != g.cout_g) return false;
   const bp_view* grid_v = k == 5 ? in : out;            // the view whose rows the kernel walks (the coarse one)
-  if (in->n != out->n || !ws_G(grid_v->w)) return false;
+  const int G = ws_G_of(k, grid_v->w), strips = ws_strips(k, grid_v->w);
+  if (in->n != out->n || !G) return false;
   if (k == 3 && (in->w != out->w || in->h != out->h)) return false;
   if (k == 4 && (in->w != 2 * out->w || in->h != 2 * out->h)) return false;
   if (k == 5 && (out->w != 2 * in->w || out->h != 2 * in->h)) return false;
@@ -957,16 +1028,18 @@ bool bp_bf16_ws_ok(const ConvGeom& g, const bp_view* in, const bp_view* out, con
   if ((int64_t)in->h * in->w * in->cstride * 2 >= (int64_t)1 << 31 || (int64_t)out->h * out->w * out->cstride * 2 >= (int64_t)1 << 31)
     return false;
   int BR, bands;
-  ws_bands(grid_v->n, grid_v->h, &BR, &bands);
-  if (mode == 1 && BR * ws_G(grid_v->w) > 256) return false;          // a lane's fp32 partial sums: <= 256 terms
-  return (int64_t)out->n * bands <= 0x7fffffff;
+  ws_bands(grid_v->n, grid_v->h, strips, &BR, &bands);
+  if (mode == 1 && BR * G > 256) return false;          // a lane's fp32 partial sums: <= 256 terms (a strip item has its own row)
+  return (int64_t)out->n * bands * strips <= 0x7fffffff;
 }
 
 size_t bp_bf16_ws_stats_workspace(const ConvGeom& g, const bp_view* in, const bp_view* out) {
-  const bp_view* grid_v = bp_bf16_ws_kind(g) == 5 ? in : out;
+  const int kind = bp_bf16_ws_kind(g);
+  const bp_view* grid_v = kind == 5 ? in : out;
+  const int strips = ws_strips(kind, grid_v->w);
   int BR, bands;
-  ws_bands(grid_v->n, grid_v->h, &BR, &bands);
-  return bp_stats_rows_bytes((int64_t)out->n * bands, g.cout_g);
+  ws_bands(grid_v->n, grid_v->h, strips, &BR, &bands);
+  return bp_stats_rows_bytes((int64_t)out->n * bands * strips, g.cout_g);
 }
 
 int bp_bf16_ws_run(const ConvGeom& g, const bp_view* in, const PW& pw, const u16* packed_ws, const bp_view* out,
@@ -977,8 +1050,9 @@ int bp_bf16_ws_run(const ConvGeom& g, const bp_view* in, const PW& pw, const u16
   const int kind = bp_bf16_ws_kind(g);
   const bp_view* grid_v = kind == 5 ? in : out;
   a.n = out->n; a.h = grid_v->h; a.wp = packed_ws; a.pw = pw;
-  ws_bands(grid_v->n, grid_v->h, &a.BR, &a.bands);
-  const int64_t rows = (int64_t)out->n * a.bands;
+  a.iw = grid_v->w; a.strips = ws_strips(kind, grid_v->w);
+  ws_bands(grid_v->n, grid_v->h, a.strips, &a.BR, &a.bands);
+  const int64_t rows = (int64_t)out->n * a.bands * a.strips;          // work items: image x band x strip
   if (sr) {
     const size_t need = bp_stats_rows_bytes(rows, g.cout_g);
     if (sr->mode != 1 || !need) return BP_EUNSUPPORTED;
@@ -986,8 +1060,9 @@ int bp_bf16_ws_run(const ConvGeom& g, const bp_view* in, const PW& pw, const u16
     a.stat = reinterpret_cast<double*>(sr->ws);
   }
   const bool act = pw.scale != nullptr;
-  const int G = ws_G(grid_v->w);
-  const int rc = kind == 3 ? ws_launch_k<3>(G, a, act, sr != nullptr, (unsigned)rows, st)
+  const int G = ws_G_of(kind, grid_v->w);
+  const int rc = a.strips > 1 ? ws_launch_g<3, 4, true>(a, act, sr != nullptr, (unsigned)rows, st)
+                 : kind == 3 ? ws_launch_k<3>(G, a, act, sr != nullptr, (unsigned)rows, st)
                  : kind == 4 ? ws_launch_k<4>(G, a, act, sr != nullptr, (unsigned)rows, st)
                              : ws_launch_k<5>(G, a, act, sr != nullptr, (unsigned)rows, st);
   if (rc != BP_OK || !sr) return rc;

@@ -177,11 +177,24 @@ class _GanPaintPlan:
     """The generator alone, eval mode only: what painting needs of a ``_GanPlan``.  No discriminator units, no
     ``prepare_backward`` (no gradient buffers, no weight-gradient workspace), no side stream, and the data-gradient
     images of the packed weights are dropped.  The units are compiled exactly as ``_GanPlan`` compiles its generator
-    (same names, same ``impl``), so the forward launches -- and the bits they produce -- are the same."""
+    (same names, same ``impl``), so the forward launches -- and the bits they produce -- are the same.
 
-    def __init__(self, model, n):
+    ``paint_dtype="bf16"``: the 128-channel trunk runs on the bf16 matrix-core kernels and is stored as bf16 -- the last
+    encoder (fp32 in, bf16 out), the residual blocks (bf16 throughout, their tails through bp_bf16_residual_forward) and
+    the first decoder (bf16 in, fp32 out).  The k9 stem, the first encoder, the last decoder and the k9 head stay fp32.
+    The two converted layers have a bias: in this eval-only plan it goes to the bf16 kernel with the forward call
+    (``bf16_bias``; graph.ConvUnit turns bf16 off for a biased layer of any other plan)."""
+
+    PAINT_DTYPES = ("fp32", "bf16")
+    bf16_bias = True
+
+    def __init__(self, model, n, paint_dtype="fp32"):
+        if paint_dtype not in self.PAINT_DTYPES:
+            raise ValueError(f"paint_dtype {paint_dtype!r}: one of {self.PAINT_DTYPES}")
         self.model, self.lib, self.device, self.impl, self.sync = model, model._lib, model.device, L.IMPL_AUTO, model.sync
         self.n, self.ws_bytes, self.ws, self.prof = n, 0, None, None
+        self.paint_dtype = paint_dtype
+        self._bf16_units, self._bf16_outs = self.bf16_policy(model.g_arch) if paint_dtype == "bf16" else ((), ())
         H, W = model.tile_size, model.tile_size
         self.y2 = Slot.new(n, H, W, 2, self.device)
         gu, gs, tr = compile_sequential(self, "generator.", model.g_arch, model.generator, self.y2,
@@ -196,6 +209,34 @@ class _GanPaintPlan:
             self.units += u.body if hasattr(u, "body") else [u]
         for u in self.units:
             u.packed_bwd = None                   # (maybe_pack skips a direction that has no image)
+        for u in self.units:
+            want = self.bf16_unit(u.name)
+            if want != u.bf16 or (want and self.lib.bp_conv_bf16_supported(
+                    C.byref(u.cv), L.PACK_FWD, C.byref(u.inp.view), C.byref(u.out.view)) != 1):
+                raise NotImplementedError(f"{u.name}: the bf16 kernels do not take this layer with these views")
+
+    @staticmethod
+    def bf16_policy(g_arch, prefix="generator."):
+        """(name prefixes of the units that run in bf16, ... of those that also STORE bf16): the residual blocks, the
+        convolution in front of the first one (it writes bf16) and the one behind the last (it reads bf16, writes fp32)."""
+        names = [layer[0].lower() for layer in g_arch]
+        res = [i for i, nm in enumerate(names) if nm == "residual block"]
+        if not res or res != list(range(res[0], res[-1] + 1)):
+            return (), ()
+        convs = [i for i, nm in enumerate(names) if nm in ("conv", "transp conv")]
+        enc, dec = max(i for i in convs if i < res[0]), min(i for i in convs if i > res[-1])
+        outs = (f"{prefix}{enc}",) + tuple(f"{prefix}{i}.res_block." for i in res)
+        return outs + (f"{prefix}{dec}",), outs
+
+    @staticmethod
+    def _named(name, keys):
+        return any(name.startswith(k) if k.endswith(".") else name == k for k in keys)
+
+    def bf16_unit(self, name):
+        return self._named(name, self._bf16_units)
+
+    def bf16_out(self, name):
+        return self._named(name, self._bf16_outs)
 
     def need_ws(self, nbytes):                    # (the eval forward uses no workspace: batch-norm runs on its running
         self.ws_bytes = max(self.ws_bytes, int(nbytes))     # statistics; the sizes are recorded and nothing is allocated)
@@ -229,8 +270,11 @@ class CGAN(torch.nn.Module):
     """Generator + discriminator with their alternating training step."""
 
     def __init__(self, tile_size=512, device="cuda:0", n_res=9, lambda_perceptual=2.5, g_arch=None, d_arch=None,
-                 sync=None):
-        """``sync`` (baryon_painter_amd.dist.Sync): data parallel, one process per GPU -- the generator's batch-norm
+                 sync=None, paint_dtype="fp32"):
+        """``paint_dtype``: "fp32" or "bf16" -- the storage and matrix-core type of the 128-channel trunk in the
+        INFERENCE plan (eval-mode ``generate``, ``paint_graph``; see ``_GanPaintPlan``).  Training ignores it.
+
+        ``sync`` (baryon_painter_amd.dist.Sync): data parallel, one process per GPU -- the generator's batch-norm
         statistics become those of the global batch, the discriminator's and the generator's gradients are averaged
         over ranks as ONE flat buffer each, right after their backward pass (the spectral-norm power iteration is
         parameter-side arithmetic and identical on every rank)."""
@@ -240,6 +284,9 @@ class CGAN(torch.nn.Module):
         if self.device.type != "cuda":
             raise RuntimeError("baryon_painter_amd.CGAN runs on an AMD GPU only; there is no CPU implementation.")
         self._lib = L.load()
+        if paint_dtype not in _GanPaintPlan.PAINT_DTYPES:
+            raise ValueError(f"paint_dtype {paint_dtype!r}: one of {_GanPaintPlan.PAINT_DTYPES}")
+        self.paint_dtype = paint_dtype
         self.tile_size = tile_size
         self.lambda_perceptual = lambda_perceptual
         self.g_arch = g_arch or cgan_generator_architecture(n_res)
@@ -250,8 +297,8 @@ class CGAN(torch.nn.Module):
         self.to(self.device)
         self.sn_layers = [m for m in self.discriminator if isinstance(m, SNConv2d)]
         self._plans = {}
-        self._paint_plans = {}          # n -> _GanPaintPlan (eval-mode generate, paint_graph)
-        self._paint_graphs = {}         # n -> the captured paint pipeline of paint_graph
+        self._paint_plans = {}          # _paint_key(n) -> _GanPaintPlan (eval-mode generate, paint_graph)
+        self._paint_graphs = {}         # _paint_key(n) -> the captured paint pipeline of paint_graph
         self._grads = {}
         self._flat = {}
         for name, net in (("d", self.discriminator), ("g", self.generator)):
@@ -318,13 +365,19 @@ class CGAN(torch.nn.Module):
             raise ValueError("one redshift per sample")
         return y, self.z_transform(z)
 
+    def _paint_key(self, n):
+        """Key of the per-(n, paint_dtype) caches: ``n`` itself for fp32 (the key of before the dtype existed)."""
+        return n if self.paint_dtype == "fp32" else (n, self.paint_dtype)
+
     def _paint_plan(self, n):
-        if n not in self._paint_plans:
-            self._paint_plans[n] = _GanPaintPlan(self, n)
-        return self._paint_plans[n]
+        key = self._paint_key(n)
+        if key not in self._paint_plans:
+            self._paint_plans[key] = _GanPaintPlan(self, n, self.paint_dtype)
+        return self._paint_plans[key]
 
     def release_paint_buffers(self):
-        """Free the inference plans and the captured paint graphs (they are rebuilt on the next use)."""
+        """Free the inference plans and the captured paint graphs of both paint dtypes (they are rebuilt on the next
+        use)."""
         self._paint_graphs.clear()
         self._paint_plans.clear()
 
@@ -356,9 +409,9 @@ class CGAN(torch.nn.Module):
         either model's block; the generator has no latent noise and nothing reads them."""
         if self.training:
             raise RuntimeError("paint_graph is an eval-mode (paint) path: call model.train(False) first")
-        g = self._paint_graphs.get(n)
+        g = self._paint_graphs.get(self._paint_key(n))
         if g is None:
-            g = self._paint_graphs[n] = self._capture_paint_graph(n)
+            g = self._paint_graphs[self._paint_key(n)] = self._capture_paint_graph(n)
         for u in g["units"]:
             u.maybe_pack()                       # eager, a no-op unless the weights changed
             u.maybe_bn_eval()                    # ... or the running statistics

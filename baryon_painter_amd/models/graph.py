@@ -307,7 +307,10 @@ class ConvUnit:
         self.out_pw = out_pw
         # bf16 matrix-core kernels for this layer (plan policy: the generator trunk under dtype="bf16"), and bf16
         # storage of its output when the plan says every consumer reads bf16
-        self.bf16 = bool(getattr(plan, "bf16_unit", lambda n_: False)(name)) and holder.bias is None \
+        # (a bias: the training-mode epilogues have none, so only a plan that never trains -- ``bf16_bias`` -- keeps bf16;
+        #  its forward hands the bias to bp_bf16_igemm_run, which adds it in fp32 before the store)
+        self.bf16 = bool(getattr(plan, "bf16_unit", lambda n_: False)(name)) \
+            and (holder.bias is None or bool(getattr(plan, "bf16_bias", False))) \
             and plan.lib.bp_conv_bf16_supported(C.byref(cv), L.PACK_FWD, None, None) == 1 \
             and plan.lib.bp_conv_bf16_supported(C.byref(cv), L.PACK_BWD, None, None) == 1
         out_bf16 = self.bf16 and out_slot is None and bool(plan.bf16_out(name)) and c >= 8 and (c & (c - 1)) == 0

@@ -132,7 +132,9 @@ int64_t bp_conv_bf16_packed_elems(const bp_conv* cv, int dir);
  * direction: x for BP_PACK_FWD, dy for BP_PACK_BWD; `out` = the produced one): 3 = the k3 s1 128 -> 128 trunk kernel (bf16
  * views: csrc/conv_bf16_ws.hip; fp32 views: csrc/conv_ws_f32.hip), 4 = the bf16 strided gather k4 s2 64 -> 128, 5 = the bf16
  * transposed form k4 s2 128 -> 64, 0 = none
- * (the tiled / flattened-K kernels).  For profiles and bench.py's kernel labels; follows bp_set_option. */
+ * (the tiled / flattened-K kernels).  Widths: kind 3 takes 16, 32, 64 and, in 64-pixel column strips, wider multiples of 64 (bf16
+ * views: 128, 192, 256; fp32 views: any; 128 is the CGAN generator's trunk at 512^2 tiles); kinds 4 and 5 take 16, 32, 64
+ * on their coarse grid.  The answer never depends on the batch size.  For profiles and bench.py's kernel labels; follows bp_set_option. */
 int bp_conv_ws_kind(const bp_conv* cv, int dir, const bp_view* in, const bp_view* out);
 int bp_conv_bf16_pack(const bp_conv* cv, int dir, const float* w_torch, void* packed, void* stream);
 int bp_conv_bf16_supported(const bp_conv* cv, int dir, const bp_view* in, const bp_view* out);

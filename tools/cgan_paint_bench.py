@@ -11,7 +11,11 @@ memory of the inference plan against the training plan.  One JSON line per measu
   plan_memory                torch.cuda.max_memory_allocated over building a plan for ``--mem-n`` tiles and one eval
                              forward through it, inference plan and training plan
 
-Usage: python tools/cgan_paint_bench.py [--batch 64] [--tiles 256] [--reps 3] [--mem-n 6] [--skip plane,memory]"""
+``--paint-dtype bf16``: the same lines for the bf16 inference plan (CGAN(paint_dtype="bf16"): the 128-channel trunk on the
+bf16 matrix-core kernels); every line carries the dtype.
+
+Usage: python tools/cgan_paint_bench.py [--batch 64] [--tiles 256] [--reps 3] [--mem-n 6] [--skip plane,memory]
+                                        [--paint-dtype fp32|bf16]"""
 import argparse
 import contextlib
 import ctypes as C
@@ -32,13 +36,13 @@ from baryon_painter_amd import lightcone as LC  # noqa: E402
 TILE, N_RES, N_PLANE = 512, 9, 4096
 
 
-def make_painter(dev):
+def make_painter(dev, paint_dtype="fp32"):
     from baryon_painter_amd.painter import CGANPainter
     from baryon_painter_amd.utils.datasets import SyntheticTileDataset
     torch.manual_seed(1234)
     ds = SyntheticTileDataset(n_sample=8, tile_size=TILE, seed=3)
     with contextlib.redirect_stdout(sys.stderr):
-        pt = CGANPainter(training_data_set=ds, tile_size=TILE, compute_device=dev, n_res=N_RES)
+        pt = CGANPainter(training_data_set=ds, tile_size=TILE, compute_device=dev, n_res=N_RES, paint_dtype=paint_dtype)
     pt.model.train(False)
     return pt, ds
 
@@ -80,7 +84,7 @@ def plan_memory(pt, n):
         torch.cuda.reset_peak_memory_stats()
         base = torch.cuda.memory_allocated()
         with torch.no_grad():
-            plan = cls(m, n)
+            plan = cls(m, n, m.paint_dtype) if cls is _GanPaintPlan else cls(m, n)
             if cls is _GanPaintPlan:
                 plan.generate(y, zc, torch.empty_like(y))
             else:
@@ -88,7 +92,7 @@ def plan_memory(pt, n):
         torch.cuda.synchronize()
         res[name + "_MiB"] = round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1)
         del plan
-    return {"metric": "plan_memory", "n": n, "tile": TILE, "n_res": N_RES, **res}
+    return {"metric": "plan_memory", "n": n, "tile": TILE, "n_res": N_RES, "paint_dtype": m.paint_dtype, **res}
 
 
 def main():
@@ -99,15 +103,16 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--mem-n", type=int, default=6)
     ap.add_argument("--skip", default="")
+    ap.add_argument("--paint-dtype", default="fp32", choices=("fp32", "bf16"))
     args = ap.parse_args()
     skip = set(filter(None, args.skip.split(",")))
     if not torch.cuda.is_available():
         raise SystemExit("cgan_paint_bench needs a GPU")
-    pt, ds = make_painter("cuda:0")
+    pt, ds = make_painter("cuda:0", args.paint_dtype)
     B, z = args.batch, 0.5
     base = np.stack([ds.raw_fields(i)[0] for i in range(8)])
     tiles = np.ascontiguousarray(np.resize(base, (args.tiles, TILE, TILE)))
-    common = {"tile": TILE, "n_res": N_RES}
+    common = {"tile": TILE, "n_res": N_RES, "paint_dtype": args.paint_dtype}
 
     few = tiles[:args.per_tile]
     pt.paint(few[0], z=z)
