@@ -148,6 +148,10 @@ SIGNATURES = {
     "bp_l1_sum": (C.c_int, [_VP, _P, _P, _P, C.c_size_t, _P]),
     "bp_tanh_l1_backward": (C.c_int, [_VP, _P, _VP, C.c_float, _VP, _P]),
     "bp_gather_tiles": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P]),
+    "bp_tile_minima": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P]),
+    "bp_gather_tiles_scales_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "bp_gather_tiles_scales": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,
+                                         C.c_size_t, _P, _P]),
     "bp_adam_step": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
                                C.c_int32, _P]),
     "bp_adam_step_dev": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, _P]),

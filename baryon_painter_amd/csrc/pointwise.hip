@@ -5,6 +5,7 @@
 #include "common.hpp"
 #include "kernels.hpp"
 #include "peer_dev.hpp"
+#include "assemble.hpp"
 #include <math.h>
 
 namespace {
@@ -824,19 +825,7 @@ __global__ __launch_bounds__(RB) void tanh_l1_backward_kernel(ViewD fake, const 
 }
 
 // ---------------------------------------------------------------- device-side batch assembly
-// One descriptor per (sample, slab): where the tile starts in the HBM-resident stack and how the
-// dihedral tile permutation maps output (r,c) to source (row,col):  row = r0 + rr*r + rc*c, ...
-struct TileDesc {
-  const float* base;      // &stack[slice][tile_y*t][tile_x*t]
-  int32_t pitch;          // n_grid
-  int32_t r0, rr, rc, c0, cr, cc;
-  int32_t pad_;
-};
-struct SampleXform {      // x -> log(scale*x * inv_sigma + 1) * inv_k   (mode 1), or scale*x (mode 0)
-  double scale, inv_sigma, inv_k;
-  int32_t mode, pad_;
-};
-
+// (descriptors and the value of a gathered pixel: assemble.hpp, shared with the gather into a pyramid, scales.hip)
 __global__ __launch_bounds__(RB) void gather_tiles_kernel(const TileDesc* d100, const TileDesc* d150,
                                                           const SampleXform* xf, float* out, int t, int64_t total) {
   const int64_t i = (int64_t)blockIdx.x * RB + threadIdx.x;
@@ -845,14 +834,9 @@ __global__ __launch_bounds__(RB) void gather_tiles_kernel(const TileDesc* d100, 
   const int r = (i / t) % t;
   const int n = i / ((int64_t)t * t);
   const TileDesc a = d100[n], b = d150[n];
-  const float va = a.base[(int64_t)(a.r0 + a.rr * r + a.rc * c) * a.pitch + (a.c0 + a.cr * r + a.cc * c)];
-  const float vb = b.base[(int64_t)(b.r0 + b.rr * r + b.rc * c) * b.pitch + (b.c0 + b.cr * r + b.cc * c)];
-  const float s = va + vb;                                   // float32 add, like the host path
+  const float s = tile_sum(a, b, r, c);
   const SampleXform x = xf[n];
-  // (python float * float32 array = a float32 multiply with the scalar rounded to float32, datasets.py:399)
-  double v = x.scale == 1.0 ? (double)s : (double)((float)x.scale * s);
-  if (x.mode == 1) v = log(v * x.inv_sigma + 1.0) * x.inv_k;
-  out[i] = (float)v;
+  out[i] = tile_transform(tile_scale(s, x), x);
 }
 
 // ---------------------------------------------------------------- Adam

@@ -4,6 +4,9 @@
 //   bp_paint_load_scales2  bp_paint_load2 with the pyramid between the shift-log transform and the layout
 //   bp_paint_store_scales  bp_paint_store for a `levels`-channel head: the inverse of the pyramid (channel 0, or the
 //                          float32 sum of the channels in channel order), then the inverse shift-log
+//   bp_tile_minima         per-tile minimum of a gathered training tile (the datasets' subtract_minimum)
+//   bp_gather_tiles_scales bp_gather_tiles [minus the minima] with the pyramid behind the transform, stored as NCHW
+//                          planes: a training batch of a multi-scale model, assembled from the stacks in HBM
 // The pyramid: d = x; for i = n_scale-1 .. 1: g = gaussian_filter(d, sigma_i); scale i = g; d -= g; scale 0 = d; with
 // include_original a leading channel holds x.  What scipy.ndimage.gaussian_filter does on a float32 tile is the
 // contract, restated here:
@@ -24,7 +27,11 @@
 // planes with it, so a pixel's channels are written by two launches, not by one per channel.  No atomics, no host
 // synchronisation; every launch can be captured.  Except for the explicit fma of the filter sums the file is compiled
 // without floating-point contraction (the host expressions round every operation).
+// The training batch (bp_gather_tiles_scales) gathers inside the axis-0 pass of the coarsest level: the staged strip is
+// made of gathered, transformed pixels (assemble.hpp: bp_gather_tiles' expression), so the stacks are read once and the
+// transformed tile is written once, for the residual and the original, beside the axis-0 intermediate.
 #include "common.hpp"
+#include "assemble.hpp"
 #include <math.h>
 
 #pragma clang fp contract(off)
@@ -47,7 +54,32 @@ __device__ __forceinline__ int fold(int i, int n) {
 
 struct Dst {
   float* p;       // nullptr: no such destination
-  int cs, co;
+  int cs, co;     // NHWC view: channel stride and offset; NCHW planes: channels per sample and first channel
+};
+
+// what bp_gather_tiles reads, the optional minima, and where the transformed tile goes
+struct GatherArgs {
+  const TileDesc* d100;
+  const TileDesc* d150;
+  const SampleXform* xf;
+  const float* minima;  // nullptr: nothing is subtracted
+  float* v;             // (n, t, t): the transformed tile
+};
+
+// one sample's share of GatherArgs, wave-uniform
+struct Gathered {
+  TileDesc a, b;
+  SampleXform x;
+  float mn;
+  bool sub;
+  __device__ __forceinline__ Gathered(const GatherArgs& g, int n)
+      : a(g.d100[n]), b(g.d150[n]), x(g.xf[n]), mn(g.minima ? g.minima[n] : 0.f), sub(g.minima != nullptr) {}
+  // bp_gather_tiles' value with the float32 `d - d.min()` of datasets.py:402 in front of the transform
+  __device__ __forceinline__ float at(int r, int c) const {
+    float s = tile_scale(tile_sum(a, b, r, c), x);
+    if (sub) s = s - mn;
+    return tile_transform(s, x);
+  }
 };
 
 // raw (n, 1, h, w) -> the float32 shift-log value of bp_paint_load: (float) (log((double) x / sigma + 1) / k)
@@ -81,6 +113,73 @@ __global__ __launch_bounds__(RB) void filter_axis0_kernel(const float* src, floa
   }
 }
 
+// The same pass with the gather in front: the strip is staged from the stacks, and the rows a workgroup owns are
+// written to g.v as well (the tile the level's residual and the original are taken from).
+__global__ __launch_bounds__(RB) void gather_axis0_kernel(GatherArgs g, float* tmp, const double* wgt, int r, int t) {
+  extern __shared__ float lds[];                         // (CH + 2r) rows of CW columns
+  const int tx = threadIdx.x % CW, ty = threadIdx.x / CW;
+  const int x = blockIdx.x * CW + tx, y0 = blockIdx.y * CH;
+  const size_t base = (size_t)blockIdx.z * t * t;
+  const int rows = min(CH, t - y0);
+  const bool col_ok = x < t;
+  const Gathered src(g, blockIdx.z);
+  for (int rr = ty; rr < rows + 2 * r; rr += RB / CW) {
+    float val = 0.f;
+    if (col_ok) {
+      const int y = fold(y0 - r + rr, t);
+      val = src.at(y, x);
+      if (rr >= r && rr < r + rows) g.v[base + (size_t)y * t + x] = val;      // y = y0 + rr - r: each pixel once
+    }
+    lds[rr * CW + tx] = val;
+  }
+  __syncthreads();
+  if (!col_ok) return;
+  for (int oy = ty; oy < rows; oy += RB / CW) {
+    const float* p = lds + oy * CW + tx;
+    double acc = 0.0;
+    for (int k = 0; k <= 2 * r; ++k) acc = fma(wgt[k], (double)p[k * CW], acc);
+    tmp[base + (size_t)(y0 + oy) * t + x] = (float)acc;
+  }
+}
+
+// n_scale = 1: the gathered tile itself, (n, 1 + inc, t, t) planes (with include_original the tile twice)
+__global__ __launch_bounds__(RB) void gather_planes_kernel(GatherArgs g, float* out, int t, int inc, unsigned total) {
+  const unsigned i = blockIdx.x * RB + threadIdx.x;
+  if (i >= total) return;
+  const unsigned hw = (unsigned)t * (unsigned)t, n = i / hw, yx = i % hw;
+  const Gathered src(g, n);
+  const float val = src.at(yx / t, yx % t);
+  for (int ch = 0; ch <= inc; ++ch) out[((size_t)n * (1 + inc) + ch) * hw + yx] = val;
+}
+
+// minimum of a tile as bp_gather_tiles sums and scales it, NaN if the tile holds one (np.min): one workgroup per
+// tile, lanes -> waves (DPP shuffles) -> LDS, combined in wave order.  min is exact, so any order gives the same bits.
+__global__ __launch_bounds__(RB) void tile_min_kernel(const TileDesc* d100, const TileDesc* d150, const SampleXform* xf,
+                                                      int t, float* minima) {
+  __shared__ float sm[RB / 64];
+  __shared__ int sn[RB / 64];
+  const int n = blockIdx.x;
+  const TileDesc a = d100[n], b = d150[n];
+  const SampleXform x = xf[n];
+  float m = INFINITY;
+  int nan = 0;
+  for (int i = threadIdx.x; i < t * t; i += RB) {
+    const float s = tile_scale(tile_sum(a, b, i / t, i % t), x);
+    nan |= s != s;
+    m = fminf(m, s);                                     // (skips a NaN: `nan` remembers it)
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    m = fminf(m, __shfl_xor(m, off));
+    nan |= __shfl_xor(nan, off);
+  }
+  if (threadIdx.x % 64 == 0) { sm[threadIdx.x / 64] = m; sn[threadIdx.x / 64] = nan; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < RB / 64; ++w) { m = fminf(m, sm[w]); nan |= sn[w]; }
+    minima[n] = nan ? __builtin_nanf("") : m;
+  }
+}
+
 struct RowArgs {
   const float* tmp;     // the axis-0 result
   const float* dsrc;    // the residual this level was filtered from
@@ -96,27 +195,34 @@ struct RowArgs {
   Dst d0, d1;
 };
 
-__device__ __forceinline__ void put(const Dst& d, size_t pixel, int ch, float v) {
-  if (d.p) d.p[pixel * d.cs + d.co + ch] = v;
+// PL = false: channel ch of pixel `pixel` of an NHWC view; PL = true: plane ch of (n, d.cs, h, w) NCHW planes
+template <bool PL>
+__device__ __forceinline__ void put(const Dst& d, size_t pixel, size_t hw, int ch, float v) {
+  if (!d.p) return;
+  if (PL) d.p[(pixel / hw * d.cs + d.co + ch) * hw + pixel % hw] = v;
+  else d.p[pixel * d.cs + d.co + ch] = v;
 }
 
 // what the last launch writes besides its own g: the residual, the original and the aux planes of a pixel
+template <bool PL>
 __device__ __forceinline__ void put_tail(const RowArgs& a, size_t pixel, int n, float res) {
-  put(a.d0, pixel, a.ch_res, res);
-  put(a.d1, pixel, a.ch_res, res);
+  const size_t hw = (size_t)a.h * a.w;
+  put<PL>(a.d0, pixel, hw, a.ch_res, res);
+  put<PL>(a.d1, pixel, hw, a.ch_res, res);
   if (a.ch_orig >= 0) {
     const float o = a.orig[pixel];
-    put(a.d0, pixel, a.ch_orig, o);
-    put(a.d1, pixel, a.ch_orig, o);
+    put<PL>(a.d0, pixel, hw, a.ch_orig, o);
+    put<PL>(a.d1, pixel, hw, a.ch_orig, o);
   }
   for (int c = 0; c < a.caux; ++c) {
     const float v = a.aux[(size_t)n * a.caux + c];
-    put(a.d0, pixel, a.ch_aux + c, v);
-    put(a.d1, pixel, a.ch_aux + c, v);
+    put<PL>(a.d0, pixel, hw, a.ch_aux + c, v);
+    put<PL>(a.d1, pixel, hw, a.ch_aux + c, v);
   }
 }
 
 // axis 1: g = (float) sum_k wgt[k + r] * tmp[row][fold(x + k)]; residual = dsrc - g (float32)
+template <bool PL>
 __global__ __launch_bounds__(RB) void filter_axis1_kernel(RowArgs a) {
   extern __shared__ float lds[];                         // RROWS rows of w + 2r floats
   const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
@@ -136,9 +242,9 @@ __global__ __launch_bounds__(RB) void filter_axis1_kernel(RowArgs a) {
     const float g = (float)acc;
     const size_t pixel = (size_t)row * a.w + x;
     const float res = a.dsrc[pixel] - g;
-    put(a.d0, pixel, a.ch_g, g);
-    put(a.d1, pixel, a.ch_g, g);
-    if (a.ch_res >= 0) put_tail(a, pixel, n, res);
+    put<PL>(a.d0, pixel, (size_t)a.h * a.w, a.ch_g, g);
+    put<PL>(a.d1, pixel, (size_t)a.h * a.w, a.ch_g, g);
+    if (a.ch_res >= 0) put_tail<PL>(a, pixel, n, res);
     else a.dres[pixel] = res;
   }
 }
@@ -147,7 +253,7 @@ __global__ __launch_bounds__(RB) void filter_axis1_kernel(RowArgs a) {
 __global__ __launch_bounds__(RB) void emit_kernel(RowArgs a, unsigned total) {
   const unsigned i = blockIdx.x * RB + threadIdx.x;
   if (i >= total) return;
-  put_tail(a, i, (int)(i / ((unsigned)a.h * (unsigned)a.w)), a.dsrc[i]);
+  put_tail<false>(a, i, (int)(i / ((unsigned)a.h * (unsigned)a.w)), a.dsrc[i]);
 }
 
 __device__ __forceinline__ float softplus_f(float x) { return x > 20.f ? x : log1pf(expf(x)); }
@@ -194,9 +300,11 @@ int check_levels(int32_t n, int32_t h, int32_t w, int32_t n_scale, const double*
 }
 
 // x (n, h, w) float32 planar -> pyramid channels [0, levels) of d0 (and d1), aux planes behind them.  `tmp` and `d`
-// are planes of n * h * w floats.
+// are planes of n * h * w floats.  With `ga` (square tiles, n_scale > 1) x is ga->v, which the first axis-0 pass gathers
+// and writes itself, and d0 / d1 are NCHW planes.
 int pyramid(const float* x, int32_t n, int32_t h, int32_t w, int32_t n_scale, int inc, const double* weights,
-            const int32_t* radii, float* tmp, float* d, const float* aux, int caux, Dst d0, Dst d1, hipStream_t sm) {
+            const int32_t* radii, float* tmp, float* d, const float* aux, int caux, Dst d0, Dst d1, hipStream_t sm,
+            const GatherArgs* ga = nullptr) {
   RowArgs a{};
   a.h = h; a.w = w; a.rows_total = n * h; a.caux = caux; a.aux = aux;
   a.d0 = d0; a.d1 = d1;
@@ -215,16 +323,20 @@ int pyramid(const float* x, int32_t n, int32_t h, int32_t w, int32_t n_scale, in
     const int r = radii[i];
     const double* wg = weights + woff[i];
     const dim3 g0((w + CW - 1) / CW, (h + CH - 1) / CH, n);
-    hipLaunchKernelGGL(filter_axis0_kernel, g0, dim3(RB), (size_t)(CH + 2 * r) * CW * sizeof(float), sm, cur, tmp, wg, r,
-                       (int)h, (int)w);
+    if (ga && cur == x)
+      hipLaunchKernelGGL(gather_axis0_kernel, g0, dim3(RB), (size_t)(CH + 2 * r) * CW * sizeof(float), sm, *ga, tmp, wg,
+                         r, (int)h);
+    else
+      hipLaunchKernelGGL(filter_axis0_kernel, g0, dim3(RB), (size_t)(CH + 2 * r) * CW * sizeof(float), sm, cur, tmp, wg,
+                         r, (int)h, (int)w);
     a.tmp = tmp; a.dsrc = cur; a.wgt = wg; a.r = r; a.ch_g = inc + i;
     const bool last = i == 1;
     a.dres = last ? nullptr : d;
     a.ch_res = last ? inc : -1;
     a.ch_orig = last && inc ? 0 : -1;
     a.orig = x;
-    hipLaunchKernelGGL(filter_axis1_kernel, dim3((n * h + RROWS - 1) / RROWS), dim3(RB),
-                       (size_t)(w + 2 * r) * RROWS * sizeof(float), sm, a);
+    hipLaunchKernelGGL(ga ? filter_axis1_kernel<true> : filter_axis1_kernel<false>, dim3((n * h + RROWS - 1) / RROWS),
+                       dim3(RB), (size_t)(w + 2 * r) * RROWS * sizeof(float), sm, a);
     BP_CHECK_LAUNCH();
     cur = d;
   }
@@ -279,6 +391,44 @@ int bp_paint_load_scales2(const float* raw_nchw, const double* sigma_k, const fl
   BP_CHECK_LAUNCH();
   return pyramid(v, n, h, w, n_scale, inc, weights, radii, s, s + plane, aux, caux,
                  Dst{out->ptr, out->cstride, out->coff}, Dst{out2->ptr, out2->cstride, out2->coff}, sm);
+}
+
+size_t bp_gather_tiles_scales_workspace(int32_t n, int32_t tile, int32_t n_scale) {
+  return n_scale > 1 ? bp_split_scale_workspace(n, tile, tile) : 0;
+}
+
+int bp_tile_minima(const void* desc100, const void* desc150, const void* xform, int32_t n, int32_t tile, float* minima,
+                   void* stream) {
+  if (!desc100 || !desc150 || !xform || n <= 0 || tile <= 0 || !minima) return BP_EINVAL;
+  if ((int64_t)tile * tile >= (int64_t)1 << 31) return BP_EUNSUPPORTED;
+  hipLaunchKernelGGL(tile_min_kernel, dim3(n), dim3(RB), 0, bp_stream(stream), static_cast<const TileDesc*>(desc100),
+                     static_cast<const TileDesc*>(desc150), static_cast<const SampleXform*>(xform), (int)tile, minima);
+  BP_CHECK_LAUNCH();
+  return BP_OK;
+}
+
+int bp_gather_tiles_scales(const void* desc100, const void* desc150, const void* xform, const float* minima, int32_t n,
+                           int32_t tile, int32_t n_scale, int32_t include_original, const double* weights,
+                           const int32_t* radii, void* scratch, size_t scratch_bytes, float* out_nchw, void* stream) {
+  const int inc = include_original ? 1 : 0;
+  if (!desc100 || !desc150 || !xform || !out_nchw) return BP_EINVAL;
+  const int rc = check_levels(n, tile, tile, n_scale, weights, radii, n_scale + inc);
+  if (rc != BP_OK) return rc;
+  if (n_scale > 1 && (!scratch || scratch_bytes < bp_gather_tiles_scales_workspace(n, tile, n_scale)))
+    return BP_EWORKSPACE;
+  const hipStream_t sm = bp_stream(stream);
+  const size_t plane = (size_t)n * tile * tile;
+  float* s = static_cast<float*>(scratch);
+  const GatherArgs ga{static_cast<const TileDesc*>(desc100), static_cast<const TileDesc*>(desc150),
+                      static_cast<const SampleXform*>(xform), minima, n_scale > 1 ? s + 2 * plane : nullptr};
+  if (n_scale == 1) {
+    hipLaunchKernelGGL(gather_planes_kernel, dim3(nblocks((int64_t)plane)), dim3(RB), 0, sm, ga, out_nchw, (int)tile, inc,
+                       (unsigned)plane);
+    BP_CHECK_LAUNCH();
+    return BP_OK;
+  }
+  return pyramid(ga.v, n, tile, tile, n_scale, inc, weights, radii, s, s + plane, nullptr, 0,
+                 Dst{out_nchw, n_scale + inc, 0}, Dst{nullptr, 0, 0}, sm, &ga);
 }
 
 int bp_paint_store_scales(const bp_view* src, const bp_pointwise* pw, int32_t softplus, int32_t include_original,

@@ -74,9 +74,12 @@ class CVAEPainter(Painter):
             return _DeviceLoader(self.device_assembler, len(self.training_data), batch_size)
         return torch.utils.data.DataLoader(self.training_data, batch_size=batch_size, shuffle=True)
 
-    def use_device_assembly(self, k_values, mode="shift-log"):
-        """Keep the training stacks in HBM and assemble batches with one gather launch per field
-        (utils.datasets.DeviceTileAssembler) instead of the host DataLoader; same shuffle order."""
+    def use_device_assembly(self, k_values=None, mode="shift-log"):
+        """Keep the training stacks in HBM and assemble batches on the device (utils.datasets.DeviceTileAssembler)
+        instead of the host DataLoader; same shuffle order.  Without arguments the transform is read from the training
+        set's chain: shift-log, optionally followed by a split-scale transform (NotImplementedError for any other
+        chain, before a stack is uploaded); ``subtract_minimum`` sets are served too.  ``k_values`` / ``mode`` given
+        explicitly mean a single-scale shift-log (or, with ``mode=None``, untransformed) batch, as before."""
         self.device_assembler = datasets.DeviceTileAssembler(self.training_data, self.compute_device,
                                                              k_values=k_values, mode=mode)
 
@@ -329,58 +332,26 @@ class CVAEPainter(Painter):
           multi scale    forward  [shift-log, as_float32 (optional), split-scale, shape-only steps ...]
                          inverse  [inverse split-scale, inverse shift-log, shape-only steps ...]
                          with the same split-scale parameters on both sides -- exactly these orders: the kernels
-                         filter the transformed tile and sum in front of the inverse transform."""
+                         filter the transformed tile and sum in front of the inverse transform.
+        (The chains are read by ``data_transforms.device_shift_log`` / ``device_split_scale``, which the training-side
+        ``datasets.DeviceTileAssembler`` shares.)"""
         from .utils import data_transforms as T
 
-        def shape_only(st):          # (by name: a transform chain restored from a checkpoint holds re-imported functions)
-            return getattr(st, "__module__", None) == T.__name__ and \
-                getattr(st, "__name__", None) in ("atleast_3d", "squeeze", "as_float32")
-
-        def steps_of(compiled):
+        def func_of(compiled):
             if compiled is None:
                 raise NotImplementedError("paint_stream needs the painter's transforms (transform=None has no device form)")
-            func = getattr(compiled, "func", None)
-            return getattr(func, "steps", None) or [func]
-
-        def range_compress(st, compiled, direction, field):
-            if st.modes[field].lower() != "shift-log":
-                raise NotImplementedError("device-side transforms implement the 'shift-log' mode only")
-            return (float(st.k_values[field]), compiled.stats[field])
+            return getattr(compiled, "func", None)
 
         def find(compiled, direction, field):
-            found = None
-            for st in steps_of(compiled):
-                if isinstance(st, T._RangeCompress) and st.direction == direction and found is None:
-                    found = range_compress(st, compiled, direction, field)
-                elif not shape_only(st):
-                    # a custom scaling step in the chain would be silently dropped on the device path
-                    raise NotImplementedError(f"transform step {st!r} has no device form")
-            if found is None:
-                raise NotImplementedError("paint_stream(transform=True) needs the painter's shift-log range compression")
-            return found
+            return T.device_shift_log(func_of(compiled), direction, field), compiled.stats[field]
 
         def find_scales(compiled, direction, field):
             """The strict multi-scale orders; returns (range compression, split-scale step)."""
-            steps = list(steps_of(compiled))
-            if direction == 0:
-                head = [lambda st: isinstance(st, T._RangeCompress) and st.direction == 0]
-                if len(steps) > 1 and getattr(steps[1], "__name__", None) == "as_float32" and shape_only(steps[1]):
-                    head.append(shape_only)
-                head.append(lambda st: isinstance(st, T._SplitScale) and st.direction == 0)
-            else:
-                head = [lambda st: isinstance(st, T._SplitScale) and st.direction == 1,
-                        lambda st: isinstance(st, T._RangeCompress) and st.direction == 1]
-            if len(steps) < len(head) or not all(ok(st) for ok, st in zip(head, steps)) or \
-                    not all(shape_only(st) for st in steps[len(head):]):
-                raise NotImplementedError(
-                    "a split-scale chain has a device form only as [shift-log, as_float32 (optional), split-scale, "
-                    "shape-only steps] / [inverse split-scale, inverse shift-log, shape-only steps]; got "
-                    f"{[getattr(st, '__name__', type(st).__name__) for st in steps]}")
-            rc = next(st for st in steps if isinstance(st, T._RangeCompress))
-            return range_compress(rc, compiled, direction, field), next(st for st in steps if isinstance(st, T._SplitScale))
+            k, split = T.device_split_scale(func_of(compiled), direction, field)
+            return (k, compiled.stats[field]), split
 
         def has_split(compiled):
-            return compiled is not None and any(isinstance(st, T._SplitScale) for st in steps_of(compiled))
+            return compiled is not None and T.has_split_scale(getattr(compiled, "func", None))
         if len(self.label_fields) != 1:
             raise NotImplementedError("Painting with more than one output field is not supported yet.")
         scales = None

@@ -176,3 +176,73 @@ def as_float32(x, field, z, stats):
     """Keep tiles float32: under NumPy >= 2 promotion ``float32_array / np.float64_scalar`` yields
     float64, whereas the NumPy 1.x the reference was written for kept float32."""
     return np.asarray(x, dtype=np.float32)
+
+
+# ---- which chains have a device form (painter.CVAEPainter.paint_stream, datasets.DeviceTileAssembler) --------------
+def chain_steps(func):
+    """The steps of a transform function: those of a chain, or the function itself."""
+    return getattr(func, "steps", None) or [func]
+
+
+def is_shape_only(st):
+    """atleast_3d / squeeze / as_float32 (by name: a chain restored from a checkpoint holds re-imported functions)."""
+    return getattr(st, "__module__", None) == __name__ and \
+        getattr(st, "__name__", None) in ("atleast_3d", "squeeze", "as_float32")
+
+
+def has_split_scale(func):
+    return func is not None and any(isinstance(st, _SplitScale) for st in chain_steps(func))
+
+
+def _shift_log_k(st, field):
+    if st.modes[field].lower() != "shift-log":
+        raise NotImplementedError("device-side transforms implement the 'shift-log' mode only")
+    return float(st.k_values[field])
+
+
+def device_shift_log(func, direction, field):
+    """k of the ONE shift-log range compression of a single-scale chain whose other steps are shape-only, in any
+    order; NotImplementedError for every other chain."""
+    found = None
+    for st in chain_steps(func):
+        if isinstance(st, _RangeCompress) and st.direction == direction and found is None:
+            found = _shift_log_k(st, field)
+        elif not is_shape_only(st):
+            # a custom scaling step in the chain would be silently dropped on the device path
+            raise NotImplementedError(f"transform step {st!r} has no device form")
+    if found is None:
+        raise NotImplementedError("the device path needs the chain's shift-log range compression")
+    return found
+
+
+def device_split_scale(func, direction, field):
+    """(k, split-scale step) of a multi-scale chain in the strict orders the kernels implement,
+         forward  [shift-log, as_float32 (optional), split-scale, shape-only steps ...]
+         inverse  [inverse split-scale, inverse shift-log, shape-only steps ...]
+    -- exactly these: the kernels filter the transformed tile and sum in front of the inverse transform."""
+    steps = list(chain_steps(func))
+    if direction == 0:
+        head = [lambda st: isinstance(st, _RangeCompress) and st.direction == 0]
+        if len(steps) > 1 and getattr(steps[1], "__name__", None) == "as_float32" and is_shape_only(steps[1]):
+            head.append(is_shape_only)
+        head.append(lambda st: isinstance(st, _SplitScale) and st.direction == 0)
+    else:
+        head = [lambda st: isinstance(st, _SplitScale) and st.direction == 1,
+                lambda st: isinstance(st, _RangeCompress) and st.direction == 1]
+    if len(steps) < len(head) or not all(ok(st) for ok, st in zip(head, steps)) or \
+            not all(is_shape_only(st) for st in steps[len(head):]):
+        raise NotImplementedError(
+            "a split-scale chain has a device form only as [shift-log, as_float32 (optional), split-scale, "
+            "shape-only steps] / [inverse split-scale, inverse shift-log, shape-only steps]; got "
+            f"{[getattr(st, '__name__', type(st).__name__) for st in steps]}")
+    rc = next(st for st in steps if isinstance(st, _RangeCompress))
+    return _shift_log_k(rc, field), next(st for st in steps if isinstance(st, _SplitScale))
+
+
+def split_scale_tables(n_scale, step_size, truncate):
+    """(radii, weights) as bp_split_scale reads them: radii[i] of level i (entry 0 unused), and the float64 weights of
+    level 1, 2, ... back to back."""
+    sig = split_scale_sigmas(n_scale, step_size)
+    radii = [0] + [gaussian_radius(s, truncate) for s in sig[1:]]
+    weights = np.concatenate([np.zeros(0)] + [gaussian_weights(s, truncate) for s in sig[1:]])
+    return radii, np.ascontiguousarray(weights, np.float64)

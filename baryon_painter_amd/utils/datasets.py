@@ -14,6 +14,7 @@ which define "bit-exact tile indexing":
 """
 import collections
 import copy
+import ctypes as C
 import os
 
 import numpy as np
@@ -290,8 +291,16 @@ class DeviceTileAssembler:
     288 GB) and every batch is one gather launch per field that reads the two tiles of each sample,
     applies the tile permutation, adds them, scales and transforms them -- bit-for-bit the index
     arithmetic of ``BAHAMASDataset.get_stack`` (computed on the host, integers only), so 8 GPUs are not
-    starved by a serial ``DataLoader(num_workers=0)`` (painter.py:88).  Supported transform: the
-    reference's "shift-log" range compression (plus identity)."""
+    starved by a serial ``DataLoader(num_workers=0)`` (painter.py:88).
+
+    The transform comes from the dataset's chain (``dataset.transform_func``), read by the functions the paint path
+    uses (``data_transforms.device_shift_log`` / ``device_split_scale``): the identity, ONE "shift-log" range compression
+    among shape-only steps, or ``[shift-log, as_float32 (optional), split-scale, shape-only steps ...]``, for which
+    every field of a sample comes out as its ``levels`` pyramid planes (``bp_gather_tiles_scales``: the gather runs
+    inside the first filter pass).  Any other chain raises NotImplementedError in the constructor, before a stack is
+    uploaded.  ``subtract_minimum`` datasets are served by a per-tile minimum on the device (``bp_tile_minima``),
+    subtracted in float32 in front of the transform, bit-equal to the host's ``d - d.min()``.  ``k_values`` (with
+    ``mode="shift-log"``) or ``mode=None`` given explicitly mean a single-scale batch without reading the chain."""
 
     REC100 = np.dtype([("base", np.int64), ("pitch", np.int32), ("r0", np.int32), ("rr", np.int32),
                        ("rc", np.int32), ("c0", np.int32), ("cr", np.int32), ("cc", np.int32), ("pad", np.int32)])
@@ -306,15 +315,44 @@ class DeviceTileAssembler:
         self.lib = L.load()
         if mode not in ("shift-log", None):
             raise NotImplementedError("DeviceTileAssembler implements the 'shift-log' transform only")
+        self.scales = None
+        if k_values is None and mode == "shift-log":
+            mode, k_values, self.scales = self._read_chain(dataset, T)
         self.mode = mode
         self.k_values = k_values or {}
         self._interp = T.interpolate_z
+        self._scratch = None                             # the pyramid's planes, grown to the largest batch
+        if self.scales is not None:                      # the pyramid's tables go up once per assembler
+            sc = self.scales
+            radii, weights = T.split_scale_tables(sc["n_scale"], sc["step_size"], sc["truncate"])
+            sc["radii"] = (C.c_int32 * len(radii))(*radii)
+            sc["weights"] = torch.from_numpy(weights).to(self.device) if sc["n_scale"] > 1 else None
         self.stacks = {}
         for f in dataset.fields:
             for z in dataset.redshifts:
                 for slab in ("100", "150"):
                     a = np.ascontiguousarray(dataset.data[f][z][slab], dtype=np.float32)
                     self.stacks[(f, z, slab)] = torch.from_numpy(a).to(self.device)
+
+    @staticmethod
+    def _read_chain(dataset, T):
+        """(mode, k_values, scales) of ``dataset.transform_func``; NotImplementedError for a chain without a device
+        form."""
+        func, fields = dataset.transform_func, [dataset.input_field] + list(dataset.label_fields)
+        if func is _identity or func is None:
+            return None, {}, None
+        if T.has_split_scale(func):
+            found = [T.device_split_scale(func, 0, f) for f in fields]
+            split = found[0][1]
+            scales = {"n_scale": split.n_scale, "step_size": split.step_size,
+                      "include_original": bool(split.include_original), "truncate": split.truncate}
+            return "shift-log", {f: k for f, (k, _) in zip(fields, found)}, scales
+        return "shift-log", {f: T.device_shift_log(func, 0, f) for f in fields}, None
+
+    @property
+    def levels(self):
+        """Channels per field of a batch."""
+        return 1 if self.scales is None else self.scales["n_scale"] + int(self.scales["include_original"])
 
     def _perm_affine(self, p):
         """(r0, rr, rc, c0, cr, cc) of ``apply_tile_permutation`` for code p, from the images of three
@@ -352,20 +390,35 @@ class DeviceTileAssembler:
         return d100, d150, xf
 
     def get_batch(self, indices):
-        """-> (x = label field(s) (N,F,t,t), y = input field (N,1,t,t), aux = redshift (N,)) on the device."""
-        import ctypes as C
+        """-> (x = label field(s) (N,F*levels,t,t), y = input field (N,levels,t,t), aux = redshift (N,)) on the device;
+        levels = 1 for a single-scale dataset."""
         torch, L, ds, t = self.torch, self.L, self.ds, self.ds.tile_size
-        if ds.subtract_minimum:
-            raise NotImplementedError("subtract_minimum on the device path")
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        n, levels = len(indices), self.levels
+        sc = self.scales or {"n_scale": 1, "include_original": False, "weights": None, "radii": None}
         outs, keep = [], []
         for field in [ds.input_field] + ds.label_fields:
             d100, d150, xf = self._descriptors(field, indices)
             dev = [torch.from_numpy(a.view(np.uint8)).to(self.device) for a in (d100, d150, xf)]
             keep.append(dev)
-            out = torch.empty((len(indices), 1, t, t), device=self.device)
-            L.check(self.lib.bp_gather_tiles(L.ptr(dev[0]), L.ptr(dev[1]), L.ptr(dev[2]), len(indices), t,
-                                             L.ptr(out), st), "gather tiles")
+            out = torch.empty((n, levels, t, t), device=self.device)
+            minima = None
+            if ds.subtract_minimum and field == ds.input_field:      # datasets.py:398-403: the input field only
+                minima = torch.empty(n, device=self.device)
+                keep.append(minima)
+                L.check(self.lib.bp_tile_minima(L.ptr(dev[0]), L.ptr(dev[1]), L.ptr(dev[2]), n, t, L.ptr(minima), st),
+                        "tile minima")
+            if self.scales is None and minima is None:
+                L.check(self.lib.bp_gather_tiles(L.ptr(dev[0]), L.ptr(dev[1]), L.ptr(dev[2]), n, t, L.ptr(out), st),
+                        "gather tiles")
+            else:
+                ws = int(self.lib.bp_gather_tiles_scales_workspace(n, t, sc["n_scale"]))
+                if ws and (self._scratch is None or self._scratch.numel() < ws):
+                    self._scratch = torch.empty(ws, dtype=torch.uint8, device=self.device)
+                L.check(self.lib.bp_gather_tiles_scales(
+                    L.ptr(dev[0]), L.ptr(dev[1]), L.ptr(dev[2]), L.ptr(minima), n, t, sc["n_scale"],
+                    int(sc["include_original"]), L.ptr(sc["weights"]), sc["radii"], L.ptr(self._scratch if ws else None),
+                    ws, L.ptr(out), st), "gather tiles into scales")
             outs.append(out)
         torch.cuda.current_stream().synchronize()        # descriptors may be freed after this
         z = torch.tensor([ds.sample_idx_to_redshift(int(i)) for i in indices], device=self.device,

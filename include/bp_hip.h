@@ -496,6 +496,27 @@ int bp_tanh_l1_backward(const bp_view* fake, const float* x_nchw, const bp_view*
  * out: (n,1,tile,tile) float32 = transform(scale * (tile100 + tile150)). */
 int bp_gather_tiles(const void* desc100, const void* desc150, const void* xform, int32_t n,
                     int32_t tile, float* out_nchw, void* stream);
+/* Training sets built with subtract_minimum (datasets.py:398-403, the SLICS_density convention) and / or a
+ * split-scale transform, from the same descriptors:
+ *   bp_tile_minima        : minima[i] (device, n float32) = min over the tile of the float32 value scale * (tile100 +
+ *                           tile150) that bp_gather_tiles forms in front of its transform; NaN if the tile holds a NaN
+ *                           (np.min).  One workgroup per tile: lanes, waves, LDS.  min is exact: bit-equal to the host.
+ *   bp_gather_tiles_scales: out (n, levels, tile, tile) float32 NCHW planes, levels = n_scale + include_original, in
+ *                           bp_split_scale's channel order = the pyramid of the float32 tile
+ *                           transform(scale * (tile100 + tile150) [- minima[i]]) (`minima` may be NULL: nothing is
+ *                           subtracted; the subtraction is a float32 one, `d -= d.min()`).  The tile is the value
+ *                           bp_gather_tiles stores and the pyramid is bp_split_scale's, bit for bit; weights, radii as
+ *                           for bp_split_scale; n_scale = 1 stores the tile itself (twice with include_original) and
+ *                           needs no scratch.  The gather runs inside the axis-0 pass of the coarsest level: the
+ *                           stacks are read once.  scratch: bp_gather_tiles_scales_workspace(n, tile, n_scale) bytes.
+ * bp_split_scale's limits (r <= 96, <= 16 scales, n <= 65535) and error order: BP_EINVAL / BP_EUNSUPPORTED /
+ * BP_EWORKSPACE are returned before anything is written.  No atomics, no host synchronisation. */
+int bp_tile_minima(const void* desc100, const void* desc150, const void* xform, int32_t n, int32_t tile,
+                   float* minima, void* stream);
+size_t bp_gather_tiles_scales_workspace(int32_t n, int32_t tile, int32_t n_scale);
+int bp_gather_tiles_scales(const void* desc100, const void* desc150, const void* xform, const float* minima,
+                           int32_t n, int32_t tile, int32_t n_scale, int32_t include_original, const double* weights,
+                           const int32_t* radii, void* scratch, size_t scratch_bytes, float* out_nchw, void* stream);
 
 /* ---- optimiser (replaces torch.optim.Adam.step, painter.py:93,228; same arithmetic) --------- */
 int bp_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
