@@ -134,6 +134,9 @@ SIGNATURES = {
     "bp_plane_blend": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P,
                                  C.c_int32, C.c_double, _P, _P, _P, C.c_int32, C.c_int32, _P]),
     "bp_plane_finish": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
+    "bp_plane_project_order_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "bp_plane_project_order": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_double, C.c_int32, _P, C.c_size_t, _P, C.c_int32,
+                                         _P]),
     "bp_plane_project_workspace": (C.c_size_t, [C.c_int32, C.c_int32]),
     "bp_plane_project": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_double, _P, C.c_size_t, _P, C.c_int32, _P]),
     "bp_latent_forward": (C.c_int, [C.POINTER(Latent), _VP, _PWP, _VP, _PWP, _P, _P, _VP, _P, _P,

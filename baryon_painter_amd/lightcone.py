@@ -157,7 +157,8 @@ def _paint_plane_device(painter, delta, tile_relative_size, n_pixel_tile, z, min
 # From painted planes to one Compton-y map (process_SLICS.py:12-66), and the light cone end to end.
 
 _SLAB = 252.5                                     # comoving thickness of a SLICS slab in Mpc/h (process_SLICS.py:26, 29)
-_projection_buffers = {}                          # per device: the float64 scratch of bp_plane_project
+_projection_buffers = {}                          # per device: the float64 scratch of bp_plane_project_order
+_DEVICE_ORDERS = (2, 3, 4, 5)                     # spline orders csrc/ymap.hip has (0 and 1 have no prefilter: host only)
 
 
 def release_projection_buffers():
@@ -176,16 +177,17 @@ def _project_host(y_map, d, scale, order):
     y_map += scipy.ndimage.zoom(d, zoom=zoom_factor, order=order, mode="mirror")
 
 
-def _project_device(plane, scale, y_map):
-    """y_map += zoom(nan_to_zero(plane) * scale) on the device (csrc/ymap.hip), on the current stream of the plane's
-    device, without a host synchronisation: ``plane`` a contiguous square CUDA float64 tensor (left as it is),
-    ``y_map`` a contiguous CUDA float64 (res, res) tensor."""
+def _project_device(plane, scale, y_map, order=3):
+    """y_map += zoom(nan_to_zero(plane) * scale, order) on the device (csrc/ymap.hip), on the current stream of the
+    plane's device, without a host synchronisation: ``plane`` a contiguous square CUDA float64 tensor (left as it is),
+    ``y_map`` a contiguous CUDA float64 (res, res) tensor, ``order`` in 2 ... 5.  The scratch kept per device is
+    measured against what THIS order asks for at every call, so a change of order can only grow it."""
     import ctypes as C
     import torch
     from . import _lib as L
     lib = L.load()
     n, res = plane.shape[0], y_map.shape[0]
-    ws = int(lib.bp_plane_project_workspace(n, res))
+    ws = int(lib.bp_plane_project_order_workspace(n, res, order))
     key = str(plane.device)
     scratch = _projection_buffers.get(key)
     if scratch is None or scratch.numel() * 8 < ws:
@@ -193,8 +195,9 @@ def _project_device(plane, scale, y_map):
         scratch = _projection_buffers[key] = torch.empty(max(ws // 8, 1), dtype=torch.float64, device=plane.device)
     with torch.cuda.device(plane.device):
         sm = C.c_void_p(torch.cuda.current_stream(plane.device).cuda_stream)
-        L.check(lib.bp_plane_project(L.ptr(plane), plane.shape[0], plane.shape[1], float(scale), L.ptr(scratch),
-                                     scratch.numel() * 8, L.ptr(y_map), res, sm), "plane project")
+        L.check(lib.bp_plane_project_order(L.ptr(plane), plane.shape[0], plane.shape[1], float(scale), int(order),
+                                           L.ptr(scratch), scratch.numel() * 8, L.ptr(y_map), res, sm),
+                "plane project")
 
 
 def _check_map(out, resolution, device=None):
@@ -212,9 +215,9 @@ def project_planes(planes, scales, resolution, order=3, on_device=False, out=Non
     (the loop of ``create_y_map``, process_SLICS.py:55-64).  ``scales[i]`` is the whole per-plane factor: the reference's
     division by ``zoom_factor**2`` is part of it (``y_map_scales`` computes it).  The planes are not modified.
 
-    ``on_device=True`` (order 3 only; NotImplementedError otherwise, before anything is launched): planes may be NumPy
+    ``on_device=True`` (orders 2 to 5; NotImplementedError otherwise, before anything is launched): planes may be NumPy
     arrays (uploaded as float64) or square CUDA float64 tensors (used in place), and each is projected by
-    ``bp_plane_project`` (csrc/ymap.hip) in float64, within 1e-12 of the largest pixel of SciPy's result.  The map is
+    ``bp_plane_project_order`` (csrc/ymap.hip) in float64, within 1e-12 of the largest pixel of SciPy's result.  The map is
     downloaded once, or, with ``out`` (a CUDA float64 (resolution, resolution) tensor), ACCUMULATED into ``out``, which
     is returned.  The scratch is kept between calls (``release_projection_buffers``)."""
     if not on_device:
@@ -224,8 +227,8 @@ def project_planes(planes, scales, resolution, order=3, on_device=False, out=Non
         for d, s in zip(planes, scales):
             _project_host(y_map, d, s, order)
         return y_map
-    if order != 3:
-        raise NotImplementedError("project_planes(on_device=True) resamples with cubic splines (order=3) only")
+    if order not in _DEVICE_ORDERS:
+        raise NotImplementedError("project_planes(on_device=True) resamples with splines of order 2 to 5 only")
     import torch
     if out is not None:
         _check_map(out, resolution)
@@ -249,7 +252,7 @@ def project_planes(planes, scales, resolution, order=3, on_device=False, out=Non
             if y_map is None:
                 dev = p.device
                 y_map = torch.zeros((resolution, resolution), dtype=torch.float64, device=dev)
-            _project_device(p, s, y_map)
+            _project_device(p, s, y_map, order)
         if out is not None:
             return out
         if y_map is None:                                        # no planes
@@ -370,9 +373,9 @@ def paint_light_cone(painter, planes, z, delta_size, tile_size, n_pixel_tile, re
     scripts/create_lightcone.py:43-54); the key and the counters below are the CVAE's latent noise and do not affect a
     CGAN's planes.
 
-    ``on_device=True`` (order 3 and a painter with a device pipeline at every redshift; NotImplementedError otherwise,
-    before any random number is drawn): ``paint_plane(on_device=True, out=...)`` leaves each plane in a device buffer
-    that ``bp_plane_project`` reads on the same stream and the next plane reuses; only the finished map is downloaded,
+    ``on_device=True`` (orders 2 to 5 and a painter with a device pipeline at every redshift; NotImplementedError
+    otherwise, before any random number is drawn): ``paint_plane(on_device=True, out=...)`` leaves each plane in a
+    device buffer that ``bp_plane_project_order`` reads on the same stream and the next plane reuses; only the finished map is downloaded,
     or nothing with ``out`` (a CUDA float64 (resolution, resolution) tensor that is accumulated into and returned).
     Small planes are painted as on the host path and uploaded.
 
@@ -384,8 +387,8 @@ def paint_light_cone(painter, planes, z, delta_size, tile_size, n_pixel_tile, re
         raise ValueError("out= needs on_device=True")
     # eligibility is decided UP FRONT, as in paint_plane: no random number is drawn for a light cone that cannot run
     if on_device:
-        if order != 3:
-            raise NotImplementedError("paint_light_cone(on_device=True) resamples with cubic splines (order=3) only")
+        if order not in _DEVICE_ORDERS:
+            raise NotImplementedError("paint_light_cone(on_device=True) resamples with splines of order 2 to 5 only")
         if not (hasattr(painter, "_paint_plane_device") and all(painter.can_paint_stream(zi) for zi in z)):
             raise NotImplementedError("paint_light_cone(on_device=True) needs a painter with a device paint pipeline "
                                       "(CVAEPainter / CGANPainter .can_paint_stream) at every redshift")
@@ -434,7 +437,7 @@ def paint_light_cone(painter, planes, z, delta_size, tile_size, n_pixel_tile, re
                 host = plane
                 plane = torch.from_numpy(np.ascontiguousarray(plane)).to(dev)
         if on_device:
-            _project_device(plane, scales[i], y_map)
+            _project_device(plane, scales[i], y_map, order)
             if return_planes:
                 kept.append(plane.cpu().numpy() if delta_size[i] >= tile_size else host)
         else:

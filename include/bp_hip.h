@@ -414,16 +414,25 @@ int bp_plane_finish(const double* acc, const double* wsum, int64_t count, double
 /* ---- Compton-y map of a light cone (lightcone.project_planes(on_device=True), process_SLICS.py:55-64) -----------
  * A painted plane is resampled to the map's resolution and added into the y map on the device, right behind
  * bp_plane_finish on the same stream: only the finished map comes back.
- *   bp_plane_project: y (res, res) float64 += scipy.ndimage.zoom(where(isnan(P), 0, P) * scale, res / n, order=3,
- *                     mode="mirror") for the square float64 plane P (rows == cols == n), in float64: cubic B-spline
- *                     prefilter under whole-sample symmetric boundaries along axis 0 then axis 1 (parallel along the
- *                     line: pieces of 224 samples with 32-sample warm-ups on the mirrored extension, exact to double
- *                     precision; lines shorter than 32 samples take SciPy's closed-form initialisation), then
- *                     tensor-product sampling at i (n - 1) / (res - 1) with mirrored taps, one thread per pixel of y.
- *                     P is not modified.  No atomics: the same inputs give the same bits.  Needs
- *                     bp_plane_project_workspace(n, res) bytes of `scratch` (two float64 images of the plane);
- *                     BP_EWORKSPACE if it is shorter, BP_EINVAL for rows != cols, n < 2 or res < 2, and nothing is
- *                     written in either case.  No host synchronisation. */
+ *   bp_plane_project_order: y (res, res) float64 += scipy.ndimage.zoom(where(isnan(P), 0, P) * scale, res / n,
+ *                     order=order, mode="mirror") for the square float64 plane P (rows == cols == n) and order 2 ... 5,
+ *                     in float64: SciPy's B-spline prefilter (its poles and gain; two poles, one after the other, at
+ *                     orders 4 and 5) under whole-sample symmetric boundaries along axis 0 then axis 1 (parallel along
+ *                     the line: pieces of 224 samples with warm-ups on the mirrored extension that leave <= 1e-18 of
+ *                     their start, 32 samples at orders 2 and 3, 64 + 32 at orders 4 and 5, exact to double precision;
+ *                     lines shorter than 32 samples take SciPy's closed-form initialisation), then tensor-product
+ *                     sampling at i (n - 1) / (res - 1) with order + 1 mirrored taps per axis, one thread per pixel of
+ *                     y.  P is not modified.  No atomics: the same inputs give the same bits.  Needs
+ *                     bp_plane_project_order_workspace(n, res, order) bytes of `scratch` (two float64 images of the
+ *                     plane; 0 for n < 2, res < 2 or an order outside 2 ... 5).  In this order, and with nothing
+ *                     launched or written: BP_EINVAL for a null pointer, rows != cols, n < 2 or res < 2;
+ *                     BP_EUNSUPPORTED for an order outside 2 ... 5 (orders 0 and 1 have no prefilter and stay on the
+ *                     host) and for n * n or res * res >= 2^31; BP_EWORKSPACE for a scratch that is too short.  No
+ *                     host synchronisation.
+ *   bp_plane_project, bp_plane_project_workspace: the same at order 3. */
+size_t bp_plane_project_order_workspace(int32_t n, int32_t res, int32_t order);
+int bp_plane_project_order(const double* plane, int32_t rows, int32_t cols, double scale, int32_t order,
+                           double* scratch, size_t scratch_bytes, double* y, int32_t res, void* stream);
 size_t bp_plane_project_workspace(int32_t n, int32_t res);
 int bp_plane_project(const double* plane, int32_t rows, int32_t cols, double scale, double* scratch,
                      size_t scratch_bytes, double* y, int32_t res, void* stream);

@@ -2,7 +2,8 @@
 against the device path (on_device=True: painted planes stay on the GPU and csrc/ymap.hip projects them), and the
 projection alone.  Fiducial 512^2 architecture with synthetic weights (as tools/plane_bench.py builds it).  The light
 cone: ``--planes`` (3) periodic delta planes of ``--delta``^2 (4096) float32 pixels, painted as ``--delta``^2 planes of
-512^2 tiles at 0.5 overlap, into a ``--res``^2 (4096) map.  One JSON line:
+512^2 tiles at 0.5 overlap, into a ``--res``^2 (4096) map, resampled with splines of ``--order`` (3; 2 to 5, the orders
+the device path has) on both paths.  One JSON line:
 
   projection_host_s            the painted planes downloaded from the device and projected by project_planes (SciPy, one
                                core), one run; ``_download_s`` is the download's share
@@ -17,7 +18,8 @@ cone: ``--planes`` (3) periodic delta planes of ``--delta``^2 (4096) float32 pix
   host_link_bytes              bytes over the host link per light cone, from the sizes: host path the float32 tiles up
                                and down; device path the deltas up and the map down
 
-Usage: python tools/ymap_bench.py [--dtype f32] [--planes 3] [--delta 4096] [--res 4096] [--reps 5] [--batch 64]"""
+Usage: python tools/ymap_bench.py [--dtype f32] [--planes 3] [--delta 4096] [--res 4096] [--reps 5] [--batch 64]
+       [--order 3]"""
 import argparse
 import json
 import os
@@ -44,6 +46,7 @@ def main():
     ap.add_argument("--res", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--order", type=int, default=3, choices=(2, 3, 4, 5))
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("ymap_bench needs a GPU")
@@ -60,7 +63,8 @@ def main():
     for i in range(k):
         rng = np.random.Generator(np.random.PCG64(100 + i))
         deltas.append((np.exp(rng.standard_normal((n, n), dtype=np.float32) * 0.5) * 0.05).astype(np.float32))
-    kw = dict(tile_size=tile_size, n_pixel_tile=TILE, resolution=res, scales=scales, batch_size=args.batch, seed=11)
+    kw = dict(tile_size=tile_size, n_pixel_tile=TILE, resolution=res, scales=scales, batch_size=args.batch, seed=11,
+              order=args.order)
 
     # ---- whole light cone, both paths
     LC.paint_light_cone(pt, deltas, z, delta_size, on_device=True, **kw)                   # capture + warm-up
@@ -81,13 +85,13 @@ def main():
                        first_tile_id=i * n_tiles, on_device=True, out=out)
         planes.append(out)
     y = torch.zeros((res, res), dtype=torch.float64, device="cuda")
-    LC.project_planes(planes, scales, res, on_device=True, out=y)                          # warm-up (scratch allocated)
+    LC.project_planes(planes, scales, res, order=args.order, on_device=True, out=y)       # warm-up (scratch allocated)
     times = []
     for _ in range(args.reps):
         y.zero_()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        LC.project_planes(planes, scales, res, on_device=True, out=y)
+        LC.project_planes(planes, scales, res, order=args.order, on_device=True, out=y)
         e1.record()
         e1.synchronize()
         times.append(e0.elapsed_time(e1) * 1e-3)
@@ -96,7 +100,7 @@ def main():
     t0 = time.perf_counter()
     host_planes = [p.cpu().numpy() for p in planes]
     t_down = time.perf_counter() - t0
-    y_ref = LC.project_planes(host_planes, scales, res)
+    y_ref = LC.project_planes(host_planes, scales, res, order=args.order)
     t_proj_host = time.perf_counter() - t0
     proj_diff = float(np.abs(y.cpu().numpy() - y_ref).max() / np.abs(y_ref).max())
 
@@ -105,7 +109,7 @@ def main():
     tile_bytes = TILE * TILE * 4
     print(json.dumps({
         "metric": "ymap_light_cone", "dtype": args.dtype, "planes": k, "delta": [n, n], "n_plane": n_plane,
-        "tiles_per_plane": n_tiles, "resolution": res, "batch": args.batch,
+        "tiles_per_plane": n_tiles, "resolution": res, "batch": args.batch, "order": args.order,
         "projection_host_s": round(t_proj_host, 4), "projection_host_download_s": round(t_down, 4),
         "projection_device_s": {"median": round(t_proj_dev, 6), "min": round(min(times), 6),
                                 "max": round(max(times), 6), "reps": args.reps},
