@@ -17,6 +17,8 @@ IMPL_DEFER = 0x200
 PACK_FWD, PACK_BWD = 0, 1
 F32, BF16 = 0, 1
 F64 = 2            # bp_plane_cut's float64 planes
+# range-compression modes of the `_mode` entry points (utils.data_transforms.MODE_IDS maps the mode names to these)
+RC_SHIFT_LOG, RC_LOG, RC_SHIFT_LOG_2P, RC_LOG_TANH, RC_X_1PX, RC_INV_X = range(6)
 
 
 class View(C.Structure):
@@ -118,6 +120,9 @@ SIGNATURES = {
     "bp_paint_load": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _VP, _P]),
     "bp_paint_load2": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _VP, _VP, _P]),
     "bp_paint_store": (C.c_int, [_VP, _PWP, C.c_int32, _P, _P, _P]),
+    "bp_paint_load_mode": (C.c_int, [C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, _VP, _P]),
+    "bp_paint_load2_mode": (C.c_int, [C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, _VP, _VP, _P]),
+    "bp_paint_store_mode": (C.c_int, [C.c_int32, _VP, _PWP, C.c_int32, _P, _P, _P]),
     "bp_paint_load_cam": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _VP, _P]),
     "bp_paint_store_cam": (C.c_int, [_VP, _P, _P, _P]),
     "bp_split_scale_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
@@ -126,6 +131,9 @@ SIGNATURES = {
     "bp_paint_load_scales2": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_size_t, _VP, _VP,
                                         _P]),
     "bp_paint_store_scales": (C.c_int, [_VP, _PWP, C.c_int32, C.c_int32, _P, _P, _P]),
+    "bp_paint_load_scales2_mode": (C.c_int, [C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,
+                                             C.c_size_t, _VP, _VP, _P]),
+    "bp_paint_store_scales_mode": (C.c_int, [C.c_int32, _VP, _PWP, C.c_int32, C.c_int32, _P, _P, _P]),
     "bp_philox_normal": (C.c_int, [C.c_uint64, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "bp_philox_normal_dev": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "bp_plane_cut_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
@@ -155,6 +163,8 @@ SIGNATURES = {
     "bp_gather_tiles_scales_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "bp_gather_tiles_scales": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,
                                          C.c_size_t, _P, _P]),
+    "bp_gather_tiles_scales_mode": (C.c_int, [C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                              _P, _P, _P, C.c_size_t, _P, _P]),
     "bp_adam_step": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
                                C.c_int32, _P]),
     "bp_adam_step_dev": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, _P]),

@@ -5,6 +5,9 @@
 //                     (merge_aux_label, utils.py:159-182): the fused form of the host transform + bp_nchw_to_view
 //   bp_paint_store    head view -> [softplus] -> inverse shift-log (data_transforms.py:97) -> NCHW tile: the fused
 //                     form of bp_view_to_nchw + the host inverse transform
+//   bp_paint_load_mode / bp_paint_load2_mode / bp_paint_store_mode   the same with any of the six range-compression modes
+//                     (range_compress.hpp) and records of four float64 per tile; the three above are these at mode
+//                     shift-log, reading their two-double tables
 //   bp_paint_load_cam / bp_paint_store_cam   the same pair for the conditional GAN: its "shift-log-cam" transform into the
 //                     tanh range, log(x / sigma + 1) / k0 - k1 (painter.CGANPainter.transform), and the generator's tanh
 //                     head followed by the inverse, both evaluated in double as the host's NumPy expressions are
@@ -14,6 +17,7 @@
 // double where NumPy promotes to double), so device and host transforms agree to the last float32 bit except for
 // libm differences of exp (<= 1 ulp of the exponential).
 #include "common.hpp"
+#include "range_compress.hpp"
 #include <math.h>
 
 namespace {
@@ -22,7 +26,8 @@ constexpr int RB = 256;
 
 // (out2: an optional second destination of the same pixels -- the generator reads the transformed tile in its
 //  concatenated input as well as the prior network: the double-precision logarithm is taken once, not once per view)
-__global__ __launch_bounds__(RB) void paint_load_kernel(const float* src, int c, const double* sigma_k, const float* aux,
+template <int M>
+__global__ __launch_bounds__(RB) void paint_load_kernel(const float* src, int c, RcTable xf, const float* aux,
                                                         int caux, float* out, int out_cs, int out_co, float* out2,
                                                         int out2_cs, int out2_co, int64_t hw, int64_t total) {
   const int64_t i = (int64_t)blockIdx.x * RB + threadIdx.x;
@@ -36,9 +41,8 @@ __global__ __launch_bounds__(RB) void paint_load_kernel(const float* src, int c,
   const int64_t p = pu, n = nu, yx = pu - nu * hwu;
   float v;
   if (ch < c) {
-    // np.log(x / std + 1) / k  with float32 x and float64 std: evaluated in double, stored as float32
-    const double x = (double)src[(n * c + ch) * hw + yx];
-    v = (float)(log(x / sigma_k[2 * n] + 1.0) / sigma_k[2 * n + 1]);
+    // e.g. np.log(x / std + 1) / k  with float32 x and float64 std: evaluated in double, stored as float32
+    v = rc_forward<M>(rc_record(xf, n), src[(n * c + ch) * hw + yx]);
   } else {
     v = aux[n * caux + (ch - c)];
   }
@@ -48,8 +52,9 @@ __global__ __launch_bounds__(RB) void paint_load_kernel(const float* src, int c,
 
 __device__ __forceinline__ float softplus_f(float x) { return x > 20.f ? x : log1pf(expf(x)); }
 
+template <int M>
 __global__ __launch_bounds__(RB) void paint_store_kernel(const float* src, int src_cs, int src_co, int c, PW pw,
-                                                         int softplus, const double* k_sigma, float* dst, int64_t hw,
+                                                         int softplus, RcTable xf, float* dst, int64_t hw,
                                                          int64_t total) {
   const int64_t i = (int64_t)blockIdx.x * RB + threadIdx.x;     // NCHW destination index (coalesced writes)
   if (i >= total) return;
@@ -61,11 +66,8 @@ __global__ __launch_bounds__(RB) void paint_store_kernel(const float* src, int s
   const int64_t n = nu;
   float v = pw_apply(pw, ch, src[(n * hw + yx) * src_cs + src_co + ch]);
   if (softplus) v = softplus_f(v);
-  // (np.exp(x * k) - 1) * std: float32 product, float32 exp, float32 subtraction, double product
-  const float t = v * (float)k_sigma[2 * n];
-  const float e = (float)exp((double)t);            // correctly rounded float32 exponential
-  const float r = e - 1.0f;
-  dst[i] = (float)((double)r * k_sigma[2 * n + 1]);
+  // e.g. (np.exp(x * k) - 1) * std: float32 product, float32 exp, float32 subtraction, double product
+  dst[i] = rc_inverse<M>(rc_record(xf, n), v);
 }
 
 // The CGAN's pair.  Same thread-to-element maps as the two kernels above (NHWC order on the way in, NCHW order on the
@@ -156,40 +158,75 @@ static inline unsigned nblocks(int64_t total) { return (unsigned)((total + RB - 
 
 extern "C" {
 
-int bp_paint_load(const float* raw_nchw, int32_t c, const double* sigma_k, const float* aux, int32_t caux,
-                  const bp_view* out, void* stream) {
-  if (!raw_nchw || !sigma_k || !bp_view_ok(out) || c <= 0 || caux < 0 || out->c != c + caux || (caux > 0 && !aux))
+// out2 == nullptr: one destination
+static int paint_load_any(int32_t mode, const float* raw_nchw, int32_t c, RcTable xf, const float* aux, int32_t caux,
+                          const bp_view* out, const bp_view* out2, void* stream) {
+  if (mode < 0 || mode >= RC_MODES) return BP_EINVAL;
+  if (!raw_nchw || !xf.p || !bp_view_ok_any(out) || (out2 && !bp_view_ok_any(out2)) || c <= 0 || caux < 0 ||
+      out->c != c + caux || (caux > 0 && !aux))
     return BP_EINVAL;
+  if (out2 && (out2->c != out->c || out2->n != out->n || out2->h != out->h || out2->w != out->w)) return BP_EINVAL;
+  if (out->dtype != BP_F32 || (out2 && out2->dtype != BP_F32)) return BP_EUNSUPPORTED;
   const int64_t hw = (int64_t)out->h * out->w, total = (int64_t)out->n * hw * (c + caux);
   if (total >= (int64_t)1 << 31) return BP_EUNSUPPORTED;
-  hipLaunchKernelGGL(paint_load_kernel, dim3(nblocks(total)), dim3(RB), 0, bp_stream(stream), raw_nchw, c, sigma_k, aux,
-                     caux, out->ptr, out->cstride, out->coff, (float*)nullptr, 0, 0, hw, total);
+  rc_dispatch(mode, [&](auto m) {
+    paint_load_kernel<decltype(m)::value><<<dim3(nblocks(total)), dim3(RB), 0, bp_stream(stream)>>>(
+        raw_nchw, c, xf, aux, caux, out->ptr, out->cstride, out->coff, out2 ? out2->ptr : (float*)nullptr,
+        out2 ? out2->cstride : 0, out2 ? out2->coff : 0, hw, total);
+  });
   BP_CHECK_LAUNCH();
   return BP_OK;
+}
+
+static int paint_store_any(int32_t mode, const bp_view* src, const bp_pointwise* pw, int32_t softplus, RcTable xf,
+                           float* dst_nchw, void* stream) {
+  if (mode < 0 || mode >= RC_MODES) return BP_EINVAL;
+  if (!bp_view_ok_any(src) || !xf.p || !dst_nchw) return BP_EINVAL;
+  if (src->dtype != BP_F32) return BP_EUNSUPPORTED;
+  const int64_t hw = (int64_t)src->h * src->w, total = (int64_t)src->n * hw * src->c;
+  if (total >= (int64_t)1 << 31) return BP_EUNSUPPORTED;
+  rc_dispatch(mode, [&](auto m) {
+    paint_store_kernel<decltype(m)::value><<<dim3(nblocks(total)), dim3(RB), 0, bp_stream(stream)>>>(
+        src->ptr, src->cstride, src->coff, src->c, bp_pw(pw), softplus, xf, dst_nchw, hw, total);
+  });
+  BP_CHECK_LAUNCH();
+  return BP_OK;
+}
+
+int bp_paint_load_mode(int32_t mode, const float* raw_nchw, int32_t c, const double* records, const float* aux,
+                       int32_t caux, const bp_view* out, void* stream) {
+  return paint_load_any(mode, raw_nchw, c, rc_table4(records), aux, caux, out, nullptr, stream);
+}
+
+int bp_paint_load2_mode(int32_t mode, const float* raw_nchw, int32_t c, const double* records, const float* aux,
+                        int32_t caux, const bp_view* out, const bp_view* out2, void* stream) {
+  if (!out2) return BP_EINVAL;
+  return paint_load_any(mode, raw_nchw, c, rc_table4(records), aux, caux, out, out2, stream);
+}
+
+int bp_paint_store_mode(int32_t mode, const bp_view* src, const bp_pointwise* pw, int32_t softplus, const double* records,
+                        float* dst_nchw, void* stream) {
+  return paint_store_any(mode, src, pw, softplus, rc_table4(records), dst_nchw, stream);
+}
+
+// The shift-log forms: the same kernels at RC_SHIFT_LOG over the tables of two doubles, {sigma, k} / {k, sigma}
+// (a bf16 view is BP_EINVAL here, as it has always been).
+int bp_paint_load(const float* raw_nchw, int32_t c, const double* sigma_k, const float* aux, int32_t caux,
+                  const bp_view* out, void* stream) {
+  if (!bp_view_ok(out)) return BP_EINVAL;
+  return paint_load_any(RC_SHIFT_LOG, raw_nchw, c, RcTable{sigma_k, 2, 0, 1}, aux, caux, out, nullptr, stream);
 }
 
 int bp_paint_load2(const float* raw_nchw, int32_t c, const double* sigma_k, const float* aux, int32_t caux,
                    const bp_view* out, const bp_view* out2, void* stream) {
-  if (!raw_nchw || !sigma_k || !bp_view_ok(out) || !bp_view_ok(out2) || c <= 0 || caux < 0 || out->c != c + caux ||
-      out2->c != out->c || out2->n != out->n || out2->h != out->h || out2->w != out->w || (caux > 0 && !aux))
-    return BP_EINVAL;
-  const int64_t hw = (int64_t)out->h * out->w, total = (int64_t)out->n * hw * (c + caux);
-  if (total >= (int64_t)1 << 31) return BP_EUNSUPPORTED;
-  hipLaunchKernelGGL(paint_load_kernel, dim3(nblocks(total)), dim3(RB), 0, bp_stream(stream), raw_nchw, c, sigma_k, aux,
-                     caux, out->ptr, out->cstride, out->coff, out2->ptr, out2->cstride, out2->coff, hw, total);
-  BP_CHECK_LAUNCH();
-  return BP_OK;
+  if (!bp_view_ok(out) || !bp_view_ok(out2)) return BP_EINVAL;
+  return paint_load_any(RC_SHIFT_LOG, raw_nchw, c, RcTable{sigma_k, 2, 0, 1}, aux, caux, out, out2, stream);
 }
 
 int bp_paint_store(const bp_view* src, const bp_pointwise* pw, int32_t softplus, const double* k_sigma, float* dst_nchw,
                    void* stream) {
-  if (!bp_view_ok(src) || !k_sigma || !dst_nchw) return BP_EINVAL;
-  const int64_t hw = (int64_t)src->h * src->w, total = (int64_t)src->n * hw * src->c;
-  if (total >= (int64_t)1 << 31) return BP_EUNSUPPORTED;
-  hipLaunchKernelGGL(paint_store_kernel, dim3(nblocks(total)), dim3(RB), 0, bp_stream(stream), src->ptr, src->cstride,
-                     src->coff, src->c, bp_pw(pw), softplus, k_sigma, dst_nchw, hw, total);
-  BP_CHECK_LAUNCH();
-  return BP_OK;
+  if (!bp_view_ok(src)) return BP_EINVAL;
+  return paint_store_any(RC_SHIFT_LOG, src, pw, softplus, RcTable{k_sigma, 2, 1, 0}, dst_nchw, stream);
 }
 
 // A bf16 view is a well-formed view these two have no form for (the CGAN has no bf16 mode): BP_EUNSUPPORTED.

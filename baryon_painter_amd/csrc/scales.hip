@@ -7,6 +7,8 @@
 //   bp_tile_minima         per-tile minimum of a gathered training tile (the datasets' subtract_minimum)
 //   bp_gather_tiles_scales bp_gather_tiles [minus the minima] with the pyramid behind the transform, stored as NCHW
 //                          planes: a training batch of a multi-scale model, assembled from the stacks in HBM
+//   bp_paint_load_scales2_mode / bp_paint_store_scales_mode / bp_gather_tiles_scales_mode   the same three with any of
+//                          the six range-compression modes (range_compress.hpp) and records of four float64 per tile
 // The pyramid: d = x; for i = n_scale-1 .. 1: g = gaussian_filter(d, sigma_i); scale i = g; d -= g; scale 0 = d; with
 // include_original a leading channel holds x.  What scipy.ndimage.gaussian_filter does on a float32 tile is the
 // contract, restated here:
@@ -32,6 +34,7 @@
 // transformed tile is written once, for the residual and the original, beside the axis-0 intermediate.
 #include "common.hpp"
 #include "assemble.hpp"
+#include "range_compress.hpp"
 #include <math.h>
 
 #pragma clang fp contract(off)
@@ -64,32 +67,39 @@ struct GatherArgs {
   const SampleXform* xf;
   const float* minima;  // nullptr: nothing is subtracted
   float* v;             // (n, t, t): the transformed tile
+  const double* rec;    // M >= 0: (n, 4) records of range_compress.hpp's mode M, applied in place of xf's transform
 };
 
+constexpr int XF_OWN = -1;      // the gather kernels' M: the transform the SampleXform itself names (bp_gather_tiles')
+
 // one sample's share of GatherArgs, wave-uniform
+template <int M>
 struct Gathered {
   TileDesc a, b;
   SampleXform x;
+  RcRec rc;
   float mn;
   bool sub;
   __device__ __forceinline__ Gathered(const GatherArgs& g, int n)
-      : a(g.d100[n]), b(g.d150[n]), x(g.xf[n]), mn(g.minima ? g.minima[n] : 0.f), sub(g.minima != nullptr) {}
+      : a(g.d100[n]), b(g.d150[n]), x(g.xf[n]), rc{}, mn(g.minima ? g.minima[n] : 0.f), sub(g.minima != nullptr) {
+    if constexpr (M >= 0) rc = rc_record(rc_table4(g.rec), n);
+  }
   // bp_gather_tiles' value with the float32 `d - d.min()` of datasets.py:402 in front of the transform
   __device__ __forceinline__ float at(int r, int c) const {
     float s = tile_scale(tile_sum(a, b, r, c), x);
     if (sub) s = s - mn;
-    return tile_transform(s, x);
+    if constexpr (M >= 0) return rc_forward<M>(rc, s);
+    else return tile_transform(s, x);
   }
 };
 
-// raw (n, 1, h, w) -> the float32 shift-log value of bp_paint_load: (float) (log((double) x / sigma + 1) / k)
-__global__ __launch_bounds__(RB) void shift_log_kernel(const float* raw, const double* sigma_k, unsigned hw, unsigned total,
+// raw (n, 1, h, w) -> the float32 transformed value of bp_paint_load, e.g. (float) (log((double) x / sigma + 1) / k)
+template <int M>
+__global__ __launch_bounds__(RB) void transform_kernel(const float* raw, RcTable xf, unsigned hw, unsigned total,
                                                        float* v) {
   const unsigned i = blockIdx.x * RB + threadIdx.x;
   if (i >= total) return;
-  const unsigned n = i / hw;
-  const double x = (double)raw[i];
-  v[i] = (float)(log(x / sigma_k[2 * n] + 1.0) / sigma_k[2 * n + 1]);
+  v[i] = rc_forward<M>(rc_record(xf, i / hw), raw[i]);
 }
 
 // axis 0: tmp[t][y][x] = (float) sum_k wgt[k + r] * src[t][fold(y + k)][x]
@@ -115,6 +125,7 @@ __global__ __launch_bounds__(RB) void filter_axis0_kernel(const float* src, floa
 
 // The same pass with the gather in front: the strip is staged from the stacks, and the rows a workgroup owns are
 // written to g.v as well (the tile the level's residual and the original are taken from).
+template <int M>
 __global__ __launch_bounds__(RB) void gather_axis0_kernel(GatherArgs g, float* tmp, const double* wgt, int r, int t) {
   extern __shared__ float lds[];                         // (CH + 2r) rows of CW columns
   const int tx = threadIdx.x % CW, ty = threadIdx.x / CW;
@@ -122,7 +133,7 @@ __global__ __launch_bounds__(RB) void gather_axis0_kernel(GatherArgs g, float* t
   const size_t base = (size_t)blockIdx.z * t * t;
   const int rows = min(CH, t - y0);
   const bool col_ok = x < t;
-  const Gathered src(g, blockIdx.z);
+  const Gathered<M> src(g, blockIdx.z);
   for (int rr = ty; rr < rows + 2 * r; rr += RB / CW) {
     float val = 0.f;
     if (col_ok) {
@@ -143,11 +154,12 @@ __global__ __launch_bounds__(RB) void gather_axis0_kernel(GatherArgs g, float* t
 }
 
 // n_scale = 1: the gathered tile itself, (n, 1 + inc, t, t) planes (with include_original the tile twice)
+template <int M>
 __global__ __launch_bounds__(RB) void gather_planes_kernel(GatherArgs g, float* out, int t, int inc, unsigned total) {
   const unsigned i = blockIdx.x * RB + threadIdx.x;
   if (i >= total) return;
   const unsigned hw = (unsigned)t * (unsigned)t, n = i / hw, yx = i % hw;
-  const Gathered src(g, n);
+  const Gathered<M> src(g, n);
   const float val = src.at(yx / t, yx % t);
   for (int ch = 0; ch <= inc; ++ch) out[((size_t)n * (1 + inc) + ch) * hw + yx] = val;
 }
@@ -258,10 +270,10 @@ __global__ __launch_bounds__(RB) void emit_kernel(RowArgs a, unsigned total) {
 
 __device__ __forceinline__ float softplus_f(float x) { return x > 20.f ? x : log1pf(expf(x)); }
 
+template <int M>
 __global__ __launch_bounds__(RB) void paint_store_scales_kernel(const float* src, int src_cs, int src_co, int c, PW pw,
-                                                                int softplus, int include_original,
-                                                                const double* k_sigma, float* dst, unsigned hw,
-                                                                unsigned total) {
+                                                                int softplus, int include_original, RcTable xf,
+                                                                float* dst, unsigned hw, unsigned total) {
   const unsigned i = blockIdx.x * RB + threadIdx.x;      // (n, 1, H, W) destination index
   if (i >= total) return;
   const unsigned n = i / hw;
@@ -273,12 +285,9 @@ __global__ __launch_bounds__(RB) void paint_store_scales_kernel(const float* src
     if (softplus) t = softplus_f(t);
     v = ch == 0 ? t : v + t;                             // ((c0 + c1) + c2) ...: NumPy's order for sum(axis=0)
   }
-  // bp_paint_store's expression, (np.exp(x * k) - 1) * std: float32 product, float32 exp, float32 subtraction,
+  // bp_paint_store's expression, e.g. (np.exp(x * k) - 1) * std: float32 product, float32 exp, float32 subtraction,
   // double product
-  const float t = v * (float)k_sigma[2 * n];
-  const float e = (float)exp((double)t);
-  const float r = e - 1.0f;
-  dst[i] = (float)((double)r * k_sigma[2 * n + 1]);
+  dst[i] = rc_inverse<M>(rc_record(xf, n), v);
 }
 
 static inline unsigned nblocks(int64_t total) { return (unsigned)((total + RB - 1) / RB); }
@@ -299,12 +308,19 @@ int check_levels(int32_t n, int32_t h, int32_t w, int32_t n_scale, const double*
   return BP_OK;
 }
 
+// f(std::integral_constant<int, M>) for the gather kernels' M: XF_OWN or a range-compression mode
+template <class F>
+inline bool gather_dispatch(int gmode, F&& f) {
+  if (gmode == XF_OWN) { f(std::integral_constant<int, XF_OWN>{}); return true; }
+  return rc_dispatch(gmode, f);
+}
+
 // x (n, h, w) float32 planar -> pyramid channels [0, levels) of d0 (and d1), aux planes behind them.  `tmp` and `d`
 // are planes of n * h * w floats.  With `ga` (square tiles, n_scale > 1) x is ga->v, which the first axis-0 pass gathers
 // and writes itself, and d0 / d1 are NCHW planes.
 int pyramid(const float* x, int32_t n, int32_t h, int32_t w, int32_t n_scale, int inc, const double* weights,
             const int32_t* radii, float* tmp, float* d, const float* aux, int caux, Dst d0, Dst d1, hipStream_t sm,
-            const GatherArgs* ga = nullptr) {
+            const GatherArgs* ga = nullptr, int gmode = XF_OWN) {
   RowArgs a{};
   a.h = h; a.w = w; a.rows_total = n * h; a.caux = caux; a.aux = aux;
   a.d0 = d0; a.d1 = d1;
@@ -324,8 +340,10 @@ int pyramid(const float* x, int32_t n, int32_t h, int32_t w, int32_t n_scale, in
     const double* wg = weights + woff[i];
     const dim3 g0((w + CW - 1) / CW, (h + CH - 1) / CH, n);
     if (ga && cur == x)
-      hipLaunchKernelGGL(gather_axis0_kernel, g0, dim3(RB), (size_t)(CH + 2 * r) * CW * sizeof(float), sm, *ga, tmp, wg,
-                         r, (int)h);
+      gather_dispatch(gmode, [&](auto m) {
+        gather_axis0_kernel<decltype(m)::value><<<g0, dim3(RB), (size_t)(CH + 2 * r) * CW * sizeof(float), sm>>>(
+            *ga, tmp, wg, r, (int)h);
+      });
     else
       hipLaunchKernelGGL(filter_axis0_kernel, g0, dim3(RB), (size_t)(CH + 2 * r) * CW * sizeof(float), sm, cur, tmp, wg,
                          r, (int)h, (int)w);
@@ -369,11 +387,13 @@ int bp_split_scale(const float* tiles, int32_t n, int32_t h, int32_t w, int32_t 
                  Dst{out->ptr, out->cstride, out->coff}, Dst{nullptr, 0, 0}, bp_stream(stream));
 }
 
-int bp_paint_load_scales2(const float* raw_nchw, const double* sigma_k, const float* aux, int32_t caux, int32_t n_scale,
-                          int32_t include_original, const double* weights, const int32_t* radii, void* scratch,
-                          size_t scratch_bytes, const bp_view* out, const bp_view* out2, void* stream) {
+static int paint_load_scales2_any(int32_t mode, const float* raw_nchw, RcTable xf, const float* aux, int32_t caux,
+                                  int32_t n_scale, int32_t include_original, const double* weights, const int32_t* radii,
+                                  void* scratch, size_t scratch_bytes, const bp_view* out, const bp_view* out2,
+                                  void* stream) {
   const int inc = include_original ? 1 : 0;
-  if (!raw_nchw || !sigma_k || !bp_view_ok_any(out) || !bp_view_ok_any(out2) || n_scale < 1 || caux < 0 ||
+  if (mode < 0 || mode >= RC_MODES) return BP_EINVAL;
+  if (!raw_nchw || !xf.p || !bp_view_ok_any(out) || !bp_view_ok_any(out2) || n_scale < 1 || caux < 0 ||
       out->c != n_scale + inc + caux || out2->c != out->c || out2->n != out->n || out2->h != out->h ||
       out2->w != out->w || (caux > 0 && !aux))
     return BP_EINVAL;
@@ -386,11 +406,28 @@ int bp_paint_load_scales2(const float* raw_nchw, const double* sigma_k, const fl
   const size_t plane = (size_t)n * h * w;
   float* v = s + 2 * plane;
   const hipStream_t sm = bp_stream(stream);
-  hipLaunchKernelGGL(shift_log_kernel, dim3(nblocks((int64_t)plane)), dim3(RB), 0, sm, raw_nchw, sigma_k,
-                     (unsigned)(h * w), (unsigned)plane, v);
+  rc_dispatch(mode, [&](auto m) {
+    transform_kernel<decltype(m)::value><<<dim3(nblocks((int64_t)plane)), dim3(RB), 0, sm>>>(
+        raw_nchw, xf, (unsigned)(h * w), (unsigned)plane, v);
+  });
   BP_CHECK_LAUNCH();
   return pyramid(v, n, h, w, n_scale, inc, weights, radii, s, s + plane, aux, caux,
                  Dst{out->ptr, out->cstride, out->coff}, Dst{out2->ptr, out2->cstride, out2->coff}, sm);
+}
+
+int bp_paint_load_scales2(const float* raw_nchw, const double* sigma_k, const float* aux, int32_t caux, int32_t n_scale,
+                          int32_t include_original, const double* weights, const int32_t* radii, void* scratch,
+                          size_t scratch_bytes, const bp_view* out, const bp_view* out2, void* stream) {
+  return paint_load_scales2_any(RC_SHIFT_LOG, raw_nchw, RcTable{sigma_k, 2, 0, 1}, aux, caux, n_scale, include_original,
+                                weights, radii, scratch, scratch_bytes, out, out2, stream);
+}
+
+int bp_paint_load_scales2_mode(int32_t mode, const float* raw_nchw, const double* records, const float* aux, int32_t caux,
+                               int32_t n_scale, int32_t include_original, const double* weights, const int32_t* radii,
+                               void* scratch, size_t scratch_bytes, const bp_view* out, const bp_view* out2,
+                               void* stream) {
+  return paint_load_scales2_any(mode, raw_nchw, rc_table4(records), aux, caux, n_scale, include_original, weights, radii,
+                                scratch, scratch_bytes, out, out2, stream);
 }
 
 size_t bp_gather_tiles_scales_workspace(int32_t n, int32_t tile, int32_t n_scale) {
@@ -407,9 +444,11 @@ int bp_tile_minima(const void* desc100, const void* desc150, const void* xform, 
   return BP_OK;
 }
 
-int bp_gather_tiles_scales(const void* desc100, const void* desc150, const void* xform, const float* minima, int32_t n,
-                           int32_t tile, int32_t n_scale, int32_t include_original, const double* weights,
-                           const int32_t* radii, void* scratch, size_t scratch_bytes, float* out_nchw, void* stream) {
+// gmode: XF_OWN (the transform xform names) or a range-compression mode over `records`
+static int gather_tiles_scales_any(int gmode, const double* records, const void* desc100, const void* desc150,
+                                   const void* xform, const float* minima, int32_t n, int32_t tile, int32_t n_scale,
+                                   int32_t include_original, const double* weights, const int32_t* radii, void* scratch,
+                                   size_t scratch_bytes, float* out_nchw, void* stream) {
   const int inc = include_original ? 1 : 0;
   if (!desc100 || !desc150 || !xform || !out_nchw) return BP_EINVAL;
   const int rc = check_levels(n, tile, tile, n_scale, weights, radii, n_scale + inc);
@@ -420,28 +459,60 @@ int bp_gather_tiles_scales(const void* desc100, const void* desc150, const void*
   const size_t plane = (size_t)n * tile * tile;
   float* s = static_cast<float*>(scratch);
   const GatherArgs ga{static_cast<const TileDesc*>(desc100), static_cast<const TileDesc*>(desc150),
-                      static_cast<const SampleXform*>(xform), minima, n_scale > 1 ? s + 2 * plane : nullptr};
+                      static_cast<const SampleXform*>(xform), minima, n_scale > 1 ? s + 2 * plane : nullptr, records};
   if (n_scale == 1) {
-    hipLaunchKernelGGL(gather_planes_kernel, dim3(nblocks((int64_t)plane)), dim3(RB), 0, sm, ga, out_nchw, (int)tile, inc,
-                       (unsigned)plane);
+    gather_dispatch(gmode, [&](auto m) {
+      gather_planes_kernel<decltype(m)::value><<<dim3(nblocks((int64_t)plane)), dim3(RB), 0, sm>>>(
+          ga, out_nchw, (int)tile, inc, (unsigned)plane);
+    });
     BP_CHECK_LAUNCH();
     return BP_OK;
   }
   return pyramid(ga.v, n, tile, tile, n_scale, inc, weights, radii, s, s + plane, nullptr, 0,
-                 Dst{out_nchw, n_scale + inc, 0}, Dst{nullptr, 0, 0}, sm, &ga);
+                 Dst{out_nchw, n_scale + inc, 0}, Dst{nullptr, 0, 0}, sm, &ga, gmode);
+}
+
+int bp_gather_tiles_scales(const void* desc100, const void* desc150, const void* xform, const float* minima, int32_t n,
+                           int32_t tile, int32_t n_scale, int32_t include_original, const double* weights,
+                           const int32_t* radii, void* scratch, size_t scratch_bytes, float* out_nchw, void* stream) {
+  return gather_tiles_scales_any(XF_OWN, nullptr, desc100, desc150, xform, minima, n, tile, n_scale, include_original,
+                                 weights, radii, scratch, scratch_bytes, out_nchw, stream);
+}
+
+int bp_gather_tiles_scales_mode(int32_t mode, const double* records, const void* desc100, const void* desc150,
+                                const void* xform, const float* minima, int32_t n, int32_t tile, int32_t n_scale,
+                                int32_t include_original, const double* weights, const int32_t* radii, void* scratch,
+                                size_t scratch_bytes, float* out_nchw, void* stream) {
+  if (mode < 0 || mode >= RC_MODES || !records) return BP_EINVAL;
+  return gather_tiles_scales_any(mode, records, desc100, desc150, xform, minima, n, tile, n_scale, include_original,
+                                 weights, radii, scratch, scratch_bytes, out_nchw, stream);
+}
+
+static int paint_store_scales_any(int32_t mode, const bp_view* src, const bp_pointwise* pw, int32_t softplus,
+                                  int32_t include_original, RcTable xf, float* dst_nchw, void* stream) {
+  if (mode < 0 || mode >= RC_MODES) return BP_EINVAL;
+  if (!bp_view_ok_any(src) || !xf.p || !dst_nchw || (include_original && src->c < 2)) return BP_EINVAL;
+  if (src->dtype != BP_F32) return BP_EUNSUPPORTED;
+  const int64_t hw = (int64_t)src->h * src->w, total = (int64_t)src->n * hw;
+  if (total * src->cstride >= (int64_t)1 << 31) return BP_EUNSUPPORTED;
+  rc_dispatch(mode, [&](auto m) {
+    paint_store_scales_kernel<decltype(m)::value><<<dim3(nblocks(total)), dim3(RB), 0, bp_stream(stream)>>>(
+        src->ptr, src->cstride, src->coff, src->c, bp_pw(pw), softplus ? 1 : 0, include_original ? 1 : 0, xf, dst_nchw,
+        (unsigned)hw, (unsigned)total);
+  });
+  BP_CHECK_LAUNCH();
+  return BP_OK;
 }
 
 int bp_paint_store_scales(const bp_view* src, const bp_pointwise* pw, int32_t softplus, int32_t include_original,
                           const double* k_sigma, float* dst_nchw, void* stream) {
-  if (!bp_view_ok_any(src) || !k_sigma || !dst_nchw || (include_original && src->c < 2)) return BP_EINVAL;
-  if (src->dtype != BP_F32) return BP_EUNSUPPORTED;
-  const int64_t hw = (int64_t)src->h * src->w, total = (int64_t)src->n * hw;
-  if (total * src->cstride >= (int64_t)1 << 31) return BP_EUNSUPPORTED;
-  hipLaunchKernelGGL(paint_store_scales_kernel, dim3(nblocks(total)), dim3(RB), 0, bp_stream(stream), src->ptr,
-                     src->cstride, src->coff, src->c, bp_pw(pw), softplus ? 1 : 0, include_original ? 1 : 0, k_sigma,
-                     dst_nchw, (unsigned)hw, (unsigned)total);
-  BP_CHECK_LAUNCH();
-  return BP_OK;
+  return paint_store_scales_any(RC_SHIFT_LOG, src, pw, softplus, include_original, RcTable{k_sigma, 2, 1, 0}, dst_nchw,
+                                stream);
+}
+
+int bp_paint_store_scales_mode(int32_t mode, const bp_view* src, const bp_pointwise* pw, int32_t softplus,
+                               int32_t include_original, const double* records, float* dst_nchw, void* stream) {
+  return paint_store_scales_any(mode, src, pw, softplus, include_original, rc_table4(records), dst_nchw, stream);
 }
 
 }  // extern "C"

@@ -11,6 +11,7 @@ There is no CPU implementation: constructing the model on a non-GPU device or wi
 built library raises.
 """
 import ctypes as C
+import functools
 import math
 import os
 
@@ -900,7 +901,7 @@ class CVAE(torch.nn.Module):
         g["graph"].replay()
         return g["out"].clone()
 
-    def paint_graph(self, n, scales=None):
+    def paint_graph(self, n, scales=None, modes=None):
         """The captured paint pipeline for batches of ``n`` RAW tiles (configs[4]).  Returns a dict with ``slots``: TWO
         input / parameter / output buffer sets, each with its own captured graph over the SAME launch plans, so that a
         caller uploads batch b+1 straight into one slot and downloads batch b-1 straight out of it while the other
@@ -918,7 +919,12 @@ class CVAE(torch.nn.Module):
         network, whose dim_y[0] = dim_x[0] = n_scale + include_original channels are the pyramid's levels.  ``raw`` and
         ``out`` are then (n, 1, H, W): the pyramid is built behind the transform (``bp_paint_load_scales2``) and undone
         in front of its inverse (``bp_paint_store_scales``); a slot also names the pipeline's ``scratch`` (one per
-        stream of the graph) and the float64 filter ``weights``, which the slots share.  Without it nothing changes."""
+        stream of the graph) and the float64 filter ``weights``, which the slots share.  Without it nothing changes.
+
+        ``modes`` (a painter whose fields are not both "shift-log"): the (input, label) range-compression mode numbers
+        (data_transforms.MODE_IDS).  The load and store nodes are then the ``_mode`` entry points, which hold the mode as
+        a constant of the graph, and ``xf_in`` / ``xf_out`` are (n, 4) float64: the records of
+        ``data_transforms.DeviceRangeCompress.records``.  Without it nothing changes."""
         if self.training:
             raise RuntimeError("paint_graph is an eval-mode (paint) path: call model.train(False) first")
         key = (n, "pipeline")
@@ -926,9 +932,12 @@ class CVAE(torch.nn.Module):
             scales = {"n_scale": int(scales["n_scale"]), "step_size": scales["step_size"],
                       "include_original": bool(scales["include_original"]), "truncate": scales.get("truncate", 3.0)}
             key = (n, "pipeline", "scales") + tuple(scales.values())
+        if modes is not None:
+            modes = (int(modes[0]), int(modes[1]))
+            key = key + ("modes",) + modes
         g = self._graphs.get(key)
         if g is None:
-            g = self._capture_paint_graph(n, pipeline=True, scales=scales)
+            g = self._capture_paint_graph(n, pipeline=True, scales=scales, modes=modes)
             self._graphs[key] = g
         for u in g["units"]:
             u.maybe_pack()
@@ -941,7 +950,7 @@ class CVAE(torch.nn.Module):
         for key in [k for k in self._graphs if isinstance(k, tuple) and len(k) > 2 and k[2] == "scales"]:
             del self._graphs[key]
 
-    def _capture_paint_graph(self, n, given_z=False, pipeline=False, scales=None):
+    def _capture_paint_graph(self, n, given_z=False, pipeline=False, scales=None, modes=None):
         """Eval-mode layers do not couple the tiles of a batch (batch-norm runs on its running statistics), so the
         batch is painted as BP_PAINT_STREAMS (default 4) sub-batches on as many streams inside one graph: kernels of different layers share
         the CUs and fill each other's stalls (the effect the training step gets from its weight-gradient
@@ -964,7 +973,8 @@ class CVAE(torch.nn.Module):
             st["eps"] = torch.zeros((1, n, per_tile), device=self.device)
             # parameter block of a slot: one contiguous device buffer = one host-to-device copy per batch
             layout, off = {}, 0
-            for name, dt, shape in (("xf_in", torch.float64, (n, 2)), ("xf_out", torch.float64, (n, 2)),
+            xw = 2 if modes is None else 4
+            for name, dt, shape in (("xf_in", torch.float64, (n, xw)), ("xf_out", torch.float64, (n, xw)),
                                     ("tile_ids", torch.int64, (n,)), ("seed", torch.int64, (1,)),
                                     ("aux", torch.float32, (n, max(self.n_aux, 1)))):
                 layout[name] = (off, dt, shape)
@@ -1018,19 +1028,22 @@ class CVAE(torch.nn.Module):
             plan.pack_all()
             auxp = L.ptr(sl["aux"][lo:lo + h]) if self.use_aux_label else None
             scratch = sc["scratch"][lo // h]
-            L.check(lib.bp_paint_load_scales2(L.ptr(sl["raw"][lo:lo + h]), L.ptr(sl["xf_in"][lo:lo + h]), auxp,
-                                              plan.caux, sc["n_scale"], sc["include_original"], L.ptr(sc["weights"]),
-                                              sc["radii"], L.ptr(scratch), sc["ws"], C.byref(plan.y2.view),
-                                              C.byref(plan.hy_slot.view), sm), "paint load (scales)")
+            load, store = (lib.bp_paint_load_scales2, lib.bp_paint_store_scales) if modes is None else \
+                (functools.partial(lib.bp_paint_load_scales2_mode, modes[0]),
+                 functools.partial(lib.bp_paint_store_scales_mode, modes[1]))
+            L.check(load(L.ptr(sl["raw"][lo:lo + h]), L.ptr(sl["xf_in"][lo:lo + h]), auxp,
+                         plan.caux, sc["n_scale"], sc["include_original"], L.ptr(sc["weights"]),
+                         sc["radii"], L.ptr(scratch), sc["ws"], C.byref(plan.y2.view),
+                         C.byref(plan.hy_slot.view), sm), "paint load (scales)")
             plan.run_prior(False)
             eps = st["eps"][:, lo:lo + h]
             L.check(lib.bp_philox_normal_dev(L.ptr(sl["seed"]), L.ptr(sl["tile_ids"][lo:lo + h]), h, 1, eps.shape[-1],
                                              L.ptr(eps), sm), "philox")
             plan.run_latent(eps.reshape(1, h, *self.dim_z), use_q=False)
             plan.run_generator(False)
-            L.check(lib.bp_paint_store_scales(C.byref(plan.mu_head.view), None, 1 if plan.mu_softplus else 0,
-                                              sc["include_original"], L.ptr(sl["xf_out"][lo:lo + h]),
-                                              L.ptr(sl["out"][lo:lo + h]), sm), "paint store (scales)")
+            L.check(store(C.byref(plan.mu_head.view), None, 1 if plan.mu_softplus else 0,
+                          sc["include_original"], L.ptr(sl["xf_out"][lo:lo + h]),
+                          L.ptr(sl["out"][lo:lo + h]), sm), "paint store (scales)")
 
         def paint_pipeline(plan, lo, sl):
             if scales is not None:
@@ -1038,16 +1051,18 @@ class CVAE(torch.nn.Module):
             lib, sm = self._lib, _stream()
             plan.pack_all()
             auxp = L.ptr(sl["aux"][lo:lo + h]) if self.use_aux_label else None
-            L.check(lib.bp_paint_load2(L.ptr(sl["raw"][lo:lo + h]), cy, L.ptr(sl["xf_in"][lo:lo + h]), auxp, plan.caux,
-                                       C.byref(plan.y2.view), C.byref(plan.hy_slot.view), sm), "paint load")
+            load, store = (lib.bp_paint_load2, lib.bp_paint_store) if modes is None else \
+                (functools.partial(lib.bp_paint_load2_mode, modes[0]), functools.partial(lib.bp_paint_store_mode, modes[1]))
+            L.check(load(L.ptr(sl["raw"][lo:lo + h]), cy, L.ptr(sl["xf_in"][lo:lo + h]), auxp, plan.caux,
+                         C.byref(plan.y2.view), C.byref(plan.hy_slot.view), sm), "paint load")
             plan.run_prior(False)
             eps = st["eps"][:, lo:lo + h]
             L.check(lib.bp_philox_normal_dev(L.ptr(sl["seed"]), L.ptr(sl["tile_ids"][lo:lo + h]), h, 1, eps.shape[-1],
                                              L.ptr(eps), sm), "philox")
             plan.run_latent(eps.reshape(1, h, *self.dim_z), use_q=False)
             plan.run_generator(False)
-            L.check(lib.bp_paint_store(C.byref(plan.mu_head.view), None, 1 if plan.mu_softplus else 0,
-                                       L.ptr(sl["xf_out"][lo:lo + h]), L.ptr(sl["out"][lo:lo + h]), sm), "paint store")
+            L.check(store(C.byref(plan.mu_head.view), None, 1 if plan.mu_softplus else 0,
+                          L.ptr(sl["xf_out"][lo:lo + h]), L.ptr(sl["out"][lo:lo + h]), sm), "paint store")
 
         def paint(plan, lo, sl):
             if pipeline:

@@ -77,8 +77,8 @@ class CVAEPainter(Painter):
     def use_device_assembly(self, k_values=None, mode="shift-log"):
         """Keep the training stacks in HBM and assemble batches on the device (utils.datasets.DeviceTileAssembler)
         instead of the host DataLoader; same shuffle order.  Without arguments the transform is read from the training
-        set's chain: shift-log, optionally followed by a split-scale transform (NotImplementedError for any other
-        chain, before a stack is uploaded); ``subtract_minimum`` sets are served too.  ``k_values`` / ``mode`` given
+        set's chain: a range compression (any of the six modes, one per field), optionally followed by a split-scale
+        transform (NotImplementedError for any other chain, before a stack is uploaded); ``subtract_minimum`` sets are served too.  ``k_values`` / ``mode`` given
         explicitly mean a single-scale shift-log (or, with ``mode=None``, untransformed) batch, as before."""
         self.device_assembler = datasets.DeviceTileAssembler(self.training_data, self.compute_device,
                                                              k_values=k_values, mode=mode)
@@ -323,14 +323,16 @@ class CVAEPainter(Painter):
         return np.concatenate(out, axis=0)
 
     # ---- throughput pipeline (BASELINE.json configs[4]) ---------------------------------------------------------
-    def _shift_log_parameters(self, zs):
-        """(sigma_in, k_in, k_out, sigma_out, scales) for the device-side transforms, read out of the compiled host
-        transforms: per tile the parameters of the reference's "shift-log" range compression
-        (data_transforms.py:72-97), and the description of a multi-scale painter's split-scale transform
-        (``CVAE.paint_graph``'s ``scales``) or None; anything else has no device form.  The chains with one:
-          single scale   any order of ONE shift-log range compression and the shape-only steps;
-          multi scale    forward  [shift-log, as_float32 (optional), split-scale, shape-only steps ...]
-                         inverse  [inverse split-scale, inverse shift-log, shape-only steps ...]
+    def _transform_parameters(self, zs):
+        """(params, scales, modes) for the device-side transforms, read out of the compiled host transforms: per tile
+        the parameter rows ``xf_in`` / ``xf_out`` of the reference's range compression (data_transforms.py:72-108) for
+        ``CVAE.paint_graph``'s block, the description of a multi-scale painter's split-scale transform (``paint_graph``'s
+        ``scales``) or None, and ``modes``: None where both fields are "shift-log" (rows {sigma, k} / {k, sigma}, the
+        pipeline as it always was), else the (input, label) mode numbers (rows: the four-double records of
+        csrc/range_compress.hpp).  Anything else has no device form.  The chains with one:
+          single scale   any order of ONE range compression and the shape-only steps;
+          multi scale    forward  [range compression, as_float32 (optional), split-scale, shape-only steps ...]
+                         inverse  [inverse split-scale, inverse range compression, shape-only steps ...]
                          with the same split-scale parameters on both sides -- exactly these orders: the kernels
                          filter the transformed tile and sum in front of the inverse transform.
         (The chains are read by ``data_transforms.device_shift_log`` / ``device_split_scale``, which the training-side
@@ -347,8 +349,8 @@ class CVAEPainter(Painter):
 
         def find_scales(compiled, direction, field):
             """The strict multi-scale orders; returns (range compression, split-scale step)."""
-            k, split = T.device_split_scale(func_of(compiled), direction, field)
-            return (k, compiled.stats[field]), split
+            rc, split = T.device_split_scale(func_of(compiled), direction, field)
+            return (rc, compiled.stats[field]), split
 
         def has_split(compiled):
             return compiled is not None and T.has_split_scale(getattr(compiled, "func", None))
@@ -356,30 +358,32 @@ class CVAEPainter(Painter):
             raise NotImplementedError("Painting with more than one output field is not supported yet.")
         scales = None
         if has_split(self.transform) or has_split(self.inverse_transform):
-            (k_in, st_in), fs = find_scales(self.transform, 0, self.input_field)
-            (k_out, st_out), bs = find_scales(self.inverse_transform, 1, self.label_fields[0])
+            (rc_in, st_in), fs = find_scales(self.transform, 0, self.input_field)
+            (rc_out, st_out), bs = find_scales(self.inverse_transform, 1, self.label_fields[0])
             if (fs.n_scale, fs.include_original) != (bs.n_scale, bs.include_original):
                 raise NotImplementedError("the split-scale transform and its inverse differ in n_scale / include_original")
             scales = {"n_scale": fs.n_scale, "step_size": fs.step_size, "include_original": fs.include_original,
                       "truncate": fs.truncate}
         else:
-            k_in, st_in = find(self.transform, 0, self.input_field)
-            k_out, st_out = find(self.inverse_transform, 1, self.label_fields[0])
-        s_in = np.sqrt(T.interpolate_z_many(st_in, zs, "var"))          # (vectorised: no Python call per tile)
-        s_out = np.sqrt(T.interpolate_z_many(st_out, zs, "var"))
-        return s_in, k_in, k_out, s_out, scales
+            rc_in, st_in = find(self.transform, 0, self.input_field)
+            rc_out, st_out = find(self.inverse_transform, 1, self.label_fields[0])
+        xf_in, xf_out = rc_in.records(st_in, zs), rc_out.records(st_out, zs)      # (vectorised: no Python call per tile)
+        modes = (rc_in.mode, rc_out.mode)
+        if rc_in.name == rc_out.name == "shift-log":
+            modes, xf_in, xf_out = None, xf_in[:, :2], xf_out[:, 1::-1]
+        return {"xf_in": xf_in, "xf_out": xf_out, "aux": np.asarray(zs, dtype=np.float64)}, scales, modes
 
     def can_paint_stream(self, z=0.0):
-        """Whether ``paint_stream`` has a device form for this painter (one label field, the 'shift-log' range compression
-        on both sides, L = 1 and a prior network; single-channel tiles, or a split-scale transform in the orders
-        ``_shift_log_parameters`` names whose levels are the model's dim_y[0] = dim_x[0]) -- WITHOUT side effects: nothing is
+        """Whether ``paint_stream`` has a device form for this painter (one label field, one of the six range compressions
+        on either side, L = 1 and a prior network; single-channel tiles, or a split-scale transform in the orders
+        ``_transform_parameters`` names whose levels are the model's dim_y[0] = dim_x[0]) -- WITHOUT side effects: nothing is
         captured, no random number is drawn.  ``lightcone.paint_plane`` asks this before it draws a plane's seed, so that
         a NotImplementedError raised later, from inside a capture, is an error and not a silent fall-back."""
         model = self.model
         if getattr(model, "L", 1) != 1 or getattr(model, "prior_network", None) is None:
             return False
         try:
-            scales = self._shift_log_parameters(np.atleast_1d(np.asarray(z, dtype=np.float64))[:1])[4]
+            scales = self._transform_parameters(np.atleast_1d(np.asarray(z, dtype=np.float64))[:1])[1]
         except NotImplementedError:
             return False
         if scales is None:
@@ -435,11 +439,10 @@ class CVAEPainter(Painter):
         per = (N + world_size - 1) // world_size
         lo, hi = min(rank * per, N), min((rank + 1) * per, N)
         B = int(batch_size)
-        s_in, k_in, k_out, s_out, scales = self._shift_log_parameters(zs[lo:hi])     # (NotImplementedError before any capture)
+        params, scales, modes = self._transform_parameters(zs[lo:hi])     # (NotImplementedError before any capture)
         self._check_channels(scales, "paint_stream paints")
-        params = {"xf_in": np.stack([s_in, np.full_like(s_in, k_in)], axis=1),
-                  "xf_out": np.stack([np.full_like(s_out, k_out), s_out], axis=1), "aux": zs[lo:hi]}
-        result = _paint_stream_pipeline(self, model, inputs, (H, W), lo, hi, B, params, ids[lo:hi], seed, out, scales)
+        result = _paint_stream_pipeline(self, model, inputs, (H, W), lo, hi, B, params, ids[lo:hi], seed, out, scales,
+                                        modes)
         return (result, (lo, hi)) if world_size > 1 else result
 
     def _paint_plane_device(self, delta, geo, z, weight_map, batch_size, tile_ids, seed, regularise_std=None, out=None):
@@ -461,12 +464,10 @@ class CVAEPainter(Painter):
         n = len(geo["origins"])
         B = int(batch_size)
         zs = np.full(n, float(z))
-        s_in, k_in, k_out, s_out, scales = self._shift_log_parameters(zs)     # (NotImplementedError before any capture)
+        params, scales, modes = self._transform_parameters(zs)     # (NotImplementedError before any capture)
         self._check_channels(scales, "device planes need")
-        params = {"xf_in": np.stack([s_in, np.full_like(s_in, k_in)], axis=1),
-                  "xf_out": np.stack([np.full_like(s_out, k_out), s_out], axis=1), "aux": zs}
         return _paint_plane_pipeline(self, model, tile, delta, geo, B, params, tile_ids, seed, weight_map,
-                                     regularise_std, out, scales)
+                                     regularise_std, out, scales, modes)
 
     # ------------------------------------------------------------------------------ checkpoints
     def save_state_to_file(self, filename, mode="model_state_dict+metadata"):
@@ -527,18 +528,26 @@ def _fill_block(hv, params, ids, a, b, B):
             hv[k][m:] = hv[k][m - 1]
 
 
+def _paint_graph(model, B, scales, modes):
+    """``model.paint_graph(B)`` with the keywords only a CVAE's takes, where they say something."""
+    kw = {k: v for k, v in (("scales", scales), ("modes", modes)) if v is not None}
+    return model.paint_graph(B, **kw)
+
+
 def _seed_word(seed):
     return np.array(int(seed) & 0xFFFFFFFFFFFFFFFF, dtype=np.uint64).astype(np.int64)
 
 
-def _paint_stream_pipeline(painter, model, inputs, tile_shape, lo, hi, B, params, ids, seed, out, scales=None):
+def _paint_stream_pipeline(painter, model, inputs, tile_shape, lo, hi, B, params, ids, seed, out, scales=None,
+                           modes=None):
     """Tiles [lo, hi) of ``inputs`` through ``model.paint_graph(B)``: pinned double-buffered upload / replay / download
     (``CVAEPainter.paint_stream``).  ``params`` and ``ids`` hold those tiles only.  Returns the (hi - lo, H, W) float32
     result (``out`` if given).  ``scales``: a multi-scale CVAE painter's split-scale description (``CVAE.paint_graph``);
-    raw tiles and painted tiles are single-channel either way."""
+    raw tiles and painted tiles are single-channel either way.  ``modes``: a CVAE painter's (input, label)
+    range-compression modes where they are not both shift-log (``CVAE.paint_graph``)."""
     H, W = tile_shape
     dev = model.device
-    g = model.paint_graph(B) if scales is None else model.paint_graph(B, scales=scales)
+    g = _paint_graph(model, B, scales, modes)
     torch_in = isinstance(inputs, torch.Tensor)
     result = out if out is not None else np.empty((hi - lo, H, W), np.float32)
     torch_out = isinstance(result, torch.Tensor)
@@ -630,7 +639,7 @@ def _paint_stream_pipeline(painter, model, inputs, tile_shape, lo, hi, B, params
 
 
 def _paint_plane_pipeline(painter, model, tile, delta, geo, B, params, tile_ids, seed, weight_map, regularise_std, out,
-                          scales=None):
+                          scales=None, modes=None):
     """One plane through ``model.paint_graph(B)`` on the device (``CVAEPainter._paint_plane_device``): cut, parameter
     block, replay, blend per batch on ONE stream, then the division."""
     import ctypes as C
@@ -650,7 +659,7 @@ def _paint_plane_pipeline(painter, model, tile, delta, geo, B, params, tile_ids,
                             out.dtype != torch.float64 or tuple(out.shape) != (n_plane, n_plane) or
                             not out.is_contiguous()):
         raise ValueError(f"out must be a contiguous float64 ({n_plane}, {n_plane}) tensor on {dev}")
-    g = model.paint_graph(B) if scales is None else model.paint_graph(B, scales=scales)
+    g = _paint_graph(model, B, scales, modes)
     # per-plane parameter blocks, one per batch, built like paint_stream's pinned ones and uploaded once: a batch
     # then costs one device-to-device copy of its block into the slot
     layout = g["block_layout"]

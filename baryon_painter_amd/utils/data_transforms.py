@@ -194,32 +194,80 @@ def has_split_scale(func):
     return func is not None and any(isinstance(st, _SplitScale) for st in chain_steps(func))
 
 
-def _shift_log_k(st, field):
-    if st.modes[field].lower() != "shift-log":
-        raise NotImplementedError("device-side transforms implement the 'shift-log' mode only")
-    return float(st.k_values[field])
+# mode name -> mode number of the device kernels (csrc/range_compress.hpp, BP_RC_* of include/bp_hip.h)
+MODE_IDS = {"shift-log": 0, "log": 1, "shift-log-2p": 2, "log-tanh": 3, "x/(1+x)": 4, "1/x": 5}
+
+
+class DeviceRangeCompress:
+    """A chain's range compression of one field as the device kernels take it: ``name`` / ``mode`` (the mode and its
+    number) and ``records(stats_of_field, zs)``, the (n, 4) float64 table {s, k, c, b} of csrc/range_compress.hpp for an
+    array of redshifts.  Every constant a kernel uses is computed here, in float64, with the host lambdas' own
+    expressions (``std * mean * k``, ``np.log(eps) / k``), so both sides share them to the bit.  Compares equal to the
+    shift-log ``k`` it was read from (callers of ``device_shift_log`` from before the other modes had a device form)."""
+
+    def __init__(self, st, field):
+        name = st.modes[field].lower()
+        if name not in _MODES:
+            raise ValueError(f"Mode '{st.modes[field]}' not supported.")
+        k = st.k_values[field]
+        two = name in ("shift-log-2p", "x/(1+x)")
+        ks = list(k) if two else [k]
+        if (two and len(ks) != 2) or (name != "shift-log" and not all(type(v) in (int, float) for v in ks + [st.eps])):
+            # NumPy scalars promote differently from Python floats in the host expressions the kernels restate
+            raise NotImplementedError(f"the device form of '{name}' needs Python-float k and eps, got {k!r}, {st.eps!r}")
+        self.name, self.mode = name, MODE_IDS[name]
+        self.k = [float(v) for v in ks]
+        self.eps, self.sqrt_of_mean = float(st.eps), bool(st.sqrt_of_mean)
+
+    def __eq__(self, other):
+        return self.k[0] == other if isinstance(other, (int, float)) else NotImplemented
+
+    __hash__ = None
+
+    def __float__(self):
+        return self.k[0]
+
+    def records(self, stats_of_field, zs):
+        zs = np.atleast_1d(np.asarray(zs, dtype=np.float64))
+        rec = np.zeros((len(zs), 4), np.float64)
+        std = np.sqrt(interpolate_z_many(stats_of_field, zs, "var"))
+        rec[:, 0], rec[:, 1] = std, self.k[-1] if self.name == "shift-log-2p" else self.k[0]
+        if self.name in ("log", "log-tanh"):
+            rec[:, 2] = self.eps
+            rec[:, 3] = np.log(self.eps) / self.k[0]
+        elif self.name == "shift-log-2p":
+            rec[:, 2] = self.k[0]
+        elif self.name == "x/(1+x)":
+            rec[:, 2] = self.k[1]
+        elif self.name == "1/x":
+            mean = interpolate_z_many(stats_of_field, zs, "mean")
+            mean = np.sqrt(mean) if self.sqrt_of_mean else mean
+            rec[:, 0], rec[:, 2], rec[:, 3] = std * mean * self.k[0], mean, std
+        return rec
 
 
 def device_shift_log(func, direction, field):
-    """k of the ONE shift-log range compression of a single-scale chain whose other steps are shape-only, in any
-    order; NotImplementedError for every other chain."""
+    """The ONE range compression of a single-scale chain whose other steps are shape-only, in any order, as a
+    ``DeviceRangeCompress`` (any of the six modes; ValueError for an unknown mode name, as on the host);
+    NotImplementedError for every other chain."""
     found = None
     for st in chain_steps(func):
         if isinstance(st, _RangeCompress) and st.direction == direction and found is None:
-            found = _shift_log_k(st, field)
+            found = DeviceRangeCompress(st, field)
         elif not is_shape_only(st):
             # a custom scaling step in the chain would be silently dropped on the device path
             raise NotImplementedError(f"transform step {st!r} has no device form")
     if found is None:
-        raise NotImplementedError("the device path needs the chain's shift-log range compression")
+        raise NotImplementedError("the device path needs the chain's range compression")
     return found
 
 
 def device_split_scale(func, direction, field):
-    """(k, split-scale step) of a multi-scale chain in the strict orders the kernels implement,
-         forward  [shift-log, as_float32 (optional), split-scale, shape-only steps ...]
-         inverse  [inverse split-scale, inverse shift-log, shape-only steps ...]
-    -- exactly these: the kernels filter the transformed tile and sum in front of the inverse transform."""
+    """(range compression, split-scale step) of a multi-scale chain in the strict orders the kernels implement,
+         forward  [range compression, as_float32 (optional), split-scale, shape-only steps ...]
+         inverse  [inverse split-scale, inverse range compression, shape-only steps ...]
+    -- exactly these: the kernels filter the transformed tile and sum in front of the inverse transform.  The range
+    compression is a ``DeviceRangeCompress``, as from ``device_shift_log``."""
     steps = list(chain_steps(func))
     if direction == 0:
         head = [lambda st: isinstance(st, _RangeCompress) and st.direction == 0]
@@ -232,11 +280,11 @@ def device_split_scale(func, direction, field):
     if len(steps) < len(head) or not all(ok(st) for ok, st in zip(head, steps)) or \
             not all(is_shape_only(st) for st in steps[len(head):]):
         raise NotImplementedError(
-            "a split-scale chain has a device form only as [shift-log, as_float32 (optional), split-scale, "
-            "shape-only steps] / [inverse split-scale, inverse shift-log, shape-only steps]; got "
+            "a split-scale chain has a device form only as [range compression, as_float32 (optional), split-scale, "
+            "shape-only steps] / [inverse split-scale, inverse range compression, shape-only steps]; got "
             f"{[getattr(st, '__name__', type(st).__name__) for st in steps]}")
     rc = next(st for st in steps if isinstance(st, _RangeCompress))
-    return _shift_log_k(rc, field), next(st for st in steps if isinstance(st, _SplitScale))
+    return DeviceRangeCompress(rc, field), next(st for st in steps if isinstance(st, _SplitScale))
 
 
 def split_scale_tables(n_scale, step_size, truncate):

@@ -294,11 +294,13 @@ class DeviceTileAssembler:
     starved by a serial ``DataLoader(num_workers=0)`` (painter.py:88).
 
     The transform comes from the dataset's chain (``dataset.transform_func``), read by the functions the paint path
-    uses (``data_transforms.device_shift_log`` / ``device_split_scale``): the identity, ONE "shift-log" range compression
-    among shape-only steps, or ``[shift-log, as_float32 (optional), split-scale, shape-only steps ...]``, for which
-    every field of a sample comes out as its ``levels`` pyramid planes (``bp_gather_tiles_scales``: the gather runs
-    inside the first filter pass).  Any other chain raises NotImplementedError in the constructor, before a stack is
-    uploaded.  ``subtract_minimum`` datasets are served by a per-tile minimum on the device (``bp_tile_minima``),
+    uses (``data_transforms.device_shift_log`` / ``device_split_scale``): the identity, ONE range compression (any of
+    the six modes, one per field) among shape-only steps, or ``[range compression, as_float32 (optional), split-scale,
+    shape-only steps ...]``, for which every field of a sample comes out as its ``levels`` pyramid planes
+    (``bp_gather_tiles_scales``: the gather runs inside the first filter pass).  A "shift-log" field goes through the
+    entry points it always went through; a field of another mode through ``bp_gather_tiles_scales_mode`` with the
+    records of ``DeviceRangeCompress.records``.  Any other chain raises NotImplementedError in the constructor, before a
+    stack is uploaded.  ``subtract_minimum`` datasets are served by a per-tile minimum on the device (``bp_tile_minima``),
     subtracted in float32 in front of the transform, bit-equal to the host's ``d - d.min()``.  ``k_values`` (with
     ``mode="shift-log"``) or ``mode=None`` given explicitly mean a single-scale batch without reading the chain."""
 
@@ -314,10 +316,14 @@ class DeviceTileAssembler:
         self.ds, self.device, self.torch, self.L = dataset, torch.device(device), torch, L
         self.lib = L.load()
         if mode not in ("shift-log", None):
-            raise NotImplementedError("DeviceTileAssembler implements the 'shift-log' transform only")
+            raise NotImplementedError("an explicit mode is 'shift-log' or None; the other range-compression modes are "
+                                      "read from the dataset's chain (k_values=None)")
         self.scales = None
+        self.compress = {}                               # field -> DeviceRangeCompress of a mode other than shift-log
         if k_values is None and mode == "shift-log":
-            mode, k_values, self.scales = self._read_chain(dataset, T)
+            found, self.scales = self._read_compressions(dataset, T)
+            mode, k_values = ("shift-log" if found else None), {f: float(rc) for f, rc in found.items()}
+            self.compress = {f: rc for f, rc in found.items() if rc.name != "shift-log"}
         self.mode = mode
         self.k_values = k_values or {}
         self._interp = T.interpolate_z
@@ -335,19 +341,44 @@ class DeviceTileAssembler:
                     self.stacks[(f, z, slab)] = torch.from_numpy(a).to(self.device)
 
     @staticmethod
-    def _read_chain(dataset, T):
-        """(mode, k_values, scales) of ``dataset.transform_func``; NotImplementedError for a chain without a device
-        form."""
+    def _read_compressions(dataset, T):
+        """({field: DeviceRangeCompress}, scales) of ``dataset.transform_func`` ({} for the identity);
+        NotImplementedError for a chain without a device form, and for a forward chain whose mode of a field is not the
+        one the range compression of ``dataset.inverse_transform_func`` (if it has one) undoes."""
         func, fields = dataset.transform_func, [dataset.input_field] + list(dataset.label_fields)
         if func is _identity or func is None:
-            return None, {}, None
+            return {}, None
+        scales = None
         if T.has_split_scale(func):
             found = [T.device_split_scale(func, 0, f) for f in fields]
             split = found[0][1]
             scales = {"n_scale": split.n_scale, "step_size": split.step_size,
                       "include_original": bool(split.include_original), "truncate": split.truncate}
-            return "shift-log", {f: k for f, (k, _) in zip(fields, found)}, scales
-        return "shift-log", {f: T.device_shift_log(func, 0, f) for f in fields}, None
+            found = {f: rc for f, (rc, _) in zip(fields, found)}
+        else:
+            found = {f: T.device_shift_log(func, 0, f) for f in fields}
+        # The mode is now read per field, so it is checked against the range compression the dataset's inverse chain
+        # undoes, where that chain holds one: a set whose two chains name different modes for a field would train on
+        # tiles that the transforms its checkpoints carry do not invert.
+        for st in T.chain_steps(getattr(dataset, "inverse_transform_func", None)):
+            if isinstance(st, T._RangeCompress) and st.direction == 1:
+                for f, rc in found.items():
+                    if str(st.modes.get(f, rc.name)).lower() != rc.name:
+                        raise NotImplementedError(
+                            f"field '{f}' is compressed with '{rc.name}' but the dataset's inverse transform undoes "
+                            f"'{st.modes[f]}': such a pair of chains has no device form")
+        return found, scales
+
+    @classmethod
+    def _read_chain(cls, dataset, T):
+        """(mode, k_values, scales) of ``dataset.transform_func``: mode "shift-log" (None for the identity), or
+        {field: mode name} where a field has another mode; NotImplementedError for a chain without a device form."""
+        found, scales = cls._read_compressions(dataset, T)
+        if not found:
+            return None, {}, scales
+        names = {f: rc.name for f, rc in found.items()}
+        mode = "shift-log" if set(names.values()) == {"shift-log"} else names
+        return mode, {f: (rc.k[0] if len(rc.k) == 1 else tuple(rc.k)) for f, rc in found.items()}, scales
 
     @property
     def levels(self):
@@ -382,7 +413,7 @@ class DeviceTileAssembler:
                 (rec[n]["r0"], rec[n]["rr"], rec[n]["rc"], rec[n]["c0"], rec[n]["cr"], rec[n]["cc"]) = self._perm_affine(p)
             scale = slics_scale(ds.n_grid) if (field == ds.input_field and ds.scale_to_SLICS) else 1.0
             xf[n]["scale"] = scale
-            if self.mode == "shift-log":
+            if self.mode == "shift-log" and field not in self.compress:
                 sig = np.sqrt(self._interp(ds.stats[field], z)["var"])
                 xf[n]["inv_sigma"] = 1.0 / sig
                 xf[n]["inv_k"] = 1.0 / float(self.k_values[field])
@@ -408,17 +439,27 @@ class DeviceTileAssembler:
                 keep.append(minima)
                 L.check(self.lib.bp_tile_minima(L.ptr(dev[0]), L.ptr(dev[1]), L.ptr(dev[2]), n, t, L.ptr(minima), st),
                         "tile minima")
-            if self.scales is None and minima is None:
+            rc = self.compress.get(field)
+            records = None
+            if rc is not None:                                       # a mode other than shift-log: its (n, 4) records
+                zs = [ds.sample_idx_to_redshift(int(i)) for i in indices]
+                records = torch.from_numpy(rc.records(ds.stats[field], zs)).to(self.device)
+                keep.append(records)
+            if self.scales is None and minima is None and rc is None:
                 L.check(self.lib.bp_gather_tiles(L.ptr(dev[0]), L.ptr(dev[1]), L.ptr(dev[2]), n, t, L.ptr(out), st),
                         "gather tiles")
             else:
                 ws = int(self.lib.bp_gather_tiles_scales_workspace(n, t, sc["n_scale"]))
                 if ws and (self._scratch is None or self._scratch.numel() < ws):
                     self._scratch = torch.empty(ws, dtype=torch.uint8, device=self.device)
-                L.check(self.lib.bp_gather_tiles_scales(
-                    L.ptr(dev[0]), L.ptr(dev[1]), L.ptr(dev[2]), L.ptr(minima), n, t, sc["n_scale"],
-                    int(sc["include_original"]), L.ptr(sc["weights"]), sc["radii"], L.ptr(self._scratch if ws else None),
-                    ws, L.ptr(out), st), "gather tiles into scales")
+                args = (L.ptr(dev[0]), L.ptr(dev[1]), L.ptr(dev[2]), L.ptr(minima), n, t, sc["n_scale"],
+                        int(sc["include_original"]), L.ptr(sc["weights"]), sc["radii"],
+                        L.ptr(self._scratch if ws else None), ws, L.ptr(out), st)
+                if rc is None:
+                    L.check(self.lib.bp_gather_tiles_scales(*args), "gather tiles into scales")
+                else:
+                    L.check(self.lib.bp_gather_tiles_scales_mode(rc.mode, L.ptr(records), *args),
+                            f"gather tiles into scales ({rc.name})")
             outs.append(out)
         torch.cuda.current_stream().synchronize()        # descriptors may be freed after this
         z = torch.tensor([ds.sample_idx_to_redshift(int(i)) for i in indices], device=self.device,

@@ -331,6 +331,28 @@ int bp_paint_load2(const float* raw_nchw, int32_t c, const double* sigma_k, cons
                    const bp_view* out, const bp_view* out2, void* stream);
 int bp_paint_store(const bp_view* src, const bp_pointwise* pw, int32_t softplus, const double* k_sigma,
                    float* dst_nchw, void* stream);
+/* ---- the six range-compression modes (utils/data_transforms.py: _MODES; csrc/range_compress.hpp) -----------------
+ * The `_mode` forms of the transform-carrying entry points take one mode per launch (a painter has one per field) and
+ * `records`: device, (n, 4) float64 {s, k, c, b} per tile, every constant computed on the host in float64
+ * (data_transforms.DeviceRangeCompress.records), so host and device share the branch values exactly:
+ *   BP_RC_SHIFT_LOG    {std, k, -, -}             log(x/std + 1)/k
+ *   BP_RC_LOG          {std, k, eps, log(eps)/k}  x > 0 ? log(x/std + eps)/k : log(eps)/k
+ *   BP_RC_SHIFT_LOG_2P {std, k[1], k[0], -}       log(x/std + k[0])/k[1]
+ *   BP_RC_LOG_TANH     {std, k, eps, -}           x > 0 ? tanh(log(x/std + eps)/k) : -1
+ *   BP_RC_X_1PX        {std, k[0], k[1], -}       x/(x + std)*k[0] - k[1]
+ *   BP_RC_INV_X        {std*mean*k, k, mean, std} t = x/(std*mean*k); t > -1 ? 2/(t + 1) - 1.001 : -1
+ * Forward is evaluated in float64 and rounded to float32 once; the inverses follow the host's float32 / float64
+ * promotion for a float32 activation (DESIGN.md has the table); a NaN takes the branch np.where takes.  The entry points
+ * without `_mode` are these at BP_RC_SHIFT_LOG over their tables of two doubles: same kernels, same bits as before.
+ * An unknown mode is BP_EINVAL and a bf16 view BP_EUNSUPPORTED, both before anything is written; otherwise arguments,
+ * limits and error order are those of the form without `_mode`. */
+enum { BP_RC_SHIFT_LOG = 0, BP_RC_LOG = 1, BP_RC_SHIFT_LOG_2P = 2, BP_RC_LOG_TANH = 3, BP_RC_X_1PX = 4, BP_RC_INV_X = 5 };
+int bp_paint_load_mode(int32_t mode, const float* raw_nchw, int32_t c, const double* records, const float* aux,
+                       int32_t caux, const bp_view* out, void* stream);
+int bp_paint_load2_mode(int32_t mode, const float* raw_nchw, int32_t c, const double* records, const float* aux,
+                        int32_t caux, const bp_view* out, const bp_view* out2, void* stream);
+int bp_paint_store_mode(int32_t mode, const bp_view* src, const bp_pointwise* pw, int32_t softplus,
+                        const double* records, float* dst_nchw, void* stream);
 /* The same pair for the conditional GAN (painter.CGANPainter: the "shift-log-cam" transform into the tanh range and
  * the generator's tanh head), everything after the float32 tanh in double, as the host's NumPy expressions:
  *   bp_paint_load_cam : out[n,:,:,ch<c] = (float) (log((double) raw / xf[n][0] + 1) / xf[n][1] - xf[n][2]), xf (n,3)
@@ -374,6 +396,13 @@ int bp_paint_load_scales2(const float* raw_nchw, const double* sigma_k, const fl
                           void* scratch, size_t scratch_bytes, const bp_view* out, const bp_view* out2, void* stream);
 int bp_paint_store_scales(const bp_view* src, const bp_pointwise* pw, int32_t softplus, int32_t include_original,
                           const double* k_sigma, float* dst_nchw, void* stream);
+/* bp_paint_load_scales2 / bp_paint_store_scales with any range-compression mode (see bp_paint_load_mode). */
+int bp_paint_load_scales2_mode(int32_t mode, const float* raw_nchw, const double* records, const float* aux,
+                               int32_t caux, int32_t n_scale, int32_t include_original, const double* weights,
+                               const int32_t* radii, void* scratch, size_t scratch_bytes, const bp_view* out,
+                               const bp_view* out2, void* stream);
+int bp_paint_store_scales_mode(int32_t mode, const bp_view* src, const bp_pointwise* pw, int32_t softplus,
+                               int32_t include_original, const double* records, float* dst_nchw, void* stream);
 /* eps (L, n, per_tile) standard normal for the sampler of cvae.py:64-65 from Philox4x32-10 keyed on `seed`, counter
  * (element group, l, tile id): a tile's noise depends on (seed, its GLOBAL id) only, not on batch, stream or rank
  * (torch.randn on the device in the reference: same distribution, no reproducible stream to match). */
@@ -526,6 +555,13 @@ size_t bp_gather_tiles_scales_workspace(int32_t n, int32_t tile, int32_t n_scale
 int bp_gather_tiles_scales(const void* desc100, const void* desc150, const void* xform, const float* minima,
                            int32_t n, int32_t tile, int32_t n_scale, int32_t include_original, const double* weights,
                            const int32_t* radii, void* scratch, size_t scratch_bytes, float* out_nchw, void* stream);
+/* bp_gather_tiles_scales with range-compression mode `mode` over `records` (see bp_paint_load_mode) in place of the
+ * transform xform names: xform's `scale` is still applied, its mode / inv_sigma / inv_k are not read.  With n_scale = 1,
+ * include_original = 0 and minima = NULL this is bp_gather_tiles for any mode (out (n, 1, tile, tile)). */
+int bp_gather_tiles_scales_mode(int32_t mode, const double* records, const void* desc100, const void* desc150,
+                                const void* xform, const float* minima, int32_t n, int32_t tile, int32_t n_scale,
+                                int32_t include_original, const double* weights, const int32_t* radii, void* scratch,
+                                size_t scratch_bytes, float* out_nchw, void* stream);
 
 /* ---- optimiser (replaces torch.optim.Adam.step, painter.py:93,228; same arithmetic) --------- */
 int bp_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
