@@ -117,6 +117,8 @@ SIGNATURES = {
     "bp_nchw_to_view": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _VP, _P]),
     "bp_view_to_nchw": (C.c_int, [_VP, _PWP, C.c_int32, _P, _P]),
     "bp_fill": (C.c_int, [_P, C.c_int64, C.c_float, _P]),
+    "bp_repeat_samples": (C.c_int, [_VP, C.c_int32, _VP, _P]),
+    "bp_repeat_samples_adjoint": (C.c_int, [_VP, C.c_int32, _VP, _P]),
     "bp_paint_load": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _VP, _P]),
     "bp_paint_load2": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _VP, _VP, _P]),
     "bp_paint_store": (C.c_int, [_VP, _PWP, C.c_int32, _P, _P, _P]),

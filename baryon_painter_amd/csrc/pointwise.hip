@@ -510,6 +510,37 @@ __global__ __launch_bounds__(RB) void fill_kernel(float* dst, int64_t n, float v
   if (i < n) dst[i] = v;
 }
 
+// ---------------------------------------------------------------- repeat over L (cvae.py:109) and its adjoint
+// dst[(l * per + p), g] = src[p, g] for l < L, raw values; T = float4 where every channel slice starts on a 16-byte
+// boundary and holds whole quads, float otherwise (strides / offsets / cg in units of T).  per = n*h*w pixels of src.
+template <typename T>
+__global__ __launch_bounds__(RB) void repeat_samples_kernel(const T* src, int s_cs, int s_co, T* dst, int d_cs, int d_co,
+                                                            int cg, int L, int64_t per, int64_t total) {
+  const int64_t i = (int64_t)blockIdx.x * RB + threadIdx.x;
+  if (i >= total) return;
+  const int64_t p = i / cg;
+  const int g = (int)(i - p * cg);
+  const T v = src[p * s_cs + s_co + g];
+  for (int l = 0; l < L; ++l) dst[((int64_t)l * per + p) * d_cs + d_co + g] = v;
+}
+
+__device__ __forceinline__ float add_t(float a, float b) { return a + b; }
+__device__ __forceinline__ float4 add_t(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+
+// d_src[p, g] = ((d_dst[p, g] + d_dst[per + p, g]) + d_dst[2 per + p, g]) + ...: ascending l, one thread per element,
+// so the same inputs give the same bits
+template <typename T>
+__global__ __launch_bounds__(RB) void repeat_samples_adjoint_kernel(const T* d_dst, int d_cs, int d_co, T* d_src, int s_cs,
+                                                                    int s_co, int cg, int L, int64_t per, int64_t total) {
+  const int64_t i = (int64_t)blockIdx.x * RB + threadIdx.x;
+  if (i >= total) return;
+  const int64_t p = i / cg;
+  const int g = (int)(i - p * cg);
+  T acc = d_dst[p * d_cs + d_co + g];
+  for (int l = 1; l < L; ++l) acc = add_t(acc, d_dst[((int64_t)l * per + p) * d_cs + d_co + g]);
+  d_src[p * s_cs + s_co + g] = acc;
+}
+
 // ---------------------------------------------------------------- latent sampler + KL
 struct LatentArgs {
   bp_latent lt;
@@ -532,8 +563,13 @@ __global__ __launch_bounds__(RB) void latent_forward_kernel(LatentArgs a) {
     const int c = (i / hw) % zc;
     const int64_t n = i / (hw * zc);
     const int64_t pix = n * hw + yx;
-    const float mu = pw_apply(a.qpw, c, a.q.p[pix * a.q.cs + a.q.co + c]);
-    const float lv = pw_apply(a.qpw, zc + c, a.q.p[pix * a.q.cs + a.q.co + zc + c]);
+    // (no source for the sample -- sampling the standard-normal prior of a model without prior network, cvae.py:83-85:
+    //  z_mu = z_log_var = 0, so z = eps * (1 + min_z_var))
+    float mu = 0.f, lv = 0.f;
+    if (a.q.p) {
+      mu = pw_apply(a.qpw, c, a.q.p[pix * a.q.cs + a.q.co + c]);
+      lv = pw_apply(a.qpw, zc + c, a.q.p[pix * a.q.cs + a.q.co + zc + c]);
+    }
     float pm = 0.f, plv = 0.f;
     if (a.p.p) {
       pm = pw_apply(a.ppw, c, a.p.p[pix * a.p.cs + a.p.co + c]);
@@ -550,7 +586,7 @@ __global__ __launch_bounds__(RB) void latent_forward_kernel(LatentArgs a) {
     for (int l = 0; l < a.lt.L; ++l) {
       const float e = a.eps[(int64_t)l * a.nelem + i];
       const int64_t zp = ((int64_t)l * a.lt.n + n) * hw + yx;
-      a.z.p[zp * a.z.cs + a.z.co + c] = fmaf(e, sd, mu);
+      a.z.p[zp * a.z.cs + a.z.co + c] = a.q.p ? fmaf(e, sd, mu) : e * sd;
     }
   }
   sh[threadIdx.x] = kl;
@@ -1297,6 +1333,52 @@ int bp_fill(float* dst, int64_t n, float value, void* stream) {
   return BP_OK;
 }
 
+static bool repeat_views_ok(const bp_view* one, int32_t L, const bp_view* many) {
+  return bp_view_ok(one) && bp_view_ok(many) && L >= 1 && (int64_t)many->n == (int64_t)L * one->n && many->h == one->h &&
+         many->w == one->w && many->c == one->c;
+}
+static bool repeat_vec4(const bp_view* a, const bp_view* b) {
+  return a->c % 4 == 0 && bp_view_vec4(a) && bp_view_vec4(b);
+}
+
+int bp_repeat_samples(const bp_view* src, int32_t L, const bp_view* dst, void* stream) {
+  if (!repeat_views_ok(src, L, dst)) return BP_EINVAL;
+  const int64_t per = bp_view_pixels(src);
+  const bool v4 = repeat_vec4(src, dst);
+  const int cg = v4 ? src->c / 4 : src->c;
+  const int64_t total = per * cg;
+  if ((total + RB - 1) / RB >= (int64_t)1 << 31) return BP_EUNSUPPORTED;
+  if (v4)
+    hipLaunchKernelGGL(repeat_samples_kernel<float4>, dim3(nblocks(total)), dim3(RB), 0, bp_stream(stream),
+                       reinterpret_cast<const float4*>(src->ptr), src->cstride / 4, src->coff / 4,
+                       reinterpret_cast<float4*>(dst->ptr), dst->cstride / 4, dst->coff / 4, cg, (int)L, per, total);
+  else
+    hipLaunchKernelGGL(repeat_samples_kernel<float>, dim3(nblocks(total)), dim3(RB), 0, bp_stream(stream),
+                       (const float*)src->ptr, src->cstride, src->coff, dst->ptr, dst->cstride, dst->coff, cg, (int)L, per,
+                       total);
+  BP_CHECK_LAUNCH();
+  return BP_OK;
+}
+
+int bp_repeat_samples_adjoint(const bp_view* d_dst, int32_t L, const bp_view* d_src, void* stream) {
+  if (!repeat_views_ok(d_src, L, d_dst)) return BP_EINVAL;
+  const int64_t per = bp_view_pixels(d_src);
+  const bool v4 = repeat_vec4(d_src, d_dst);
+  const int cg = v4 ? d_src->c / 4 : d_src->c;
+  const int64_t total = per * cg;
+  if ((total + RB - 1) / RB >= (int64_t)1 << 31) return BP_EUNSUPPORTED;
+  if (v4)
+    hipLaunchKernelGGL(repeat_samples_adjoint_kernel<float4>, dim3(nblocks(total)), dim3(RB), 0, bp_stream(stream),
+                       reinterpret_cast<const float4*>(d_dst->ptr), d_dst->cstride / 4, d_dst->coff / 4,
+                       reinterpret_cast<float4*>(d_src->ptr), d_src->cstride / 4, d_src->coff / 4, cg, (int)L, per, total);
+  else
+    hipLaunchKernelGGL(repeat_samples_adjoint_kernel<float>, dim3(nblocks(total)), dim3(RB), 0, bp_stream(stream),
+                       (const float*)d_dst->ptr, d_dst->cstride, d_dst->coff, d_src->ptr, d_src->cstride, d_src->coff, cg,
+                       (int)L, per, total);
+  BP_CHECK_LAUNCH();
+  return BP_OK;
+}
+
 static bool latent_view_ok(const bp_latent* lt, const bp_view* v, int n, int c) {
   return bp_view_ok(v) && v->n == n && v->h == lt->zh && v->w == lt->zw && v->c == c;
 }
@@ -1305,7 +1387,7 @@ int bp_latent_forward(const bp_latent* lt, const bp_view* q_raw, const bp_pointw
                       const bp_pointwise* p_pw, const float* eps, float* stats4, const bp_view* z,
                       double* kl_sum, void* workspace, size_t workspace_bytes, void* stream) {
   if (!lt || lt->n <= 0 || lt->L <= 0 || lt->zc <= 0 || !eps || !stats4 || !kl_sum) return BP_EINVAL;
-  if (!latent_view_ok(lt, q_raw, lt->n, 2 * lt->zc)) return BP_EINVAL;
+  if (q_raw ? !latent_view_ok(lt, q_raw, lt->n, 2 * lt->zc) : p_raw != nullptr) return BP_EINVAL;
   if (p_raw && !latent_view_ok(lt, p_raw, lt->n, 2 * lt->zc)) return BP_EINVAL;
   if (!latent_view_ok(lt, z, lt->n * lt->L, lt->zc)) return BP_EINVAL;
   LatentArgs a{};

@@ -79,7 +79,7 @@ def paint_plane(painter, delta, tile_relative_size, n_pixel_tile, z, min_tile_ov
     every call: like the reference (fresh ``torch.randn`` per tile, cvae.py:64) two planes never share their latent
     noise unless asked to, and ``torch.manual_seed`` makes a whole light cone reproducible.  Pass an explicit ``seed``
     (+ distinct ``first_tile_id`` ranges) to reproduce one plane.  Painters / transforms the device pipeline has no
-    form for (modes other than 'shift-log', no transform, several label fields, L != 1, no prior network) go through
+    form for (no transform, several label fields, L != 1) go through
     ``paint_batch`` as before.
 
     ``on_device=True`` (opt-in; needs ``painter.can_paint_stream(z)``, NotImplementedError otherwise, raised before any

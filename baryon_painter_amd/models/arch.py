@@ -82,7 +82,7 @@ def conv_up(in_channel, channels, scales, **kw_args):
     return _chain(in_channel, channels, scales, type="transp conv", **kw_args)
 
 
-def fiducial_architecture(tile_size=512, predict_var=False, n_res=4, n_scale=1):
+def fiducial_architecture(tile_size=512, predict_var=False, n_res=4, n_scale=1, p_y_in=None, prior=True):
     """The "CVAE fiducial" network: trained_models/CVAE/fiducial/architecture.txt
     (mean head only); ``predict_var=True`` gives the two-head superset that
     scripts/CVAE_single_scale.py:97-138 builds.  dim_z = tile_size/32.
@@ -91,8 +91,17 @@ def fiducial_architecture(tile_size=512, predict_var=False, n_res=4, n_scale=1):
     of ``data_transforms.create_split_scale_transform``, the original included where it is kept), from which the
     script derives dim_y, dim_x = n_x_features (one label field) and the generator's stem
     (CVAE_single_scale.py:92-95,113); the stems that read y -- prior_z_y, q_y_in -- and q_x_in take that many channels
-    plus the aux label, and the heads end in n_x_features channels."""
+    plus the aux label, and the heads end in n_x_features channels.
+
+    ``p_y_in``: a layer list for the generator's conditioning stem (cvae.py:106), passed through; it reads the
+    n_scale + 1 channels of y with the aux label, keeps the resolution, and the generator's first convolution then takes
+    its output channels beside h_z.  None (default): the identity, as in the reference's configurations.
+    ``prior=False`` leaves ``prior_z_y`` out: the standard-normal prior of cvae.py:83-85."""
     n_aux_label, n_x_feature = 1, n_scale
+    c_hy = n_aux_label + n_scale
+    for layer in p_y_in or []:
+        if layer[0].lower() in ("conv", "sn conv", "transp conv"):
+            c_hy = layer[1]["out_channels"]
     zs = tile_size // 32
     dim_z = (1, zs, zs)
     dim = (n_x_feature, tile_size, tile_size)
@@ -117,9 +126,9 @@ def fiducial_architecture(tile_size=512, predict_var=False, n_res=4, n_scale=1):
         "q_x_in": conv_down(in_channel=n_x_feature, channels=[8, 16, 32], scales=[2, 4, 4]),
         "q_y_in": conv_down(in_channel=n_scale + n_aux_label, channels=[8, 16, 32], scales=[2, 4, 4]),
         "q_x_y_out": conv_block(64, 2 * dim_z[0], kernel=5) + [("unflatten", (2, *dim_z))],
-        "p_y_in": None,
+        "p_y_in": p_y_in,
         "p_z_in": conv_up(1, channels=[1, 1, 1], scales=[2, 4, 4], bias=False, batchnorm=True),
-        "p_y_z_in": (conv_block(n_aux_label + n_scale + 1, 16, kernel=5)
+        "p_y_z_in": (conv_block(c_hy + 1, 16, kernel=5)
                      + conv_down(in_channel=16, channels=[32, 64, 128], scales=[2, 2, 2])
                      + [("residual block", res_block(128)) for _ in range(n_res)]
                      + conv_up(128, channels=[64, 32, 16], scales=[2, 2, 2], bias=False,
@@ -129,6 +138,8 @@ def fiducial_architecture(tile_size=512, predict_var=False, n_res=4, n_scale=1):
         "min_z_var": 1e-7,
         "L": 1,
     }
+    if not prior:
+        del arch["prior_z_y"]
     return arch
 
 

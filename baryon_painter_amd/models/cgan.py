@@ -21,7 +21,7 @@ import torch
 
 from .. import _lib as L
 from .arch import cgan_discriminator_architecture, cgan_generator_architecture
-from .graph import SNConv2d, Slot, build_holders, compile_sequential, _stream
+from .graph import SNConv2d, Slot, build_holders, capture_without_gc, compile_sequential, _stream
 
 
 class _GanPlan:
@@ -456,7 +456,8 @@ class CGAN(torch.nn.Module):
         torch.cuda.current_stream(dev).wait_stream(side)
         for sl in st["slots"]:
             graph = torch.cuda.CUDAGraph()
-            with torch.no_grad(), torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):
+            with torch.no_grad(), capture_without_gc(), \
+                    torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):
                 run(sl)
             sl["graph"] = graph
         return st

@@ -19,7 +19,8 @@ import torch
 
 from .. import _lib as L
 from .arch import conv_block, conv_down, conv_up, res_block  # noqa: F401  (reference: ``from .utils import *``)
-from .graph import (PW, ConvUnit, PackBatch, Slot, build_holders, compile_sequential, probe_output, _stream)
+from .graph import (PW, ConvUnit, PackBatch, Slot, build_holders, capture_without_gc, compile_sequential, probe_output,
+                    _stream)
 
 pi = math.pi
 
@@ -27,7 +28,9 @@ pi = math.pi
 class _Plan:
     """All device buffers and the launch schedule for one (batch, mode) signature."""
 
-    def __init__(self, model, n, with_grad, with_q=True):
+    def __init__(self, model, n, with_grad, with_q=True, samples=None):
+        """``samples``: latent draws per input of this plan; None = the model's ``L`` (``sample_P`` paints with one,
+        cvae.py:155)."""
         self.model = model
         self.lib = model._lib
         self.device = model.device
@@ -41,7 +44,7 @@ class _Plan:
         self.ws = None
         a = model.architecture
         dev = self.device
-        Lr = model.L
+        Lr = self.L = model.L if samples is None else int(samples)
         cy, H, W = model.dim_y
         cx = model.dim_x[0]
         if tuple(model.dim_x[1:]) != (H, W):
@@ -104,16 +107,36 @@ class _Plan:
         c_hz, hz_h, hz_w = probe_output(a["p_z_in"], zc, zh, zw)
         if (hz_h, hz_w) != (H, W):
             raise ValueError(f"p_z_in produces {hz_h}x{hz_w}, dim_y is {H}x{W}")
-        if model.p_y_in is not None:
-            raise NotImplementedError("p_y_in networks are not supported by the HIP path yet "
-                                      "(the reference configurations use p_y_in=None)")
+        # p_y_in=None (or an empty list) is the identity: y and the aux planes themselves are the generator's h_y
+        y_net = model.has_p_y_in
         c_hy = cy + caux
+        if y_net:
+            c_hy, hy_h, hy_w = probe_output(a["p_y_in"], cy + caux, H, W)
+            if (hy_h, hy_w) != (H, W):
+                raise ValueError(f"p_y_in produces {hy_h}x{hy_w}, dim_y is {H}x{W}")
         ccat = c_hz + c_hy
         self.p_in = Slot.new(nL, H, W, ccat, dev, cstride=((ccat + 3) // 4) * 4)
         self.p_in.pw = PW.identity(ccat, dev)
         hz_slot = self.p_in.sub(0, c_hz, pw=self.p_in.pw.slice(0, c_hz),
-                                dense_grad=os.environ.get("BP_DENSE_ZGRAD", "1") != "0")
-        self.hy_slot = self.p_in.sub(c_hz, ccat)
+                                dense_grad=not y_net and os.environ.get("BP_DENSE_ZGRAD", "1") != "0")
+        # p_y_in(y): n samples, whatever L is (cvae.py:106: batch-norm statistics over n).  Its last convolution writes
+        # RAW values and leaves its batch-norm / activation pending on the [c_hz, ccat) slice of p_in's pointwise.  L = 1:
+        # straight into that slice of p_in, as p_z_in does; L > 1: into a slot of its own, which bp_repeat_samples copies
+        # into the slice L times (the pending record then applies to every copy alike).
+        self.y_units, self.hy_one = [], None
+        if y_net:
+            hy_pw = self.p_in.pw.slice(c_hz, ccat)
+            self.hy_slot = self.p_in.sub(c_hz, ccat, pw=hy_pw)
+            hy_out = self.hy_slot if Lr == 1 else Slot.new(n, H, W, c_hy, dev, pw=hy_pw)
+            uy, sy, tr = compile_sequential(self, "p_y_in.", a["p_y_in"], model.p_y_in, self.y2,
+                                            out_slot=hy_out, out_pw=hy_pw, need_input_grad=False)
+            self._no_trailing(tr, "p_y_in")
+            if sy is not hy_out:
+                raise NotImplementedError("p_y_in must end in a convolution (+ batch-norm / activation)")
+            self.y_units = uy
+            self.hy_one = hy_out if Lr != 1 else None
+        else:
+            self.hy_slot = self.p_in.sub(c_hz, ccat)
         uz, sz, tr = compile_sequential(self, "p_z_in.", a["p_z_in"], model.p_z_in, self.z,
                                         out_slot=hz_slot, out_pw=hz_slot.pw)
         self._no_trailing(tr, "p_z_in")
@@ -121,8 +144,9 @@ class _Plan:
             raise NotImplementedError("p_z_in must end in a convolution")
         ub, sb, tr = compile_sequential(self, "p_y_z_in.", a["p_y_z_in"], model.p_y_z_in, self.p_in)
         self._no_trailing(tr, "p_y_z_in")
-        if ub and isinstance(ub[0], ConvUnit):
+        if ub and isinstance(ub[0], ConvUnit) and not y_net:
             ub[0].restrict_dgrad(0, c_hz, target=hz_slot)   # y and the aux label are data: only h_z carries a gradient
+        # (with a p_y_in network every channel of p_in carries one: the data gradient covers all c_hz + c_hy)
         self.g_units = [uz, ub]
         self.h = sb
         um, sm, tr = compile_sequential(self, "p_mu_out.", a["p_y_z_out"][0], model.p_mu_out, sb)
@@ -166,7 +190,7 @@ class _Plan:
         self.deferring = False
         self.defer_reduce = with_grad and os.environ.get("BP_DEFER_REDUCE", "1") != "0"
         if self.defer_reduce:
-            for u in self._flat([u for us in self.q_units for u in us] + list(self.p_units)
+            for u in self._flat([u for us in self.q_units for u in us] + list(self.p_units) + list(self.y_units)
                                 + [u for us in self.g_units for u in us] + list(self.mu_units) + list(self.var_units)):
                 # (BP_DEFER_MAX_MB: layers with larger partial sums reduce at once.  Measured: deferring ALL fp32 layers,
                 #  the trunk's 16 MB and the encoder layer's 25 MB of partial sums included, is best -- 41.3 vs 41.6 ms
@@ -179,8 +203,16 @@ class _Plan:
             self.ws2 = torch.zeros_like(self.ws)
         # q_x_in, q_y_in and the prior network are independent chains of small kernels (none fills the GPU):
         # q_y_in and the prior run on their own streams, each with its own reduction workspace
-        all_units = self._flat([u for us in self.q_units for u in us] + list(self.p_units)
+        all_units = self._flat([u for us in self.q_units for u in us] + list(self.p_units) + list(self.y_units)
                                + [u for us in self.g_units for u in us] + list(self.mu_units) + list(self.var_units))
+        # p_y_in does not depend on the latent: in a training plan it runs on the weight-gradient stream (idle during the
+        # forward pass) beside the recognition / prior networks, with a reduction workspace of its own.  Not with global
+        # batch-norm statistics: those collectives stay on the main stream, in program order.
+        self.y_beside = bool(self.y_units) and self.side is not None and not (model.sync is not None and model.sync.sync_bn)
+        if self.y_beside:
+            self.ws_y = torch.zeros_like(self.ws)
+            for u in self._flat(self.y_units):
+                u.ws_name = "ws_y"
         for u in self._flat([u for us in self.g_units for u in us] + list(self.mu_units) + list(self.var_units)):
             u.pack_late = True              # (graph.PackBatch: nothing in front of run_generator reads their weights)
         self.pack_batch = PackBatch(self, [u for u in all_units if isinstance(u, ConvUnit)])
@@ -310,6 +342,10 @@ class _Plan:
         for us in reversed(self.g_units):
             for u in reversed(us):
                 u.prepare_backward()
+        if self.hy_one is not None:
+            self.hy_slot.ensure_grad()           # (the slice of d/d p_in that bp_repeat_samples_adjoint sums over l)
+        for u in reversed(self.y_units):
+            u.prepare_backward()
         self.z.ensure_grad()
         for u in reversed(self.p_units):
             u.prepare_backward()
@@ -367,7 +403,15 @@ class _Plan:
             return
         self.pack_batch.run()
 
-    def load_inputs(self, y, aux, x=None):
+    def run_y_net(self, training):
+        """h_y = p_y_in(y with aux) into its slice of the generator's input, repeated over L (cvae.py:106-109)."""
+        for u in self.y_units:
+            u.forward(training)
+        if self.hy_one is not None:
+            L.check(self.lib.bp_repeat_samples(C.byref(self.hy_one.view), self.L, C.byref(self.hy_slot.view), _stream()),
+                    "repeat h_y over L")
+
+    def load_inputs(self, y, aux, x=None, training=False):
         self.pack_all()
         lib, st = self.lib, _stream()
         m = self.model
@@ -380,14 +424,17 @@ class _Plan:
         L.check(lib.bp_nchw_to_view(L.ptr(y), cy, auxp, self.caux, C.byref(self.y2.view), st), "merge_aux_label")
 
         def generator_copy(stream):
-            for l in range(m.L):
+            if self.y_units:
+                return self.run_y_net(training)
+            for l in range(self.L):
                 v = L.View(self.p_in.buf[l * self.n:].data_ptr(), self.n, self.hy_slot.h, self.hy_slot.w,
                            self.hy_slot.c, self.hy_slot.cstride, self.hy_slot.coff)
                 L.check(lib.bp_nchw_to_view(L.ptr(y), cy, auxp, self.caux, C.byref(v), stream), "merge_aux_label (P)")
         # the generator's copy of y is not read before run_generator: in a training plan it goes to the weight-
         # gradient stream (idle during the forward pass), beside the recognition / prior networks
         self._gen_inputs = None
-        if self.side is not None and not torch.cuda.is_current_stream_capturing():
+        if self.side is not None and not torch.cuda.is_current_stream_capturing() \
+                and (not self.y_units or self.y_beside):
             self.side.wait_stream(torch.cuda.current_stream(self.device))
             with torch.cuda.stream(self.side):
                 generator_copy(_stream())
@@ -412,10 +459,12 @@ class _Plan:
         lib, st = self.lib, _stream()
         self.eps = eps.to(torch.float32).contiguous()
         q = self.q_head if use_q else self.p_head
-        if q is None:
-            raise NotImplementedError("sampling from the standard-normal prior (no prior_z_y) is not implemented")
+        if use_q and q is None:
+            raise RuntimeError("this plan was built without the recognition network")
         p = self.p_head
-        L.check(lib.bp_latent_forward(C.byref(self.lat), C.byref(q.view), q.pw_struct(),
+        # (q None: sampling without a prior network = the standard-normal prior, cvae.py:83-85: a null source)
+        L.check(lib.bp_latent_forward(C.byref(self.lat), None if q is None else C.byref(q.view),
+                                      None if q is None else q.pw_struct(),
                                       None if p is None else C.byref(p.view),
                                       None if p is None else p.pw_struct(), L.ptr(self.eps),
                                       L.ptr(self.stats4), C.byref(self.z.view), L.ptr(self.kl_sum),
@@ -446,7 +495,7 @@ class _Plan:
     def forward_train(self, x, y, aux, eps, training=True):
         m = self.model
         self.mark("step")
-        self.load_inputs(y, aux, x)
+        self.load_inputs(y, aux, x, training)
         self.mark("inputs+packs")
         if self.levels is not None and training:
             self._run_levels(self.levels, lambda u: u.forward_steps(training))
@@ -541,6 +590,12 @@ class _Plan:
             u.backward(grads)
             if fine:
                 self.mark(f"  bwd {u.name}")
+        if self.y_units:                                 # p_y_in: d/d h_y is the [c_hz, ccat) slice of d/d p_in
+            if self.hy_one is not None:
+                L.check(lib.bp_repeat_samples_adjoint(C.byref(self.hy_slot.grad), self.L, C.byref(self.hy_one.grad), st),
+                        "sum d/d h_y over L")
+            for u in reversed(self.y_units):
+                u.backward(grads)
         L.check(lib.bp_latent_backward(C.byref(self.lat), C.byref(self.z.grad), L.ptr(self.stats4),
                                        L.ptr(self.eps), L.ptr(self.seed), float(self.model.beta_KL),
                                        C.byref(self.q_head.grad),
@@ -704,12 +759,15 @@ class CVAE(torch.nn.Module):
         else:
             raise NotImplementedError("Architecture {} not supported yet!".format(architecture["type"]))
 
+        # (p_y_in=None or an empty list is the identity, cvae.py:106)
+        self.has_p_y_in = self.p_y_in is not None and len(architecture["p_y_in"]) > 0
         self.min_z_var = architecture.get("min_z_var", 1e-7)
         self.likelihood_scaling = architecture.get("likelihood_scaling", 1.0)
         self.alpha_var = 1.0
         self.beta_KL = 1.0
         self.n_aux = 1
         self._plans = {}
+        self._paint_plans = {}
         self._graphs = {}
         self._eps_override = None
         self.to(self.device)
@@ -745,7 +803,7 @@ class CVAE(torch.nn.Module):
         """Run the weight gradients (and the independent q_y_in / prior branches) on their own streams beside the
         main chain (default), or everything serially on the main stream (``False``: every kernel has the GPU to
         itself, e.g. to time kernels)."""
-        for plan in self._plans.values():
+        for plan in list(self._plans.values()) + list(self._paint_plans.values()):
             plan.side = plan._side_stream if enabled else None
             plan.branch = plan._branch_streams if enabled else None
 
@@ -759,6 +817,7 @@ class CVAE(torch.nn.Module):
         if hasattr(self, "_flat_params"):
             self._flatten_parameters()
             self._plans = {}
+            self._paint_plans = {}
             self._graphs = {}
         return out
 
@@ -777,17 +836,28 @@ class CVAE(torch.nn.Module):
         self._plans[(n, want_g, want_q)] = plan
         return plan
 
+    def _paint_plan(self, n):
+        """The plan ``sample_P`` runs: one latent draw per input whatever ``L`` is (cvae.py:155 passes L=1 to P), no
+        recognition network, no gradients.  With L = 1 that is the cached plan every caller shares."""
+        if self.L == 1:
+            return self._plan(n, False, False)
+        plan = self._paint_plans.get(n)
+        if plan is None:
+            plan = self._paint_plans[n] = _Plan(self, n, False, False, samples=1)
+        return plan
+
     def cuda(self, device=None):
         return self
 
     # ---- reference API --------------------------------------------------------------------
-    def _draw_eps(self, n):
+    def _draw_eps(self, n, samples=None):
+        ls = self.L if samples is None else samples
         if self._eps_override is not None:
             e = torch.as_tensor(self._eps_override, device=self.device, dtype=torch.float32)
-            if tuple(e.shape) != (self.L, n, *self.dim_z):
-                raise ValueError(f"eps override has shape {tuple(e.shape)}, expected {(self.L, n, *self.dim_z)}")
+            if tuple(e.shape) != (ls, n, *self.dim_z):
+                raise ValueError(f"eps override has shape {tuple(e.shape)}, expected {(ls, n, *self.dim_z)}")
             return e
-        return torch.randn(size=(self.L, n, *self.dim_z), device=self.device)     # cvae.py:64
+        return torch.randn(size=(ls, n, *self.dim_z), device=self.device)     # cvae.py:64
 
     def _check_inputs(self, x, y):
         if y.dim() != 4 or tuple(y.shape[1:]) != self.dim_y:
@@ -842,13 +912,11 @@ class CVAE(torch.nn.Module):
             self._check_inputs(None, y)
             n = y.shape[0]
             aux = self._aux(aux_label, n)
-            if self.L != 1:
-                raise NotImplementedError("sample_P with L != 1")
-            plan = self._plan(n, False, False)
-            plan.load_inputs(y, aux)
+            plan = self._paint_plan(n)
+            plan.load_inputs(y, aux, training=self.training)
             if z is None:
                 plan.run_prior(self.training)
-                plan.run_latent(self._draw_eps(n), use_q=False)
+                plan.run_latent(self._draw_eps(n, plan.L), use_q=False)
             else:
                 zt = torch.as_tensor(z, device=self.device, dtype=torch.float32)
                 if tuple(zt.shape) != (n, *self.dim_z):
@@ -967,8 +1035,12 @@ class CVAE(torch.nn.Module):
               "out": None if pipeline else torch.zeros((n, cx, H, W), device=self.device),
               "z": torch.zeros((n, *self.dim_z), device=self.device) if given_z else None}
         if pipeline:
-            if self.L != 1 or self.prior_network is None:
-                raise NotImplementedError("the paint pipeline needs L = 1 and a prior network")
+            if scales is not None and self.has_p_y_in:
+                raise NotImplementedError("the captured paint pipeline has no split-scale load step for a p_y_in network "
+                                          "(bp_paint_load_scales2 writes two destinations); paint / paint_batch take it")
+            if self.L != 1:
+                raise NotImplementedError("the captured paint pipeline needs L = 1 (sample_P and paint take any L: they "
+                                          "paint with one latent draw per tile)")
             per_tile = self.dim_z[0] * self.dim_z[1] * self.dim_z[2]
             st["eps"] = torch.zeros((1, n, per_tile), device=self.device)
             # parameter block of a slot: one contiguous device buffer = one host-to-device copy per batch
@@ -997,11 +1069,11 @@ class CVAE(torch.nn.Module):
         while parts > 1 and (n % parts != 0 or n // parts < 8):
             parts -= 1
         h = n // parts
-        plans = [self._plan(h, False, False)] + [_Plan(self, h, False, False) for _ in range(parts - 1)]
+        plans = [self._paint_plan(h)] + [_Plan(self, h, False, False, samples=1) for _ in range(parts - 1)]
         st["plans"] = plans
         units = []
         for plan in plans:
-            for us in [plan.p_units] + plan.g_units + [plan.mu_units]:
+            for us in [plan.p_units] + plan.g_units + [plan.mu_units, plan.y_units]:
                 for u in us:
                     units += u.body if hasattr(u, "body") else [u]
         st["units"] = units
@@ -1053,8 +1125,15 @@ class CVAE(torch.nn.Module):
             auxp = L.ptr(sl["aux"][lo:lo + h]) if self.use_aux_label else None
             load, store = (lib.bp_paint_load2, lib.bp_paint_store) if modes is None else \
                 (functools.partial(lib.bp_paint_load2_mode, modes[0]), functools.partial(lib.bp_paint_store_mode, modes[1]))
-            L.check(load(L.ptr(sl["raw"][lo:lo + h]), cy, L.ptr(sl["xf_in"][lo:lo + h]), auxp, plan.caux,
-                         C.byref(plan.y2.view), C.byref(plan.hy_slot.view), sm), "paint load")
+            if plan.y_units:
+                # the transformed tile goes where the generator needs it: with a p_y_in network that is y2 alone
+                load1 = lib.bp_paint_load if modes is None else functools.partial(lib.bp_paint_load_mode, modes[0])
+                L.check(load1(L.ptr(sl["raw"][lo:lo + h]), cy, L.ptr(sl["xf_in"][lo:lo + h]), auxp, plan.caux,
+                              C.byref(plan.y2.view), sm), "paint load")
+                plan.run_y_net(False)
+            else:
+                L.check(load(L.ptr(sl["raw"][lo:lo + h]), cy, L.ptr(sl["xf_in"][lo:lo + h]), auxp, plan.caux,
+                             C.byref(plan.y2.view), C.byref(plan.hy_slot.view), sm), "paint load")
             plan.run_prior(False)
             eps = st["eps"][:, lo:lo + h]
             L.check(lib.bp_philox_normal_dev(L.ptr(sl["seed"]), L.ptr(sl["tile_ids"][lo:lo + h]), h, 1, eps.shape[-1],
@@ -1073,7 +1152,7 @@ class CVAE(torch.nn.Module):
                                                   C.byref(plan.z.view), _stream()), "z layout")
             else:
                 plan.run_prior(False)
-                plan.run_latent(torch.randn(size=(self.L, h, *self.dim_z), device=self.device), use_q=False)
+                plan.run_latent(torch.randn(size=(1, h, *self.dim_z), device=self.device), use_q=False)
             plan.run_generator(False)
             self._head_to_nchw(plan.mu_head, plan.mu_softplus, st["out"][lo:lo + h])
 
@@ -1098,7 +1177,8 @@ class CVAE(torch.nn.Module):
             graph = torch.cuda.CUDAGraph()
             # (thread-local capture: under data parallelism the process group's watchdog thread may query events
             #  while this thread captures; that is harmless and must not invalidate the capture)
-            with torch.no_grad(), torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):
+            with torch.no_grad(), capture_without_gc(), \
+                    torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):
                 run(sl)
             graphs.append(graph)
             if sl is not None:
@@ -1131,7 +1211,7 @@ class CVAE(torch.nn.Module):
         auxs = torch.zeros((n, self.n_aux), device=dev) if self.use_aux_label else None
         seed = torch.full((1,), -1.0, device=dev)            # d(loss)/d(ELBO), loss = -ELBO
         units = []
-        for us in plan.q_units + [plan.p_units] + plan.g_units + [plan.mu_units, plan.var_units]:
+        for us in plan.q_units + [plan.p_units] + plan.g_units + [plan.mu_units, plan.var_units, plan.y_units]:
             for u in us:
                 units += u.body if hasattr(u, "body") else [u]
 
@@ -1157,7 +1237,8 @@ class CVAE(torch.nn.Module):
             run()
         torch.cuda.current_stream(dev).wait_stream(side)
         graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):
+        with torch.no_grad(), capture_without_gc(), \
+                torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):
             run()
         with torch.no_grad():
             for t, k in zip((self._flat_params, optimizer.exp_avg, optimizer.exp_avg_sq), keep):

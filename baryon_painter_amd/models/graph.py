@@ -13,7 +13,9 @@ Conventions
   * every slot has at most two gradient contributions (``grad`` and ``grad2``), which the
     producer's backward adds while it applies the activation derivative.
 """
+import contextlib
 import ctypes as C
+import gc
 import os
 
 import torch
@@ -35,6 +37,24 @@ FUSED_FINALIZE = os.environ.get("BP_FUSED_FINALIZE", "1") != "0"
 
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+@contextlib.contextmanager
+def capture_without_gc():
+    """Around a stream capture: collect cyclic garbage first, then keep the collector off until the capture has ended.
+    A model and its plans reference each other, so a dropped model -- with its captured graphs and device buffers -- is
+    only freed by the cyclic collector, which runs whenever Python's allocation counters say so.  Inside a capture that
+    destroys a hipGraph and frees device memory from the capturing thread, which the runtime refuses there, and an error
+    in a destructor ends the process (seen as "Fatal Python error: Aborted" with a "Garbage-collecting" frame under
+    ``_capture_paint_graph``).  ``torch.cuda.graph`` itself no longer collects before it begins a capture."""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 # ------------------------------------------------------------------ parameter containers

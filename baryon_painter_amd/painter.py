@@ -375,12 +375,12 @@ class CVAEPainter(Painter):
 
     def can_paint_stream(self, z=0.0):
         """Whether ``paint_stream`` has a device form for this painter (one label field, one of the six range compressions
-        on either side, L = 1 and a prior network; single-channel tiles, or a split-scale transform in the orders
+        on either side and L = 1, with or without a prior network or a p_y_in network; single-channel tiles, or a split-scale transform in the orders
         ``_transform_parameters`` names whose levels are the model's dim_y[0] = dim_x[0]) -- WITHOUT side effects: nothing is
         captured, no random number is drawn.  ``lightcone.paint_plane`` asks this before it draws a plane's seed, so that
         a NotImplementedError raised later, from inside a capture, is an error and not a silent fall-back."""
         model = self.model
-        if getattr(model, "L", 1) != 1 or getattr(model, "prior_network", None) is None:
+        if getattr(model, "L", 1) != 1:         # (the captured pipeline only; paint / paint_batch take any L)
             return False
         try:
             scales = self._transform_parameters(np.atleast_1d(np.asarray(z, dtype=np.float64))[:1])[1]
@@ -388,6 +388,8 @@ class CVAEPainter(Painter):
             return False
         if scales is None:
             return model.dim_y[0] == 1
+        if getattr(model, "has_p_y_in", False):     # (no split-scale load step with one destination: CVAE.paint_graph)
+            return False
         levels = scales["n_scale"] + int(scales["include_original"])
         return model.dim_y[0] == levels and model.dim_x[0] == levels
 
@@ -398,6 +400,8 @@ class CVAEPainter(Painter):
             if cy != 1:
                 raise NotImplementedError(f"{what} single-channel input tiles (or a split-scale transform's levels)")
         else:
+            if getattr(self.model, "has_p_y_in", False):
+                raise NotImplementedError(f"{what} split-scale tiles only for models without a p_y_in network")
             levels = scales["n_scale"] + int(scales["include_original"])
             if cy != levels or cx != levels:
                 raise NotImplementedError(f"{what} dim_y[0] = dim_x[0] = {levels} for this split-scale transform, the "

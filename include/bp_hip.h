@@ -314,6 +314,15 @@ int bp_nchw_to_view(const float* src_nchw, int32_t c, const float* aux, int32_t 
 int bp_view_to_nchw(const bp_view* src, const bp_pointwise* pw, int32_t softplus, float* dst_nchw,
                     void* stream);
 int bp_fill(float* dst, int64_t n, float value, void* stream);
+/* h_y.repeat(L, 1, 1, 1) of cvae.py:109 and its adjoint, on channel-slice views (fp32; dst->n == L * src->n, same h, w, c):
+ *   bp_repeat_samples        : dst[l * n + m] = src[m] for l < L.  RAW values: a batch-norm / activation pending on
+ *                              the slice applies to every copy alike
+ *   bp_repeat_samples_adjoint: d_src[m] = ((d_dst[m] + d_dst[n + m]) + d_dst[2 n + m]) + ... in float32, ascending l:
+ *                              the same inputs give the same bits
+ * 16-byte accesses where c, both channel strides and both offsets are multiples of 4 and both bases 16-byte aligned,
+ * one float per access otherwise.  BP_EINVAL before anything is written for a malformed or bf16 view or L < 1. */
+int bp_repeat_samples(const bp_view* src, int32_t L, const bp_view* dst, void* stream);
+int bp_repeat_samples_adjoint(const bp_view* d_dst, int32_t L, const bp_view* d_src, void* stream);
 
 /* ---- paint() pipeline (painter.py:371-392 around cvae.py:149-162; utils/data_transforms.py:72-97) ----------------
  * The raw tile goes in, the physical tile comes out: the reference's "shift-log" range compression and its inverse
@@ -476,6 +485,10 @@ typedef struct bp_latent {
 
 /* q_raw / p_raw: raw head outputs (N,zh,zw,2*zc) with their pointwise (BN+ReLU); p_raw may be
  * NULL (no prior network: standard-normal prior).  eps: (L,N,zc,zh,zw) standard normal.
+ * q_raw NULL (then p_raw must be NULL too): sampling that standard-normal prior (cvae.py:83-85, 97-100): z_mu =
+ * z_log_var = 0, so z = eps * (1 + min_z_var), written as that one float32 product; stats4 and kl_sum are zero.  (The
+ * reference adds the zero mean, 0 + eps * sd, which turns eps = -0.0 into +0.0; the product keeps -0.0: the one value
+ * on which the two differ, and they compare equal.)
  * Outputs: stats4 (4,N,zc,zh,zw) = {z_mu, z_log_var, prior_mu, prior_log_var} (NCHW planes),
  * z (L*N, zh, zw, zc) view, kl_sum: one double = sum[...] of cvae.py:129-130 (un-normalised). */
 int bp_latent_forward(const bp_latent* lt, const bp_view* q_raw, const bp_pointwise* q_pw,
