@@ -21,13 +21,14 @@ import torch
 
 from .. import _lib as L
 from .arch import cgan_discriminator_architecture, cgan_generator_architecture
-from .graph import SNConv2d, Slot, build_holders, capture_without_gc, compile_sequential, _stream
+from .graph import PlanBase, SNConv2d, Slot, build_holders, compile_sequential, _stream
+from . import paint_graph as PG
 
 
-class _GanPlan:
+class _GanPlan(PlanBase):
     def __init__(self, model, n):
         self.model, self.lib, self.device, self.impl, self.sync = model, model._lib, model.device, L.IMPL_AUTO, model.sync
-        self.n, self.ws_bytes, self.ws, self.prof = n, 0, None, None
+        self.n, self.ws = n, None
         H, W = model.tile_size, model.tile_size
         dev = self.device
         self.y2 = Slot.new(n, H, W, 2, dev)
@@ -83,27 +84,6 @@ class _GanPlan:
         self.v_dfake = L.View(self.d_in_fake.grad_buf.data_ptr(), n, h_, w_, 1, di.cstride, 2)
         self.cnt_d = float(n * ds.h * ds.w)           # discriminator outputs per half
         self.cnt_px = float(n * H * W)
-
-    def need_ws(self, nbytes):
-        self.ws_bytes = max(self.ws_bytes, int(nbytes))
-
-    def impl_of(self, kind, unit=None):
-        return self.impl
-
-    def prof_begin(self):
-        """HIP events around every launch when ``self.prof`` is a list (bench / tools), as in cvae._Plan."""
-        if self.prof is None:
-            return None
-        e = torch.cuda.Event(enable_timing=True)
-        e.record()
-        return e
-
-    def prof_end(self, e0, unit, kind, nstreams=1):
-        if e0 is None:
-            return
-        e1 = torch.cuda.Event(enable_timing=True)
-        e1.record()
-        self.prof.append((e0, e1, unit, kind, nstreams))
 
     # ---- forward pieces
     def generate(self, y, zc, training):
@@ -173,9 +153,10 @@ class _GanPlan:
             torch.cuda.current_stream().wait_stream(self.side)     # every weight gradient is written
 
 
-class _GanPaintPlan:
+class _GanPaintPlan(PlanBase):
     """The generator alone, eval mode only: what painting needs of a ``_GanPlan``.  No discriminator units, no
-    ``prepare_backward`` (no gradient buffers, no weight-gradient workspace), no side stream, and the data-gradient
+    ``prepare_backward`` (no gradient buffers, no weight-gradient workspace), no workspace at all (batch-norm runs on its
+    running statistics: ``need_ws`` records the sizes and nothing is allocated), no side stream, and the data-gradient
     images of the packed weights are dropped.  The units are compiled exactly as ``_GanPlan`` compiles its generator
     (same names, same ``impl``), so the forward launches -- and the bits they produce -- are the same.
 
@@ -192,7 +173,7 @@ class _GanPaintPlan:
         if paint_dtype not in self.PAINT_DTYPES:
             raise ValueError(f"paint_dtype {paint_dtype!r}: one of {self.PAINT_DTYPES}")
         self.model, self.lib, self.device, self.impl, self.sync = model, model._lib, model.device, L.IMPL_AUTO, model.sync
-        self.n, self.ws_bytes, self.ws, self.prof = n, 0, None, None
+        self.n, self.ws = n, None
         self.paint_dtype = paint_dtype
         self._bf16_units, self._bf16_outs = self.bf16_policy(model.g_arch) if paint_dtype == "bf16" else ((), ())
         H, W = model.tile_size, model.tile_size
@@ -204,9 +185,7 @@ class _GanPaintPlan:
         if gs.shape() != (n, H, W, 1) or gs.pw is not None:
             raise ValueError(f"generator output {gs.shape()}")
         self.g_units, self.g_raw = gu, gs
-        self.units = []
-        for u in gu:
-            self.units += u.body if hasattr(u, "body") else [u]
+        self.units = self.flat_units(gu)
         for u in self.units:
             u.packed_bwd = None                   # (maybe_pack skips a direction that has no image)
         for u in self.units:
@@ -237,18 +216,6 @@ class _GanPaintPlan:
 
     def bf16_out(self, name):
         return self._named(name, self._bf16_outs)
-
-    def need_ws(self, nbytes):                    # (the eval forward uses no workspace: batch-norm runs on its running
-        self.ws_bytes = max(self.ws_bytes, int(nbytes))     # statistics; the sizes are recorded and nothing is allocated)
-
-    def impl_of(self, kind, unit=None):
-        return self.impl
-
-    def prof_begin(self):
-        return None
-
-    def prof_end(self, e0, unit, kind, nstreams=1):
-        return
 
     def forward(self):
         for u in self.g_units:
@@ -421,25 +388,10 @@ class CGAN(torch.nn.Module):
         H = W = self.tile_size
         dev = self.device
         plan = self._paint_plan(n)
-        layout, off = {}, 0
-        for name, dt, shape in (("xf_in", torch.float64, (n, 3)), ("xf_out", torch.float64, (n, 3)),
-                                ("tile_ids", torch.int64, (n,)), ("seed", torch.int64, (1,)),
-                                ("aux", torch.float32, (n, 1))):
-            layout[name] = (off, dt, shape)
-            nb = int(torch.tensor([], dtype=dt).element_size()) * int(torch.Size(shape).numel())
-            off += (nb + 7) // 8 * 8
-        st = {"block_layout": layout, "block_bytes": off, "plan": plan, "units": plan.units}
-
-        def new_slot():
-            sl = {"raw": torch.zeros((n, 1, H, W), device=dev), "out": torch.zeros((n, 1, H, W), device=dev),
-                  "block": torch.zeros(off, device=dev, dtype=torch.uint8)}
-            for name, (o, dt, shape) in layout.items():
-                nb = int(torch.tensor([], dtype=dt).element_size()) * int(torch.Size(shape).numel())
-                sl[name] = sl["block"][o:o + nb].view(dt).view(shape)
-            sl["xf_in"].fill_(1.0)
-            sl["xf_out"].fill_(1.0)
-            return sl
-        st["slots"] = [new_slot(), new_slot()]
+        block = PG.ParamBlock(PG.paint_fields(n, 3))
+        st = {"param_block": block, "block_layout": block.layout, "block_bytes": block.nbytes, "plan": plan,
+              "units": plan.units,
+              "slots": [PG.new_slot((n, 1, H, W), (n, 1, H, W), block, dev) for _ in range(2)]}
 
         def run(sl):
             lib, sm = self._lib, _stream()
@@ -449,17 +401,7 @@ class CGAN(torch.nn.Module):
             L.check(lib.bp_paint_store_cam(C.byref(plan.g_raw.view), L.ptr(sl["xf_out"]), L.ptr(sl["out"]), sm),
                     "paint store")
 
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side), torch.no_grad():
-            run(st["slots"][0])                   # warm-up outside capture (packs weights, batch-norm scale / shift)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        for sl in st["slots"]:
-            graph = torch.cuda.CUDAGraph()
-            with torch.no_grad(), capture_without_gc(), \
-                    torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):
-                run(sl)
-            sl["graph"] = graph
+        PG.capture(run, st["slots"], dev)
         return st
 
     def train_step(self, x, y, z, opt_g, opt_d, capture=None):

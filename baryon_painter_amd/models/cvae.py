@@ -19,13 +19,13 @@ import torch
 
 from .. import _lib as L
 from .arch import conv_block, conv_down, conv_up, res_block  # noqa: F401  (reference: ``from .utils import *``)
-from .graph import (PW, ConvUnit, PackBatch, Slot, build_holders, capture_without_gc, compile_sequential, probe_output,
-                    _stream)
+from .graph import PW, ConvUnit, PackBatch, PlanBase, Slot, build_holders, compile_sequential, probe_output, _stream
+from . import paint_graph as PG
 
 pi = math.pi
 
 
-class _Plan:
+class _Plan(PlanBase):
     """All device buffers and the launch schedule for one (batch, mode) signature."""
 
     def __init__(self, model, n, with_grad, with_q=True, samples=None):
@@ -190,7 +190,7 @@ class _Plan:
         self.deferring = False
         self.defer_reduce = with_grad and os.environ.get("BP_DEFER_REDUCE", "1") != "0"
         if self.defer_reduce:
-            for u in self._flat([u for us in self.q_units for u in us] + list(self.p_units) + list(self.y_units)
+            for u in self.flat_units([u for us in self.q_units for u in us] + list(self.p_units) + list(self.y_units)
                                 + [u for us in self.g_units for u in us] + list(self.mu_units) + list(self.var_units)):
                 # (BP_DEFER_MAX_MB: layers with larger partial sums reduce at once.  Measured: deferring ALL fp32 layers,
                 #  the trunk's 16 MB and the encoder layer's 25 MB of partial sums included, is best -- 41.3 vs 41.6 ms
@@ -203,7 +203,7 @@ class _Plan:
             self.ws2 = torch.zeros_like(self.ws)
         # q_x_in, q_y_in and the prior network are independent chains of small kernels (none fills the GPU):
         # q_y_in and the prior run on their own streams, each with its own reduction workspace
-        all_units = self._flat([u for us in self.q_units for u in us] + list(self.p_units) + list(self.y_units)
+        all_units = self.flat_units([u for us in self.q_units for u in us] + list(self.p_units) + list(self.y_units)
                                + [u for us in self.g_units for u in us] + list(self.mu_units) + list(self.var_units))
         # p_y_in does not depend on the latent: in a training plan it runs on the weight-gradient stream (idle during the
         # forward pass) beside the recognition / prior networks, with a reduction workspace of its own.  Not with global
@@ -211,9 +211,9 @@ class _Plan:
         self.y_beside = bool(self.y_units) and self.side is not None and not (model.sync is not None and model.sync.sync_bn)
         if self.y_beside:
             self.ws_y = torch.zeros_like(self.ws)
-            for u in self._flat(self.y_units):
+            for u in self.flat_units(self.y_units):
                 u.ws_name = "ws_y"
-        for u in self._flat([u for us in self.g_units for u in us] + list(self.mu_units) + list(self.var_units)):
+        for u in self.flat_units([u for us in self.g_units for u in us] + list(self.mu_units) + list(self.var_units)):
             u.pack_late = True              # (graph.PackBatch: nothing in front of run_generator reads their weights)
         self.pack_batch = PackBatch(self, [u for u in all_units if isinstance(u, ConvUnit)])
         # Under data parallelism the recognition branches and the prior network advance level by level and share ONE
@@ -234,9 +234,9 @@ class _Plan:
                 and (not sync_bn or peer_stats):
             self.branch = self._branch_streams = [torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)]
             self.ws_b, self.ws_c = torch.zeros_like(self.ws), torch.zeros_like(self.ws)
-            for u in self._flat(self.q_units[1]):
+            for u in self.flat_units(self.q_units[1]):
                 u.ws_name = "ws_b"
-            for u in self._flat(self.p_units):
+            for u in self.flat_units(self.p_units):
                 u.ws_name = "ws_c"
 
         # The weight gradients of the q_y_in / prior branches get streams of their own: nine small launches that would
@@ -245,9 +245,9 @@ class _Plan:
         # main stream.
         if self.side is not None and self.q_units and self.p_units and os.environ.get("BP_BRANCH_SIDE", "1") != "0":
             self.side_branch = {k: (torch.cuda.Stream(device=dev), torch.zeros_like(self.ws)) for k in ("b", "c")}
-            for u in self._flat(self.q_units[1]):
+            for u in self.flat_units(self.q_units[1]):
                 u.side_name = "b"
-            for u in self._flat(self.p_units):
+            for u in self.flat_units(self.p_units):
                 u.side_name = "c"
 
     # ---- bf16 policy (dtype="bf16", BASELINE.json configs[3]).  The generator trunk p_y_z_in and the first two layers
@@ -267,16 +267,6 @@ class _Plan:
         return self.bf16 and (name.startswith("p_y_z_in.") or (self._HEAD_TAIL and name in ("p_mu_out.0", "p_var_out.0")))
 
     # ---- helpers
-    @staticmethod
-    def _flat(units):
-        out = []
-        for u in units:
-            out += u.body if hasattr(u, "body") else [u]
-        return out
-
-    def need_ws(self, nbytes):
-        self.ws_bytes = max(self.ws_bytes, int(nbytes))
-
     side_branch = None
 
     def side_of(self, unit):
@@ -295,23 +285,6 @@ class _Plan:
         if only and unit is not None and unit not in only.split(","):
             v = None
         return self.impl if v is None else {"auto": L.IMPL_AUTO, "direct": L.IMPL_DIRECT, "mfma": L.IMPL_MFMA}[v]
-
-    # per-launch HIP-event timing of the convolution kernels (bench.py roofline); off by default
-    prof = None
-
-    def prof_begin(self):
-        if self.prof is None:
-            return None
-        e = torch.cuda.Event(enable_timing=True)
-        e.record()
-        return e
-
-    def prof_end(self, e0, unit, kind, nstreams=1):
-        if e0 is None:
-            return
-        e1 = torch.cuda.Event(enable_timing=True)
-        e1.record()
-        self.prof.append((e0, e1, unit, kind, nstreams))
 
     @staticmethod
     def _no_trailing(tr, where):
@@ -1025,15 +998,16 @@ class CVAE(torch.nn.Module):
         stream)."""
         cy, H, W = self.dim_y
         cx = self.dim_x[0]
+        dev = self.device
         if scales is not None:
             levels = scales["n_scale"] + int(scales["include_original"])
             if not pipeline or cy != levels or cx != levels:
                 raise ValueError(f"a {levels}-level split-scale transform needs dim_y[0] = dim_x[0] = {levels}, the "
                                  f"model has {cy} and {cx}")
-        st = {"y": None if pipeline else torch.zeros((n, cy, H, W), device=self.device),
-              "aux": torch.zeros((n, self.n_aux), device=self.device) if self.use_aux_label and not pipeline else None,
-              "out": None if pipeline else torch.zeros((n, cx, H, W), device=self.device),
-              "z": torch.zeros((n, *self.dim_z), device=self.device) if given_z else None}
+        st = {"y": None if pipeline else torch.zeros((n, cy, H, W), device=dev),
+              "aux": torch.zeros((n, self.n_aux), device=dev) if self.use_aux_label and not pipeline else None,
+              "out": None if pipeline else torch.zeros((n, cx, H, W), device=dev),
+              "z": torch.zeros((n, *self.dim_z), device=dev) if given_z else None}
         if pipeline:
             if scales is not None and self.has_p_y_in:
                 raise NotImplementedError("the captured paint pipeline has no split-scale load step for a p_y_in network "
@@ -1042,42 +1016,22 @@ class CVAE(torch.nn.Module):
                 raise NotImplementedError("the captured paint pipeline needs L = 1 (sample_P and paint take any L: they "
                                           "paint with one latent draw per tile)")
             per_tile = self.dim_z[0] * self.dim_z[1] * self.dim_z[2]
-            st["eps"] = torch.zeros((1, n, per_tile), device=self.device)
+            st["eps"] = torch.zeros((1, n, per_tile), device=dev)
             # parameter block of a slot: one contiguous device buffer = one host-to-device copy per batch
-            layout, off = {}, 0
-            xw = 2 if modes is None else 4
-            for name, dt, shape in (("xf_in", torch.float64, (n, xw)), ("xf_out", torch.float64, (n, xw)),
-                                    ("tile_ids", torch.int64, (n,)), ("seed", torch.int64, (1,)),
-                                    ("aux", torch.float32, (n, max(self.n_aux, 1)))):
-                layout[name] = (off, dt, shape)
-                nb = int(torch.tensor([], dtype=dt).element_size()) * int(torch.Size(shape).numel())
-                off += (nb + 7) // 8 * 8
-            st["block_layout"], st["block_bytes"] = layout, off
-
-            def new_slot():
-                sl = {"raw": torch.zeros((n, 1 if scales is not None else cy, H, W), device=self.device),
-                      "out": torch.zeros((n, 1 if scales is not None else cx, H, W), device=self.device),
-                      "block": torch.zeros(off, device=self.device, dtype=torch.uint8)}
-                for name, (o, dt, shape) in layout.items():
-                    nb = int(torch.tensor([], dtype=dt).element_size()) * int(torch.Size(shape).numel())
-                    sl[name] = sl["block"][o:o + nb].view(dt).view(shape)
-                sl["xf_in"].fill_(1.0)
-                sl["xf_out"].fill_(1.0)
-                return sl
-            st["slots"] = [new_slot(), new_slot()]
+            block = PG.ParamBlock(PG.paint_fields(n, 2 if modes is None else 4, max(self.n_aux, 1)))
+            st["param_block"], st["block_layout"], st["block_bytes"] = block, block.layout, block.nbytes
+            st["slots"] = [PG.new_slot((n, 1 if scales is not None else cy, H, W),
+                                       (n, 1 if scales is not None else cx, H, W), block, dev) for _ in range(2)]
         parts = int(os.environ.get("BP_PAINT_STREAMS", "4"))
         while parts > 1 and (n % parts != 0 or n // parts < 8):
             parts -= 1
         h = n // parts
         plans = [self._paint_plan(h)] + [_Plan(self, h, False, False, samples=1) for _ in range(parts - 1)]
         st["plans"] = plans
-        units = []
-        for plan in plans:
-            for us in [plan.p_units] + plan.g_units + [plan.mu_units, plan.y_units]:
-                for u in us:
-                    units += u.body if hasattr(u, "body") else [u]
-        st["units"] = units
-        others = [torch.cuda.Stream(device=self.device) for _ in range(parts - 1)]
+        st["units"] = PlanBase.flat_units([u for plan in plans
+                                           for us in [plan.p_units] + plan.g_units + [plan.mu_units, plan.y_units]
+                                           for u in us])
+        others = [torch.cuda.Stream(device=dev) for _ in range(parts - 1)]
         if scales is not None:
             import numpy as np
             from ..utils import data_transforms as T
@@ -1087,61 +1041,63 @@ class CVAE(torch.nn.Module):
             ws = int(self._lib.bp_split_scale_workspace(h, H, W))
             sc = {"n_scale": scales["n_scale"], "include_original": int(scales["include_original"]),
                   "radii": (C.c_int32 * len(radii))(*radii), "ws": ws,
-                  "weights": torch.from_numpy(np.ascontiguousarray(wts, np.float64)).to(self.device)
-                  if len(wts) else torch.zeros(1, dtype=torch.float64, device=self.device),
+                  "weights": torch.from_numpy(np.ascontiguousarray(wts, np.float64)).to(dev)
+                  if len(wts) else torch.zeros(1, dtype=torch.float64, device=dev),
                   # one scratch per stream of the graph; the two slots replay on one stream and share them
-                  "scratch": [torch.empty(max(ws // 4, 1), device=self.device) for _ in range(parts)]}
+                  "scratch": [torch.empty(max(ws // 4, 1), device=dev) for _ in range(parts)]}
             st["scales"] = sc
             for sl in st["slots"]:
                 sl["scratch"], sl["weights"] = sc["scratch"], sc["weights"]
 
-        def paint_pipeline_scales(plan, lo, sl):
-            lib, sm = self._lib, _stream()
-            plan.pack_all()
-            auxp = L.ptr(sl["aux"][lo:lo + h]) if self.use_aux_label else None
-            scratch = sc["scratch"][lo // h]
-            load, store = (lib.bp_paint_load_scales2, lib.bp_paint_store_scales) if modes is None else \
-                (functools.partial(lib.bp_paint_load_scales2_mode, modes[0]),
-                 functools.partial(lib.bp_paint_store_scales_mode, modes[1]))
-            L.check(load(L.ptr(sl["raw"][lo:lo + h]), L.ptr(sl["xf_in"][lo:lo + h]), auxp,
-                         plan.caux, sc["n_scale"], sc["include_original"], L.ptr(sc["weights"]),
-                         sc["radii"], L.ptr(scratch), sc["ws"], C.byref(plan.y2.view),
-                         C.byref(plan.hy_slot.view), sm), "paint load (scales)")
-            plan.run_prior(False)
-            eps = st["eps"][:, lo:lo + h]
-            L.check(lib.bp_philox_normal_dev(L.ptr(sl["seed"]), L.ptr(sl["tile_ids"][lo:lo + h]), h, 1, eps.shape[-1],
-                                             L.ptr(eps), sm), "philox")
-            plan.run_latent(eps.reshape(1, h, *self.dim_z), use_q=False)
-            plan.run_generator(False)
-            L.check(store(C.byref(plan.mu_head.view), None, 1 if plan.mu_softplus else 0,
-                          sc["include_original"], L.ptr(sl["xf_out"][lo:lo + h]),
-                          L.ptr(sl["out"][lo:lo + h]), sm), "paint store (scales)")
+        if pipeline:
+            # The load and store steps of this capture, chosen once: the legacy shift-log entry points (two-double rows)
+            # or, with ``modes``, their ``_mode`` forms, which hold the mode as a constant of the graph.
+            lib, y_net = self._lib, bool(plans[0].y_units)
+
+            def entry(name, mode):
+                return getattr(lib, name) if modes is None else functools.partial(getattr(lib, name + "_mode"), mode)
+            m_in, m_out = modes if modes is not None else (None, None)
+            if scales is not None:
+                what = " (scales)"
+                load_fn, store_fn = entry("bp_paint_load_scales2", m_in), entry("bp_paint_store_scales", m_out)
+
+                def load(plan, lo, raw, xf, auxp, sm):
+                    return load_fn(raw, xf, auxp, plan.caux, sc["n_scale"], sc["include_original"], L.ptr(sc["weights"]),
+                                   sc["radii"], L.ptr(sc["scratch"][lo // h]), sc["ws"], C.byref(plan.y2.view),
+                                   C.byref(plan.hy_slot.view), sm)
+
+                def store(plan, xf, out, sm):
+                    return store_fn(C.byref(plan.mu_head.view), None, 1 if plan.mu_softplus else 0,
+                                    sc["include_original"], xf, out, sm)
+            else:
+                what = ""
+                # the transformed tile goes where the generator needs it: with a p_y_in network that is y2 alone
+                # (bp_paint_load, then the network), without one y2 and the generator's input (bp_paint_load2)
+                load_fn = entry("bp_paint_load" if y_net else "bp_paint_load2", m_in)
+                store_fn = entry("bp_paint_store", m_out)
+
+                def load(plan, lo, raw, xf, auxp, sm):
+                    dst = (C.byref(plan.y2.view),) if y_net else (C.byref(plan.y2.view), C.byref(plan.hy_slot.view))
+                    return load_fn(raw, cy, xf, auxp, plan.caux, *dst, sm)
+
+                def store(plan, xf, out, sm):
+                    return store_fn(C.byref(plan.mu_head.view), None, 1 if plan.mu_softplus else 0, xf, out, sm)
 
         def paint_pipeline(plan, lo, sl):
-            if scales is not None:
-                return paint_pipeline_scales(plan, lo, sl)
-            lib, sm = self._lib, _stream()
+            sm = _stream()
             plan.pack_all()
             auxp = L.ptr(sl["aux"][lo:lo + h]) if self.use_aux_label else None
-            load, store = (lib.bp_paint_load2, lib.bp_paint_store) if modes is None else \
-                (functools.partial(lib.bp_paint_load2_mode, modes[0]), functools.partial(lib.bp_paint_store_mode, modes[1]))
-            if plan.y_units:
-                # the transformed tile goes where the generator needs it: with a p_y_in network that is y2 alone
-                load1 = lib.bp_paint_load if modes is None else functools.partial(lib.bp_paint_load_mode, modes[0])
-                L.check(load1(L.ptr(sl["raw"][lo:lo + h]), cy, L.ptr(sl["xf_in"][lo:lo + h]), auxp, plan.caux,
-                              C.byref(plan.y2.view), sm), "paint load")
+            L.check(load(plan, lo, L.ptr(sl["raw"][lo:lo + h]), L.ptr(sl["xf_in"][lo:lo + h]), auxp, sm),
+                    "paint load" + what)
+            if y_net:
                 plan.run_y_net(False)
-            else:
-                L.check(load(L.ptr(sl["raw"][lo:lo + h]), cy, L.ptr(sl["xf_in"][lo:lo + h]), auxp, plan.caux,
-                             C.byref(plan.y2.view), C.byref(plan.hy_slot.view), sm), "paint load")
             plan.run_prior(False)
             eps = st["eps"][:, lo:lo + h]
-            L.check(lib.bp_philox_normal_dev(L.ptr(sl["seed"]), L.ptr(sl["tile_ids"][lo:lo + h]), h, 1, eps.shape[-1],
-                                             L.ptr(eps), sm), "philox")
+            L.check(self._lib.bp_philox_normal_dev(L.ptr(sl["seed"]), L.ptr(sl["tile_ids"][lo:lo + h]), h, 1,
+                                                   eps.shape[-1], L.ptr(eps), sm), "philox")
             plan.run_latent(eps.reshape(1, h, *self.dim_z), use_q=False)
             plan.run_generator(False)
-            L.check(store(C.byref(plan.mu_head.view), None, 1 if plan.mu_softplus else 0,
-                          L.ptr(sl["xf_out"][lo:lo + h]), L.ptr(sl["out"][lo:lo + h]), sm), "paint store")
+            L.check(store(plan, L.ptr(sl["xf_out"][lo:lo + h]), L.ptr(sl["out"][lo:lo + h]), sm), "paint store" + what)
 
         def paint(plan, lo, sl):
             if pipeline:
@@ -1152,12 +1108,12 @@ class CVAE(torch.nn.Module):
                                                   C.byref(plan.z.view), _stream()), "z layout")
             else:
                 plan.run_prior(False)
-                plan.run_latent(torch.randn(size=(1, h, *self.dim_z), device=self.device), use_q=False)
+                plan.run_latent(torch.randn(size=(1, h, *self.dim_z), device=dev), use_q=False)
             plan.run_generator(False)
             self._head_to_nchw(plan.mu_head, plan.mu_softplus, st["out"][lo:lo + h])
 
         def run(sl=None):
-            main = torch.cuda.current_stream(self.device)
+            main = torch.cuda.current_stream(dev)
             for k, s2 in enumerate(others):
                 s2.wait_stream(main)
                 with torch.cuda.stream(s2):
@@ -1166,24 +1122,7 @@ class CVAE(torch.nn.Module):
             for s2 in others:
                 main.wait_stream(s2)
 
-        side = torch.cuda.Stream(device=self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        slots = st.get("slots", [None])
-        with torch.cuda.stream(side), torch.no_grad():
-            run(slots[0])                         # warm-up outside capture (packs weights, sizes workspaces)
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        graphs = []
-        for sl in slots:
-            graph = torch.cuda.CUDAGraph()
-            # (thread-local capture: under data parallelism the process group's watchdog thread may query events
-            #  while this thread captures; that is harmless and must not invalidate the capture)
-            with torch.no_grad(), capture_without_gc(), \
-                    torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):
-                run(sl)
-            graphs.append(graph)
-            if sl is not None:
-                sl["graph"] = graph
-        st["graph"] = graphs[0]
+        st["graph"] = PG.capture(run, st.get("slots", [None]), dev)[0]
         return st
 
     # ---- the whole training step as one hipGraph (small minibatches are launch-bound: ~450 launches per step)
@@ -1210,10 +1149,8 @@ class CVAE(torch.nn.Module):
         ys = torch.zeros((n, cy, H, W), device=dev)
         auxs = torch.zeros((n, self.n_aux), device=dev) if self.use_aux_label else None
         seed = torch.full((1,), -1.0, device=dev)            # d(loss)/d(ELBO), loss = -ELBO
-        units = []
-        for us in plan.q_units + [plan.p_units] + plan.g_units + [plan.mu_units, plan.var_units, plan.y_units]:
-            for u in us:
-                units += u.body if hasattr(u, "body") else [u]
+        units = plan.flat_units([u for us in plan.q_units + [plan.p_units] + plan.g_units
+                                 + [plan.mu_units, plan.var_units, plan.y_units] for u in us])
 
         holder = {}
 
@@ -1231,15 +1168,7 @@ class CVAE(torch.nn.Module):
         keep = [t.clone() for t in (self._flat_params, optimizer.exp_avg, optimizer.exp_avg_sq)]
         bufs = [(b, b.clone()) for b in self.buffers()]
         optimizer.upload_hyper(max(optimizer.n_steps, 1))
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side), torch.no_grad():
-            run()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), capture_without_gc(), \
-                torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):
-            run()
+        graph, = PG.capture(lambda _: run(), [None], dev)
         with torch.no_grad():
             for t, k in zip((self._flat_params, optimizer.exp_avg, optimizer.exp_avg_sq), keep):
                 t.copy_(k)

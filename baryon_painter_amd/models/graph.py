@@ -283,6 +283,50 @@ class Slot:
         self.grad2 = view
 
 
+class PlanBase:
+    """What ``ConvUnit`` / ``compile_sequential`` ask of a plan besides its ``model``, ``lib``, ``device``, ``impl`` and
+    ``sync``: the workspace size, the kernel family, per-launch timing and the bf16 policy.  A plan overrides what
+    differs (cvae._Plan, cgan._GanPlan, cgan._GanPaintPlan)."""
+
+    ws_bytes = 0
+    # per-launch HIP-event timing of the convolution kernels (bench.py roofline, tools); off unless set to a list
+    prof = None
+
+    def need_ws(self, nbytes):
+        self.ws_bytes = max(self.ws_bytes, int(nbytes))
+
+    def impl_of(self, kind, unit=None):
+        return self.impl
+
+    def prof_begin(self):
+        if self.prof is None:
+            return None
+        e = torch.cuda.Event(enable_timing=True)
+        e.record()
+        return e
+
+    def prof_end(self, e0, unit, kind, nstreams=1):
+        if e0 is None:
+            return
+        e1 = torch.cuda.Event(enable_timing=True)
+        e1.record()
+        self.prof.append((e0, e1, unit, kind, nstreams))
+
+    def bf16_unit(self, name):
+        return False
+
+    def bf16_out(self, name):
+        return False
+
+    @staticmethod
+    def flat_units(units):
+        """``units`` with every residual block replaced by the units of its body."""
+        out = []
+        for u in units:
+            out += u.body if hasattr(u, "body") else [u]
+        return out
+
+
 class ConvUnit:
     """conv / transp conv [+ batchnorm] [+ relu | leaky relu | prelu]  (utils.py:128-147)."""
 

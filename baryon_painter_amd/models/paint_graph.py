@@ -1,0 +1,79 @@
+"""The slot format and the capture of the device paint paths (``CVAE.paint_graph``, ``CGAN.paint_graph``).
+
+A captured paint pipeline has two *slots*: input / parameter / output buffer sets, each with its own graph over the same
+launch plans.  A slot's per-batch parameters live in ONE uint8 device buffer, its *parameter block*, so that a batch
+costs one host-to-device copy; ``ParamBlock`` is the byte layout of that buffer and the typed views over it, on the
+device and on a pinned host mirror (``painter._paint_stream_pipeline`` / ``_paint_plane_pipeline``).  A model states the
+fields of its block, its buffers and what one replay runs; everything else about a slot and a capture is here.
+"""
+import torch
+
+from .graph import capture_without_gc
+
+
+class ParamBlock:
+    """Byte layout of ``fields``, an ordered list of (name, torch dtype, shape), each rounded up to 8 bytes:
+    ``layout`` name -> (byte offset, dtype, shape) and ``nbytes``.  Needs no GPU."""
+
+    def __init__(self, fields):
+        self.layout, self._size, off = {}, {}, 0
+        for name, dt, shape in fields:
+            shape = tuple(shape)
+            self.layout[name] = (off, dt, shape)
+            self._size[name] = int(torch.tensor([], dtype=dt).element_size()) * int(torch.Size(shape).numel())
+            off += (self._size[name] + 7) // 8 * 8
+        self.nbytes = off
+
+    def views(self, buf):
+        """name -> typed view of the uint8 tensor ``buf`` (``nbytes`` long): torch views of a device buffer, NumPy views
+        of a host buffer.  The views alias ``buf``."""
+        if buf.dtype != torch.uint8 or buf.dim() != 1 or buf.numel() != self.nbytes:
+            raise ValueError(f"a parameter block is a flat uint8 tensor of {self.nbytes} bytes")
+        out = {}
+        for name, (off, dt, shape) in self.layout.items():
+            v = buf[off:off + self._size[name]].view(dt).view(shape)
+            out[name] = v if buf.is_cuda else v.numpy()
+        return out
+
+
+def paint_fields(n, xf_width, aux_width=1):
+    """The fields of a paint pipeline's block for batches of ``n`` tiles: ``xf_in`` / ``xf_out`` (n, xf_width) float64
+    parameter rows of the transform and its inverse, ``tile_ids`` (n,) int64, ``seed`` (1,) int64 Philox key, ``aux``
+    (n, aux_width) float32 value of the conditioning plane.  Both models carry all five, so that one caller fills either
+    model's block."""
+    return [("xf_in", torch.float64, (n, xf_width)), ("xf_out", torch.float64, (n, xf_width)),
+            ("tile_ids", torch.int64, (n,)), ("seed", torch.int64, (1,)), ("aux", torch.float32, (n, aux_width))]
+
+
+def new_slot(raw_shape, out_shape, block, device):
+    """One slot: ``raw``, ``out``, the uint8 ``block`` and its named views, ``xf_in`` / ``xf_out`` filled with 1.0 (a
+    valid transform for the warm-up)."""
+    sl = {"raw": torch.zeros(raw_shape, device=device), "out": torch.zeros(out_shape, device=device),
+          "block": torch.zeros(block.nbytes, device=device, dtype=torch.uint8)}
+    sl.update(block.views(sl["block"]))
+    sl["xf_in"].fill_(1.0)
+    sl["xf_out"].fill_(1.0)
+    return sl
+
+
+def capture(run, slots, device):
+    """``run(slots[0])`` once outside capture on a side stream (packs weights, sizes workspaces), then one graph per
+    slot, captured on that stream in the order of ``slots``; a slot that is a dict gets its graph as ``"graph"``.
+    Returns the graphs.  ``slots`` is ``[None]`` where what is captured has no slots."""
+    side = torch.cuda.Stream(device=device)
+    side.wait_stream(torch.cuda.current_stream(device))
+    with torch.cuda.stream(side), torch.no_grad():
+        run(slots[0])
+    torch.cuda.current_stream(device).wait_stream(side)
+    graphs = []
+    for sl in slots:
+        graph = torch.cuda.CUDAGraph()
+        # (thread-local capture: under data parallelism the process group's watchdog thread may query events
+        #  while this thread captures; that is harmless and must not invalidate the capture)
+        with torch.no_grad(), capture_without_gc(), \
+                torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):
+            run(sl)
+        graphs.append(graph)
+        if sl is not None:
+            sl["graph"] = graph
+    return graphs

@@ -39,6 +39,67 @@ class Painter:
     def paint(self, input, **kwargs):
         raise NotImplementedError("This is an abstract base class.")
 
+    # ---- device paint paths, shared by the painters whose model has a ``paint_graph`` (CVAEPainter, CGANPainter).  A
+    # painter supplies ``_tile_shape()`` -> (H, W), ``_shape_mismatch(shape)`` -> the message for tiles of another shape,
+    # and ``_device_paint_parameters(zs)`` -> (params, scales, modes) of ``_paint_stream_pipeline`` for tiles at
+    # redshifts ``zs``, NotImplementedError where the painter has no device form (raised before any capture).
+    def release_paint_buffers(self):
+        """Free what the device paint paths keep between calls: ``paint_stream``'s page-locked host staging buffers -- two
+        parameter blocks plus up to four (batch, 1, H, W) fp32 buffers, 256 MiB of pinned memory at batch 64 of 512^2
+        tiles, which otherwise live as long as the painter (page-locking them costs tens of milliseconds per call, hence
+        the cache) -- and ``_paint_plane_device``'s accumulators and scratch."""
+        self.__dict__.pop("_paint_host_buffers", None)
+        self.__dict__.pop("_plane_device_buffers", None)
+
+    def paint_stream(self, inputs, z, batch_size=64, tile_ids=None, seed=0, rank=0, world_size=1, out=None):
+        """Paint MANY raw tiles: ``inputs`` (N, H, W) float32 host array (NumPy, memory map, or a pinned torch tensor),
+        redshifts ``z`` (scalar or (N,)) -> (N, H, W) float32 physical tiles.  The production form of ``paint``
+        (process_SLICS.py:201-218 calls it tile by tile):
+
+          * the transform and its inverse run on the device, fused into the layout kernels on either side of the
+            network (``bp_paint_load`` / ``bp_paint_store`` and their kin), bit-compatible with the host transforms;
+          * batches of ``batch_size`` tiles replay ONE captured hipGraph (``model.paint_graph``);
+          * host->device and device->host copies go through pinned double buffers on their own streams, so that
+            batch b+1 is uploaded and batch b-1 downloaded while batch b is painted;
+          * a CVAE's prior noise of tile i comes from a counter-based generator keyed on (``seed``, ``tile_ids[i]``
+            [default: i], int64), so the result does not depend on ``batch_size`` or on how tiles are dealt to ranks;
+            the seed travels in the per-batch parameter block: one captured graph serves every seed;
+          * ``rank`` / ``world_size``: this process paints the contiguous block of tiles that is its share (one
+            process per GPU, no collective: tiles are independent) and returns (block, (lo, hi))."""
+        model = self.model
+        model.train(False)
+        H, W = self._tile_shape()
+        N = len(inputs)
+        if tuple(inputs.shape[1:]) != (H, W):
+            raise ValueError(self._shape_mismatch(tuple(inputs.shape)))
+        zs = np.broadcast_to(np.asarray(z, dtype=np.float64), (N,))
+        ids = np.arange(N, dtype=np.int64) if tile_ids is None else np.asarray(tile_ids, dtype=np.int64)
+        per = (N + world_size - 1) // world_size
+        lo, hi = min(rank * per, N), min((rank + 1) * per, N)
+        params, scales, modes = self._device_paint_parameters(zs[lo:hi])     # (NotImplementedError before any capture)
+        result = _paint_stream_pipeline(self, model, inputs, (H, W), lo, hi, int(batch_size), params, ids[lo:hi], seed,
+                                        out, scales, modes)
+        return (result, (lo, hi)) if world_size > 1 else result
+
+    def _paint_plane_device(self, delta, geo, z, weight_map, batch_size, tile_ids, seed, regularise_std=None, out=None):
+        """The device form of ``lightcone.paint_plane`` (on_device=True): ``geo`` is ``lightcone.plane_geometry``'s,
+        ``weight_map`` the host's ``make_weight_map`` (float64, uploaded as it is), ``tile_ids`` / ``seed`` / ``batch_size``
+        those the host path hands to ``paint_stream``.  Per batch, on ONE stream: the tiles are cut (and resampled) from
+        the device plane into a slot's ``raw`` (bp_plane_cut), the batch's parameter block is copied in from a per-plane
+        device copy, the graph is replayed, and the slot's ``out`` is blended into float64 accumulators
+        (bp_plane_blend); bp_plane_finish divides.  Returns the (n_plane, n_plane) float64 plane, or ``out`` (a CUDA
+        float64 tensor of that shape) filled in place."""
+        model = self.model
+        model.train(False)
+        tile, W = self._tile_shape()
+        if tile != W:
+            raise NotImplementedError("device planes need square tiles")
+        if tuple(weight_map.shape) != (tile, tile):
+            raise ValueError(f"weight map {weight_map.shape} does not match the model's {tile}^2 tiles")
+        params, scales, modes = self._device_paint_parameters(np.full(len(geo["origins"]), float(z)))
+        return _paint_plane_pipeline(self, model, tile, delta, geo, int(batch_size), params, tile_ids, seed, weight_map,
+                                     regularise_std, out, scales, modes)
+
 
 class CVAEPainter(Painter):
     def __init__(self, filename=None, training_data_set=None, test_data_set=None, architecture="test",
@@ -373,105 +434,52 @@ class CVAEPainter(Painter):
             modes, xf_in, xf_out = None, xf_in[:, :2], xf_out[:, 1::-1]
         return {"xf_in": xf_in, "xf_out": xf_out, "aux": np.asarray(zs, dtype=np.float64)}, scales, modes
 
-    def can_paint_stream(self, z=0.0):
-        """Whether ``paint_stream`` has a device form for this painter (one label field, one of the six range compressions
-        on either side and L = 1, with or without a prior network or a p_y_in network; single-channel tiles, or a split-scale transform in the orders
-        ``_transform_parameters`` names whose levels are the model's dim_y[0] = dim_x[0]) -- WITHOUT side effects: nothing is
-        captured, no random number is drawn.  ``lightcone.paint_plane`` asks this before it draws a plane's seed, so that
-        a NotImplementedError raised later, from inside a capture, is an error and not a silent fall-back."""
-        model = self.model
-        if getattr(model, "L", 1) != 1:         # (the captured pipeline only; paint / paint_batch take any L)
-            return False
-        try:
-            scales = self._transform_parameters(np.atleast_1d(np.asarray(z, dtype=np.float64))[:1])[1]
-        except NotImplementedError:
-            return False
-        if scales is None:
-            return model.dim_y[0] == 1
-        if getattr(model, "has_p_y_in", False):     # (no split-scale load step with one destination: CVAE.paint_graph)
-            return False
-        levels = scales["n_scale"] + int(scales["include_original"])
-        return model.dim_y[0] == levels and model.dim_x[0] == levels
+    def _tile_shape(self):
+        return tuple(self.model.dim_y[1:])
 
-    def _check_channels(self, scales, what):
-        """NotImplementedError unless the model's channels are what the device transforms feed (before any capture)."""
-        cy, cx = self.model.dim_y[0], self.model.dim_x[0]
+    def _shape_mismatch(self, shape):
+        return f"Shape mismatch between input and model: {shape} vs {self.model.dim_y}"
+
+    def _device_paint_parameters(self, zs):
+        """``_transform_parameters(zs)`` where this painter has a device form -- one label field, one of the six range
+        compressions on either side and L = 1, with or without a prior network or a p_y_in network; single-channel
+        tiles, or a split-scale transform in the orders ``_transform_parameters`` names whose levels are the model's
+        dim_y[0] = dim_x[0], without a p_y_in network -- and NotImplementedError where it has none.  No side effects."""
+        model = self.model
+        if getattr(model, "L", 1) != 1:
+            raise NotImplementedError("the captured paint pipeline needs L = 1 (paint / paint_batch take any L)")
+        params, scales, modes = self._transform_parameters(zs)
+        cy, cx = model.dim_y[0], model.dim_x[0]
         if scales is None:
             if cy != 1:
-                raise NotImplementedError(f"{what} single-channel input tiles (or a split-scale transform's levels)")
+                raise NotImplementedError("the device paint path takes single-channel input tiles (or a split-scale "
+                                          "transform's levels)")
         else:
-            if getattr(self.model, "has_p_y_in", False):
-                raise NotImplementedError(f"{what} split-scale tiles only for models without a p_y_in network")
+            if getattr(model, "has_p_y_in", False):     # (no split-scale load step with one destination: CVAE.paint_graph)
+                raise NotImplementedError("the device paint path takes split-scale tiles only for models without a "
+                                          "p_y_in network")
             levels = scales["n_scale"] + int(scales["include_original"])
             if cy != levels or cx != levels:
-                raise NotImplementedError(f"{what} dim_y[0] = dim_x[0] = {levels} for this split-scale transform, the "
-                                          f"model has {cy} and {cx}")
+                raise NotImplementedError(f"the device paint path needs dim_y[0] = dim_x[0] = {levels} for this "
+                                          f"split-scale transform, the model has {cy} and {cx}")
+        return params, scales, modes
+
+    def can_paint_stream(self, z=0.0):
+        """Whether ``paint_stream`` has a device form for this painter (``_device_paint_parameters``) -- WITHOUT side
+        effects: nothing is captured, no random number is drawn.  ``lightcone.paint_plane`` asks this before it draws a
+        plane's seed, so that a NotImplementedError raised later, from inside a capture, is an error and not a silent
+        fall-back."""
+        try:
+            self._device_paint_parameters(np.atleast_1d(np.asarray(z, dtype=np.float64))[:1])
+        except NotImplementedError:
+            return False
+        return True
 
     def release_paint_buffers(self):
-        """Free the page-locked host staging buffers ``paint_stream`` keeps between calls: two parameter blocks plus up to
-        four (batch, 1, H, W) fp32 buffers -- 256 MiB of pinned memory at batch 64 of 512^2 tiles -- which otherwise live
-        as long as the painter (page-locking them costs tens of milliseconds per call, hence the cache)."""
-        self.__dict__.pop("_paint_host_buffers", None)
-        self.__dict__.pop("_plane_device_buffers", None)      # (and _paint_plane_device's accumulators and scratch)
-        if hasattr(self.model, "release_scale_buffers"):      # (and a multi-scale pipeline's pyramid scratch)
+        """``Painter.release_paint_buffers``, and a multi-scale pipeline's pyramid scratch."""
+        super().release_paint_buffers()
+        if hasattr(self.model, "release_scale_buffers"):
             self.model.release_scale_buffers()
-
-    def paint_stream(self, inputs, z, batch_size=64, tile_ids=None, seed=0, rank=0, world_size=1, out=None):
-        """Paint MANY raw tiles: ``inputs`` (N, H, W) float32 host array (NumPy, memory map, or a pinned torch tensor),
-        redshifts ``z`` (scalar or (N,)) -> (N, H, W) float32 physical tiles.  The production form of ``paint``
-        (process_SLICS.py:201-218 calls it tile by tile):
-
-          * the transform and its inverse run on the device, fused into the layout kernels on either side of the
-            network (``bp_paint_load`` / ``bp_paint_store``), bit-compatible with the host transforms;
-          * batches of ``batch_size`` tiles replay ONE captured hipGraph (prior + sampler + generator on four streams);
-          * host->device and device->host copies go through pinned double buffers on their own streams, so that
-            batch b+1 is uploaded and batch b-1 downloaded while batch b is painted;
-          * the prior noise of tile i comes from a counter-based generator keyed on (``seed``, ``tile_ids[i]``
-            [default: i], int64), so the result does not depend on ``batch_size`` or on how tiles are dealt to ranks;
-            the seed travels in the per-batch parameter block: one captured graph serves every seed;
-          * ``rank`` / ``world_size``: this process paints the contiguous block of tiles that is its share (one
-            process per GPU, no collective: tiles are independent) and returns (block, (lo, hi))."""
-        model = self.model
-        model.train(False)
-        dev = model.device
-        cy, H, W = model.dim_y
-        N = len(inputs)
-        if tuple(inputs.shape[1:]) != (H, W):
-            raise ValueError(f"Shape mismatch between input and model: {tuple(inputs.shape)} vs {model.dim_y}")
-        zs = np.broadcast_to(np.asarray(z, dtype=np.float64), (N,))
-        ids = np.arange(N, dtype=np.int64) if tile_ids is None else np.asarray(tile_ids, dtype=np.int64)
-        per = (N + world_size - 1) // world_size
-        lo, hi = min(rank * per, N), min((rank + 1) * per, N)
-        B = int(batch_size)
-        params, scales, modes = self._transform_parameters(zs[lo:hi])     # (NotImplementedError before any capture)
-        self._check_channels(scales, "paint_stream paints")
-        result = _paint_stream_pipeline(self, model, inputs, (H, W), lo, hi, B, params, ids[lo:hi], seed, out, scales,
-                                        modes)
-        return (result, (lo, hi)) if world_size > 1 else result
-
-    def _paint_plane_device(self, delta, geo, z, weight_map, batch_size, tile_ids, seed, regularise_std=None, out=None):
-        """The device form of ``lightcone.paint_plane`` (on_device=True): ``geo`` is ``lightcone.plane_geometry``'s,
-        ``weight_map`` the host's ``make_weight_map`` (float64, uploaded as it is), ``tile_ids`` / ``seed`` / ``batch_size``
-        those the host path hands to ``paint_stream``.  Per batch, on ONE stream: the tiles are cut (and resampled) from
-        the device plane into a slot's ``raw`` (bp_plane_cut), the batch's parameter block is copied in from a per-plane
-        device copy, the graph is replayed, and the slot's ``out`` is blended into float64 accumulators
-        (bp_plane_blend); bp_plane_finish divides.  Returns the (n_plane, n_plane) float64 plane, or ``out`` (a CUDA
-        float64 tensor of that shape) filled in place."""
-        model = self.model
-        model.train(False)
-        cy, H, W = model.dim_y
-        tile = H
-        if H != W:
-            raise NotImplementedError("device planes need square tiles")
-        if tuple(weight_map.shape) != (tile, tile):
-            raise ValueError(f"weight map {weight_map.shape} does not match the model's {tile}^2 tiles")
-        n = len(geo["origins"])
-        B = int(batch_size)
-        zs = np.full(n, float(z))
-        params, scales, modes = self._transform_parameters(zs)     # (NotImplementedError before any capture)
-        self._check_channels(scales, "device planes need")
-        return _paint_plane_pipeline(self, model, tile, delta, geo, B, params, tile_ids, seed, weight_map,
-                                     regularise_std, out, scales, modes)
 
     # ------------------------------------------------------------------------------ checkpoints
     def save_state_to_file(self, filename, mode="model_state_dict+metadata"):
@@ -510,15 +518,6 @@ class CVAEPainter(Painter):
 # models.cgan.CGAN): the models differ in what their captured graph does and in the columns of the transform
 # parameters, not in how batches are fed to it.  ``params``: per tile of this call, ``xf_in`` / ``xf_out`` (n, k) float64
 # rows of the graph's ``block_layout`` and ``aux`` (n,) the value of its conditioning plane.
-
-def _block_views(buf, layout):
-    """The typed NumPy views of one host parameter block (uint8 tensor) under ``layout``."""
-    hv = {}
-    for name, (o, dt, shape) in layout.items():
-        nb = torch.tensor([], dtype=dt).element_size() * int(np.prod(shape))
-        hv[name] = buf[o:o + nb].view(dt).view(shape).numpy()
-    return hv
-
 
 def _fill_block(hv, params, ids, a, b, B):
     """Tiles [a, b) of ``params`` / ``ids`` into the views of one block of ``B`` rows."""
@@ -559,7 +558,7 @@ def _paint_stream_pipeline(painter, model, inputs, tile_shape, lo, hi, B, params
     up, down = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
     # Two slots = the graph's own two buffer sets (paint_graph): uploads land where the load kernel reads, downloads
     # leave from where the store kernel writes.  Per slot one pinned parameter block (one copy per batch).
-    layout = g["block_layout"]
+    block = g["param_block"]
     # pinned host buffers are kept between calls (page-locking 4 x 64 MiB costs tens of milliseconds per call);
     # release_paint_buffers() frees them; the tile buffers are only allocated for NumPy inputs / outputs
     cache = painter.__dict__.setdefault("_paint_host_buffers", {})
@@ -571,7 +570,7 @@ def _paint_stream_pipeline(painter, model, inputs, tile_shape, lo, hi, B, params
     slots = []
     for gs, hb in zip(g["slots"], cache[key]):
         h_blk = hb["h_blk"]
-        hv = _block_views(h_blk, layout)
+        hv = block.views(h_blk)
         hv["seed"][0] = _seed_word(seed)
         if not torch_in and hb["h_in"] is None:
             hb["h_in"] = torch.empty((B, 1, H, W), dtype=torch.float32).pin_memory()
@@ -666,11 +665,11 @@ def _paint_plane_pipeline(painter, model, tile, delta, geo, B, params, tile_ids,
     g = _paint_graph(model, B, scales, modes)
     # per-plane parameter blocks, one per batch, built like paint_stream's pinned ones and uploaded once: a batch
     # then costs one device-to-device copy of its block into the slot
-    layout = g["block_layout"]
+    block = g["param_block"]
     n_batches = (n + B - 1) // B
     blocks = torch.zeros((n_batches, g["block_bytes"]), dtype=torch.uint8)
     for bi in range(n_batches):
-        hv = _block_views(blocks[bi], layout)
+        hv = block.views(blocks[bi])
         hv["seed"][0] = _seed_word(seed)
         _fill_block(hv, params, tile_ids, bi * B, min(bi * B + B, n), B)
     lib = L.load()
@@ -963,47 +962,22 @@ class CGANPainter(Painter):
         return {"xf_in": np.stack([s_in, k0, k1], axis=1), "xf_out": np.stack([k0, k1, s_out], axis=1),
                 "aux": np.asarray(zs, np.float64).astype(np.float32) - np.float32(1.0)}
 
+    def _tile_shape(self):
+        return self.model.tile_size, self.model.tile_size
+
+    def _shape_mismatch(self, shape):
+        return f"Shape mismatch between input and model: {shape} vs {(1, *self._tile_shape())}"
+
+    def _device_paint_parameters(self, zs):
+        """The shift-log-cam transform, the conditioning plane, the generator's tanh and the inverse transform run on the
+        device (``bp_paint_load_cam`` / ``bp_paint_store_cam`` around the generator, one captured hipGraph per batch size
+        on one stream); ``tile_ids`` and ``seed`` do not affect the result (no latent noise)."""
+        return self._cam_parameters(zs), None, None
+
     def release_paint_buffers(self):
-        """Free what the paint paths keep between calls: the pinned staging buffers of ``paint_stream``, the
-        accumulators of ``_paint_plane_device``, and the model's inference plans and captured graphs."""
-        self.__dict__.pop("_paint_host_buffers", None)
-        self.__dict__.pop("_plane_device_buffers", None)
+        """``Painter.release_paint_buffers``, and the model's inference plans and captured graphs."""
+        super().release_paint_buffers()
         self.model.release_paint_buffers()
-
-    def paint_stream(self, inputs, z, batch_size=64, tile_ids=None, seed=0, rank=0, world_size=1, out=None):
-        """Paint MANY raw tiles, as ``CVAEPainter.paint_stream`` does: ``inputs`` (N, H, W) float32 host array (NumPy,
-        memory map, or a pinned torch tensor), redshifts ``z`` (scalar or (N,)) -> (N, H, W) float32 physical tiles.
-        The shift-log-cam transform, the conditioning plane, the generator's tanh and the inverse transform run on the
-        device (``bp_paint_load_cam`` / ``bp_paint_store_cam`` around the generator, one captured hipGraph per batch
-        size on one stream); uploads and downloads go through the same pinned double buffers.  ``rank`` /
-        ``world_size``: this process paints its contiguous share and returns (block, (lo, hi)).  ``tile_ids`` and
-        ``seed`` do not affect the result (no latent noise)."""
-        model = self.model
-        model.train(False)
-        H = W = model.tile_size
-        N = len(inputs)
-        if tuple(inputs.shape[1:]) != (H, W):
-            raise ValueError(f"Shape mismatch between input and model: {tuple(inputs.shape)} vs {(1, H, W)}")
-        zs = np.broadcast_to(np.asarray(z, dtype=np.float64), (N,))
-        ids = np.arange(N, dtype=np.int64) if tile_ids is None else np.asarray(tile_ids, dtype=np.int64)
-        per = (N + world_size - 1) // world_size
-        lo, hi = min(rank * per, N), min((rank + 1) * per, N)
-        params = self._cam_parameters(zs[lo:hi])                       # (NotImplementedError before any capture)
-        result = _paint_stream_pipeline(self, model, inputs, (H, W), lo, hi, int(batch_size), params, ids[lo:hi], seed,
-                                        out)
-        return (result, (lo, hi)) if world_size > 1 else result
-
-    def _paint_plane_device(self, delta, geo, z, weight_map, batch_size, tile_ids, seed, regularise_std=None, out=None):
-        """The device form of ``lightcone.paint_plane`` (on_device=True), as ``CVAEPainter._paint_plane_device``, with
-        the CGAN's graph and parameter block."""
-        model = self.model
-        model.train(False)
-        tile = model.tile_size
-        if tuple(weight_map.shape) != (tile, tile):
-            raise ValueError(f"weight map {weight_map.shape} does not match the model's {tile}^2 tiles")
-        params = self._cam_parameters(np.full(len(geo["origins"]), float(z)))
-        return _paint_plane_pipeline(self, model, tile, delta, geo, int(batch_size), params, tile_ids, seed, weight_map,
-                                     regularise_std, out)
 
     # ------------------------------------------------------------------------------ checkpoints
     def _meta(self):

@@ -174,9 +174,21 @@ def test_split_scale_pipeline_refuses_a_p_y_in_network_before_capture(painter_a)
     n_graphs = len(q.model._graphs)
     with pytest.raises(NotImplementedError, match="p_y_in"):
         q.model.paint_graph(2, scales={"n_scale": 1, "step_size": 2.0, "include_original": False})
-    with pytest.raises(NotImplementedError, match="p_y_in"):
-        q._check_channels({"n_scale": 1, "include_original": False}, "paint_stream paints")
-    assert len(q.model._graphs) == n_graphs
+    # ... and by the painter, for a one-level split-scale chain (whose levels ARE this model's channels)
+    fwd, inv = T.create_range_compress_transforms(HC.K_VALUES, HC.MODES)
+    split, unsplit = T.create_split_scale_transform(1, 2.0, False)
+    good = (q.transform, q.inverse_transform)
+    try:
+        q.transform = type(good[0])(T.chain_transformations([fwd, T.as_float32, split, T.atleast_3d]), good[0].stats)
+        q.inverse_transform = type(good[1])(T.chain_transformations([unsplit, inv, T.squeeze]), good[1].stats)
+        assert not q.can_paint_stream()
+        with pytest.raises(NotImplementedError, match="p_y_in"):
+            q.paint_stream(painter_a[3][:2], painter_a[4][:2], batch_size=2)
+        with pytest.raises(NotImplementedError, match="p_y_in"):
+            q._device_paint_parameters(np.zeros(1))
+    finally:
+        q.transform, q.inverse_transform = good
+    assert q.can_paint_stream() and len(q.model._graphs) == n_graphs
 
 
 # ---------------------------------------------------------------- what existed before launches what it launched
