@@ -52,6 +52,12 @@ class Latent(C.Structure):
                 ("zw", C.c_int32), ("min_z_var", C.c_float)]
 
 
+class Linear(C.Structure):
+    _fields_ = [("in_features", C.c_int32), ("out_features", C.c_int32), ("in_c", C.c_int32), ("in_h", C.c_int32),
+                ("in_w", C.c_int32), ("out_c", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32),
+                ("has_bias", C.c_int32)]
+
+
 class Loglik(C.Structure):
     _fields_ = [("n", C.c_int32), ("L", C.c_int32), ("c", C.c_int32), ("h", C.c_int32),
                 ("w", C.c_int32), ("mu_softplus", C.c_int32), ("predict_var", C.c_int32),
@@ -149,6 +155,10 @@ SIGNATURES = {
                                          _P]),
     "bp_plane_project_workspace": (C.c_size_t, [C.c_int32, C.c_int32]),
     "bp_plane_project": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_double, _P, C.c_size_t, _P, C.c_int32, _P]),
+    "bp_linear_workspace": (C.c_size_t, [C.c_int32, C.POINTER(Linear)]),
+    "bp_linear_forward": (C.c_int, [C.POINTER(Linear), _VP, _PWP, _P, _P, _VP, _P, C.c_size_t, _P]),
+    "bp_linear_backward_data": (C.c_int, [C.POINTER(Linear), _VP, _P, _VP, _P]),
+    "bp_linear_backward_weight": (C.c_int, [C.POINTER(Linear), _VP, _PWP, _VP, _P, _P, _P]),
     "bp_latent_forward": (C.c_int, [C.POINTER(Latent), _VP, _PWP, _VP, _PWP, _P, _P, _VP, _P, _P,
                                     C.c_size_t, _P]),
     "bp_latent_backward": (C.c_int, [C.POINTER(Latent), _VP, _P, _P, _P, C.c_float, _VP, _VP, _P]),

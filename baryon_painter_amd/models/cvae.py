@@ -19,7 +19,8 @@ import torch
 
 from .. import _lib as L
 from .arch import conv_block, conv_down, conv_up, res_block  # noqa: F401  (reference: ``from .utils import *``)
-from .graph import PW, ConvUnit, PackBatch, PlanBase, Slot, build_holders, compile_sequential, probe_output, _stream
+from .graph import PW, ConvUnit, PackBatch, PlanBase, Slot, build_holders, compile_sequential, dense_blocks, \
+    latent_shape, probe_output, _stream
 from . import paint_graph as PG
 
 pi = math.pi
@@ -50,7 +51,7 @@ class _Plan(PlanBase):
         if tuple(model.dim_x[1:]) != (H, W):
             raise NotImplementedError("dim_x and dim_y must share the spatial size")
         caux = model.n_aux if model.use_aux_label else 0
-        zc, zh, zw = model.dim_z
+        zc, zh, zw = latent_shape(model.dim_z)       # (a vector latent (d,) is the slot (n, 1, 1, d))
         self.caux = caux
 
         # ---- inputs: y (+aux planes) as NHWC; x is read as NCHW by the loss and as NHWC by Q
@@ -76,7 +77,7 @@ class _Plan(PlanBase):
             self._no_trailing(tr, "q_y_in")
             if sx is not sx0 or sy is not sy0:
                 raise NotImplementedError("q_x_in / q_y_in must end in a convolution")
-            uo, so, tr = compile_sequential(self, "q_out.", a["q_x_y_out"], model.q_out, cat)
+            uo, so, tr = compile_sequential(self, "q_out.", a["q_x_y_out"], model.q_out, cat, dense="tail")
             self._latent_trailing(tr, "q_x_y_out")
             self.q_units = [ux, uy, uo]
             self.q_head = so
@@ -87,7 +88,7 @@ class _Plan(PlanBase):
         self.p_units, self.p_head = [], None
         if model.prior_network is not None:
             up, sp, tr = compile_sequential(self, "prior_network.", a["prior_z_y"], model.prior_network,
-                                            self.y2, need_input_grad=False)
+                                            self.y2, need_input_grad=False, dense="tail")
             self._latent_trailing(tr, "prior_z_y")
             self.p_units, self.p_head = up, sp
             if sp.shape() != (n, zh, zw, 2 * zc):
@@ -138,10 +139,10 @@ class _Plan(PlanBase):
         else:
             self.hy_slot = self.p_in.sub(c_hz, ccat)
         uz, sz, tr = compile_sequential(self, "p_z_in.", a["p_z_in"], model.p_z_in, self.z,
-                                        out_slot=hz_slot, out_pw=hz_slot.pw)
+                                        out_slot=hz_slot, out_pw=hz_slot.pw, dense="head")
         self._no_trailing(tr, "p_z_in")
         if sz is not hz_slot:
-            raise NotImplementedError("p_z_in must end in a convolution")
+            raise NotImplementedError("p_z_in must end in a convolution (or be one dense block)")
         ub, sb, tr = compile_sequential(self, "p_y_z_in.", a["p_y_z_in"], model.p_y_z_in, self.p_in)
         self._no_trailing(tr, "p_y_z_in")
         if ub and isinstance(ub[0], ConvUnit) and not y_net:
@@ -640,6 +641,47 @@ class _Plan(PlanBase):
         return sl
 
 
+def check_dense_language(architecture, sync=None):
+    """Where dense blocks (flatten / linear / unflatten, ``graph.dense_blocks``) stand in a Type-1 architecture, checked
+    on the host: tails of q_x_y_out and prior_z_y, head of p_z_in, nowhere else; shapes that do not fit are a ValueError.
+    Architectures without a linear layer and with a three-entry dim_z pass unexamined: they compile as they always did."""
+    a = architecture
+    if a.get("type") != "Type-1":
+        return
+    nets = {"q_x_in": ("q_x_in.", None), "q_y_in": ("q_y_in.", None), "q_x_y_out": ("q_out.", "tail"),
+            "p_y_in": ("p_y_in.", None), "p_z_in": ("p_z_in.", "head"), "p_y_z_in": ("p_y_z_in.", None),
+            "prior_z_y": ("prior_network.", "tail")}
+    lists = [(k, a.get(k)) + nets[k] for k in nets]
+    lists += [(f"p_y_z_out[{i}]", seq, ("p_mu_out.", "p_var_out.")[i], None) for i, seq in enumerate(a["p_y_z_out"][:2])]
+    dense = any(layer[0].lower() == "linear" for _, seq, _, _ in lists for layer in seq or [])
+    dim_z = tuple(a["dim_z"])
+    if not dense and len(dim_z) == 3:
+        return
+    for key, seq, prefix, where in lists:
+        try:
+            dense_blocks(seq, prefix, where)
+        except NotImplementedError as e:
+            raise NotImplementedError(f"{key}: {e}") from None
+    if sync is not None:
+        raise NotImplementedError("a dense architecture (linear layers / a vector dim_z) under data parallelism (sync=) is "
+                                  "not supported: the lock-step level builder and the peer ring budget do not cover it")
+    zc, zh, zw = latent_shape(dim_z)
+    if len(dim_z) == 1 and (not a["p_z_in"] or a["p_z_in"][0][0].lower() != "linear"):
+        raise ValueError(f"dim_z = {dim_z} is a vector: p_z_in must begin with a linear layer")
+    cy, H, W = a["dim_y"]
+    cx = a["dim_x"][0]
+    caux = 1 if a["aux_label"] else 0
+    cqx, hq, wq = probe_output(a["q_x_in"], cx, H, W)
+    cqy, hq2, wq2 = probe_output(a["q_y_in"], cy + caux, H, W)
+    heads = [("q_x_y_out", probe_output(a["q_x_y_out"], cqx + cqy, hq, wq))] if (hq, wq) == (hq2, wq2) else []
+    if "prior_z_y" in a:
+        heads.append(("prior_z_y", probe_output(a["prior_z_y"], cy + caux, H, W)))
+    for key, got in heads:
+        if got != (2 * zc, zh, zw):
+            raise ValueError(f"{key} produces (c, h, w) = {got}, dim_z = {dim_z} needs {(2 * zc, zh, zw)}")
+    probe_output(a["p_z_in"], zc, zh, zw)
+
+
 DEFER_MAX_BYTES = int(os.environ.get("BP_DEFER_MAX_MB", "1048576")) << 20
 
 
@@ -691,6 +733,7 @@ class CVAE(torch.nn.Module):
         if self.device.type != "cuda":
             raise RuntimeError("baryon_painter_amd.CVAE runs on an AMD GPU only (device='cuda:N'); "
                                "there is no CPU implementation of the hot path.")
+        check_dense_language(architecture, sync)        # (host only: refusals come before any device allocation)
         self._lib = L.load()
         self.impl = {"auto": L.IMPL_AUTO, "direct": L.IMPL_DIRECT, "mfma": L.IMPL_MFMA}[impl]
         self.sync = sync
@@ -897,6 +940,7 @@ class CVAE(torch.nn.Module):
                 lib, st = self._lib, _stream()
                 zt = zt.contiguous()
                 L.check(lib.bp_nchw_to_view(L.ptr(zt), self.dim_z[0], None, 0, C.byref(plan.z.view), st), "z layout")
+                # ((n, d) of a vector latent is the same bytes as NCHW (n, d, 1, 1))
             plan.run_generator(self.training)
             lib, st = self._lib, _stream()
             cx, H, W = self.dim_x
@@ -1015,7 +1059,7 @@ class CVAE(torch.nn.Module):
             if self.L != 1:
                 raise NotImplementedError("the captured paint pipeline needs L = 1 (sample_P and paint take any L: they "
                                           "paint with one latent draw per tile)")
-            per_tile = self.dim_z[0] * self.dim_z[1] * self.dim_z[2]
+            per_tile = math.prod(self.dim_z)
             st["eps"] = torch.zeros((1, n, per_tile), device=dev)
             # parameter block of a slot: one contiguous device buffer = one host-to-device copy per batch
             block = PG.ParamBlock(PG.paint_fields(n, 2 if modes is None else 4, max(self.n_aux, 1)))

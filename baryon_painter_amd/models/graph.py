@@ -16,6 +16,7 @@ Conventions
 import contextlib
 import ctypes as C
 import gc
+import math
 import os
 
 import torch
@@ -856,6 +857,124 @@ class ConvUnit:
             plan.prof_end(t0, self, "backward_data")
 
 
+class LinearUnit:
+    """linear [+ relu | leaky relu | prelu]  (utils.py:132-139), with the ``flatten`` in front of it and the ``unflatten``
+    behind it folded into the shapes of its slots: the input slot (n, h, w, c) is read as c*h*w features with c slowest,
+    the output slot (n, ho, wo, co) written the same way (a flat operand is (n, 1, 1, d)).  Same contract as ``ConvUnit``:
+    the output is stored RAW with the activation pending on its pointwise record; the kernels (csrc/linear.hip) read
+    ``weight`` and write its gradient in torch's layout, in place in the flat buffers -- nothing is packed."""
+
+    bf16 = False                     # (these chains stay fp32 under dtype="bf16")
+    _sub = None
+    ws_name = "ws"
+
+    def __init__(self, plan, name, holder, act, act_arg, act_holder, inp, out_shape, out_slot=None, out_pw=None,
+                 need_dgrad=True):
+        self.plan, self.name = plan, name
+        dev = plan.device
+        K, O = holder.in_features, holder.out_features
+        if inp.dt != L.F32:
+            raise NotImplementedError(f"{name}: a linear layer cannot read a bf16 activation")
+        if inp.c * inp.h * inp.w != K:
+            raise ValueError(f"{name}: input has {inp.c * inp.h * inp.w} features, layer expects in_features={K}")
+        co, ho, wo = out_shape
+        if co * ho * wo != O:
+            raise ValueError(f"{name}: out_features={O} cannot be unflattened to {out_shape}")
+        self.holder, self.act_holder = holder, act_holder
+        self.act, self.act_arg = act, act_arg
+        self.inp, self.need_dgrad = inp, need_dgrad
+        self.desc = L.Linear(K, O, inp.c, inp.h, inp.w, co, ho, wo, 0 if holder.bias is None else 1)
+        self.has_pw = act is not None
+        if out_pw is None and self.has_pw:
+            out_pw = PW.identity(co, dev)
+        if out_pw is not None:
+            out_pw.scale.fill_(1.0)
+            out_pw.shift.fill_(0.0)
+            out_pw.slope.fill_(0.0 if act == "relu" else float(act_arg) if act == "leaky relu" else 1.0)
+        self.out_pw = out_pw
+        if out_slot is None:
+            self.out = Slot.new(inp.n, ho, wo, co, dev, pw=out_pw)
+        else:
+            if out_slot.shape() != (inp.n, ho, wo, co):
+                raise ValueError(f"{name}: concat slot shape {out_slot.shape()} != {(inp.n, ho, wo, co)}")
+            self.out = out_slot
+            self.out.pw = out_pw
+        self.out.producer = self
+        self.sums = torch.zeros(3 * co, device=dev, dtype=torch.float64)
+        self.dx = None
+        plan.need_ws(plan.lib.bp_linear_workspace(inp.n, C.byref(self.desc)))
+
+    def _ws(self):
+        return getattr(self.plan, self.ws_name)
+
+    def macs(self, kind="forward"):
+        return self.inp.n * self.desc.in_features * self.desc.out_features
+
+    def algorithmic_bytes(self, kind, nstreams=1):
+        """One pass over the weight matrix (read, or written by the weight gradient) plus the two activation operands."""
+        d = self.desc
+        return 4 * (d.in_features * d.out_features + self.inp.n * (d.in_features + d.out_features))
+
+    def maybe_pack(self):
+        pass                         # the kernels read torch's layout
+
+    def maybe_bn_eval(self):
+        pass
+
+    def forward(self, training):
+        plan, lib, hold = self.plan, self.plan.lib, self.holder
+        t0 = plan.prof_begin()
+        L.check(lib.bp_linear_forward(C.byref(self.desc), C.byref(self.inp.view), self.inp.pw_struct(),
+                                      L.ptr(hold.weight), L.ptr(hold.bias), C.byref(self.out.view), L.ptr(self._ws()),
+                                      plan.ws_bytes, _stream()), f"{self.name} forward")
+        plan.prof_end(t0, self, "forward")
+        if self.act == "prelu":
+            self.out_pw.slope.copy_(self.act_holder.weight.detach().expand(self.out.c))
+
+    def prepare_backward(self):
+        self.out.ensure_grad()
+        self.plan.need_ws(self.plan.lib.bp_act_backward_workspace(C.byref(self.out.view)))
+        self.dx = self.inp.claim_grad() if self.need_dgrad else None
+
+    def backward(self, grads):
+        """``out.grad`` (+ ``out.grad2``) hold d/d(activated out): activation backward in place, then the weight gradient
+        (on the plan's weight-gradient stream, like a convolution's) and the data gradient."""
+        plan, lib, st = self.plan, self.plan.lib, _stream()
+        out, hold = self.out, self.holder
+        if self.has_pw or out.grad2 is not None:
+            pw = None if self.out_pw is None else C.byref(self.out_pw.struct)
+            L.check(lib.bp_act_backward(C.byref(out.grad), None if out.grad2 is None else C.byref(out.grad2),
+                                        C.byref(out.view), pw, None, C.byref(out.grad), L.ptr(self.sums),
+                                        L.ptr(self._ws()), plan.ws_bytes, st), f"{self.name} act backward")
+            if self.act == "prelu":
+                L.check(lib.bp_prelu_slope_grad(L.ptr(self.sums), out.c, L.ptr(grads[id(self.act_holder.weight)]), st),
+                        f"{self.name} prelu grad")
+        g = out.grad
+        dbias = None if hold.bias is None else grads[id(hold.bias)]
+        side = plan.side_of(self)[0] if hasattr(plan, "side_of") else getattr(plan, "side", None)
+
+        def wgrad():
+            t0 = plan.prof_begin()
+            L.check(lib.bp_linear_backward_weight(C.byref(self.desc), C.byref(self.inp.view), self.inp.pw_struct(),
+                                                  C.byref(g), L.ptr(grads[id(hold.weight)]), L.ptr(dbias), _stream()),
+                    f"{self.name} backward_weight")
+            plan.prof_end(t0, self, "backward_weight")
+
+        if getattr(plan, "skip_wgrad", False):
+            pass
+        elif side is None:
+            wgrad()
+        else:
+            side.wait_stream(torch.cuda.current_stream())     # fork: d_raw of this layer is complete
+            with torch.cuda.stream(side):
+                wgrad()
+        if self.dx is not None:
+            t0 = plan.prof_begin()
+            L.check(lib.bp_linear_backward_data(C.byref(self.desc), C.byref(g), L.ptr(hold.weight), C.byref(self.dx), st),
+                    f"{self.name} backward_data")
+            plan.prof_end(t0, self, "backward_data")
+
+
 class PackBatch:
     """All weight re-layouts of a plan in one launch (``bp_conv_pack_jobs``) instead of two per layer.
 
@@ -987,27 +1106,131 @@ class ResidualUnit:
             u.backward(grads)
 
 
+# ------------------------------------------------------------------ dense blocks
+_CONV_LIKE = ("conv", "sn conv", "transp conv", "residual block")
+_DENSE_ACTS = ("relu", "leaky relu", "prelu")
+
+
+def _layer_list(architecture):
+    return [(layer[0].lower(), layer[1] if len(layer) == 2 else None) for layer in architecture or []]
+
+
+def unflatten_shape(shape):
+    """Logical (c, h, w) of ``unflatten`` to ``shape``: three entries are (c, h, w); four, the latent heads'
+    (2, c, h, w), are 2c channels (``h[:, 0]`` / ``h[:, 1]`` of the reference, cvae.py:75-76, are channels [0, c) and
+    [c, 2c)); one or two entries, (d,) or (2, d), are flat: d or 2d features in the slot (n, 1, 1, d)."""
+    shape = tuple(int(v) for v in shape)
+    if len(shape) == 3:
+        return shape
+    if len(shape) == 4:
+        return (shape[0] * shape[1], shape[2], shape[3])
+    if len(shape) in (1, 2):
+        return (math.prod(shape), 1, 1)
+    raise ValueError(f"unflatten to {shape}: one to four entries are understood")
+
+
+def latent_shape(dim_z):
+    """(c, h, w) of the latent slot: ``dim_z`` itself, or (d, 1, 1) for a vector latent (d,)."""
+    dim_z = tuple(int(v) for v in dim_z)
+    if len(dim_z) == 3:
+        return dim_z
+    if len(dim_z) == 1:
+        return (dim_z[0], 1, 1)
+    raise ValueError(f"dim_z {dim_z}: one entry (d,) or three (c, h, w)")
+
+
+def dense_blocks(architecture, prefix, where):
+    """The dense blocks of a layer list,
+        [("flatten",)] ("linear", cfg) [relu | leaky relu | prelu] { ("linear", cfg) [act] } [("unflatten", shape)],
+    as {index of the first layer: {"flatten", "linears": [(index, act index or None)], "unflatten": shape or None,
+    "end": index behind the block}}.  ``where``: "tail" (q_x_y_out, prior_z_y: behind every convolution), "head"
+    (p_z_in: in front of every convolution) or None (no dense block may stand in this net).  Needs no device: every
+    refusal of the language is raised here, as NotImplementedError naming the layer."""
+    layers = _layer_list(architecture)
+    names = [n for n, _ in layers]
+    conv_like = [i for i, n in enumerate(names) if n in _CONV_LIKE]
+    blocks, i = {}, 0
+    while i < len(layers):
+        if names[i] != "linear" and not (names[i] == "flatten" and i + 1 < len(layers) and names[i + 1] == "linear"):
+            i += 1
+            continue
+        if where is None:
+            k = i if names[i] == "linear" else i + 1
+            raise NotImplementedError(f"{prefix}{k}: layer 'linear' is not supported by the HIP path in this network "
+                                      "(dense blocks: tails of q_x_y_out / prior_z_y, head of p_z_in)")
+        start = i
+        flat = names[i] == "flatten"
+        i += flat
+        linears = []
+        while i < len(layers) and names[i] == "linear":
+            a = i + 1 if i + 1 < len(layers) and names[i + 1] in _DENSE_ACTS else None
+            linears.append((i, a))
+            i = i + 1 if a is None else i + 2
+        unflat = None
+        if i < len(layers) and names[i] == "unflatten":
+            unflat = layers[i][1]
+            i += 1
+        if i < len(layers) and names[i] in ("tanh", "sigmoid", "softplus", "batchnorm"):
+            raise NotImplementedError(f"{prefix}{i}: '{names[i]}' behind the dense block {prefix}{linears[-1][0]} is not "
+                                      "supported by the HIP path")
+        if where == "tail" and any(c > start for c in conv_like):
+            raise NotImplementedError(f"{prefix}{linears[0][0]}: 'linear' in front of a convolution is not supported by "
+                                      "the HIP path in this network (its dense block is the tail)")
+        if where == "head" and (start != 0 or blocks):
+            raise NotImplementedError(f"{prefix}{linears[0][0]}: 'linear' behind other layers is not supported by the HIP "
+                                      "path in this network (its dense block is the head)")
+        blocks[start] = {"flatten": flat, "linears": linears, "unflatten": unflat, "end": i}
+    return blocks
+
+
 # ------------------------------------------------------------------ sequential compiler
 def compile_sequential(plan, prefix, architecture, holders, inp, out_slot=None, out_pw=None,
-                       need_input_grad=True):
+                       need_input_grad=True, dense=None):
     """Group the layer list into units.  Returns (units, output slot, trailing) where
     ``trailing`` lists parameter-free layers after the last convolution that are not
-    expressible as a pending pointwise (softplus / tanh / sigmoid / unflatten / flatten)."""
+    expressible as a pending pointwise (softplus / tanh / sigmoid / unflatten / flatten).
+    ``dense``: where a dense block may stand in this net ("tail" / "head" / None, see ``dense_blocks``)."""
     units, trailing = [], []
     if architecture is None:
         return units, inp, trailing
-    layers = []
-    for layer in architecture:
-        name = layer[0].lower()
-        layers.append((name, layer[1] if len(layer) == 2 else None))
-    # index of the last conv-like layer (its output may go to a concat slot)
-    conv_like = [i for i, (n, _) in enumerate(layers) if n in ("conv", "sn conv", "transp conv", "residual block")]
+    layers = _layer_list(architecture)
+    blocks = dense_blocks(architecture, prefix, dense)
+    # index of the last conv-like layer, and of the last layer that produces a tensor -- that one or a linear layer
+    # behind it: its output may go to a concat slot
+    conv_like = [i for i, (n, _) in enumerate(layers) if n in _CONV_LIKE]
     last_conv = conv_like[-1] if conv_like else -1
+    last_producer = max([last_conv] + [b["linears"][-1][0] for b in blocks.values()])
     cur = inp
     i = 0
     first = True
     while i < len(layers):
         name, cfg = layers[i]
+        if i in blocks:
+            b = blocks[i]
+            if not b["flatten"] and (cur.h, cur.w) != (1, 1):
+                raise NotImplementedError(f"{prefix}{i}: 'linear' on an input that is neither flat nor directly behind "
+                                          "'flatten' is not supported by the HIP path")
+            for li, ai in b["linears"]:
+                holder = holders[li]
+                final = li == b["linears"][-1][0]
+                shape = unflatten_shape(b["unflatten"]) if final and b["unflatten"] is not None \
+                    else (holder.out_features, 1, 1)
+                if final and b["unflatten"] is not None and math.prod(shape) != holder.out_features:
+                    raise ValueError(f"{prefix}{li}: out_features={holder.out_features} cannot be unflattened to "
+                                     f"{tuple(b['unflatten'])}")
+                act = act_arg = act_holder = None
+                if ai is not None:
+                    act, act_arg = layers[ai]
+                    act_holder = holders[ai] if act == "prelu" else None
+                is_last = li == last_producer
+                u = LinearUnit(plan, f"{prefix}{li}", holder, act, act_arg, act_holder, cur, shape,
+                               out_slot=out_slot if is_last else None, out_pw=out_pw if is_last else None,
+                               need_dgrad=(need_input_grad or not first))
+                units.append(u)
+                cur = u.out
+                first = False
+            i = b["end"]
+            continue
         if name in ("conv", "sn conv", "transp conv"):
             holder = holders[i]
             j = i + 1
@@ -1019,7 +1242,7 @@ def compile_sequential(plan, prefix, architecture, holders, inp, out_slot=None, 
                 act, act_arg = layers[j][0], layers[j][1]
                 act_holder = holders[j] if act == "prelu" else None
                 j += 1
-            is_last = (i == last_conv)
+            is_last = (i == last_producer)
             u = ConvUnit(plan, f"{prefix}{i}", holder, bn, act, act_arg, act_holder, cur,
                          out_slot=out_slot if is_last else None, out_pw=out_pw if is_last else None,
                          need_dgrad=(need_input_grad or not first))
@@ -1031,7 +1254,7 @@ def compile_sequential(plan, prefix, architecture, holders, inp, out_slot=None, 
             body, body_out, tr = compile_sequential(plan, f"{prefix}{i}.res_block.", cfg[0], rh.res_block, cur)
             if tr:
                 raise NotImplementedError("residual branch must end in a convolution/batch-norm")
-            if i == last_conv and out_slot is not None:
+            if i == last_producer and out_slot is not None:
                 raise NotImplementedError("residual block as the last layer of a concatenated branch")
             u = ResidualUnit(plan, f"{prefix}{i}", body, cur, rh.tail)
             units.append(u)
@@ -1062,4 +1285,18 @@ def probe_output(architecture, c, h, w):
                 op = cfg.get("output_padding", 0)
                 h, w = (h - 1) * st - 2 * pd + k + op, (w - 1) * st - 2 * pd + k + op
             c = cfg["out_channels"]
+        elif name == "flatten":
+            c, h, w = c * h * w, 1, 1
+        elif name == "linear":
+            cfg = layer[1]
+            if (h, w) != (1, 1):
+                raise NotImplementedError("'linear' on an input that is neither flat nor directly behind 'flatten'")
+            if cfg["in_features"] != c:
+                raise ValueError(f"linear: in_features={cfg['in_features']} on an input of {c} features")
+            c = cfg["out_features"]
+        elif name == "unflatten":
+            shape = unflatten_shape(layer[1])
+            if math.prod(shape) != c * h * w:
+                raise ValueError(f"unflatten: {c * h * w} features cannot be viewed as {tuple(layer[1])}")
+            c, h, w = shape
     return c, h, w

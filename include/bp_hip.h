@@ -475,6 +475,46 @@ size_t bp_plane_project_workspace(int32_t n, int32_t res);
 int bp_plane_project(const double* plane, int32_t rows, int32_t cols, double scale, double* scratch,
                      size_t scratch_bytes, double* y, int32_t res, void* stream);
 
+/* ---- fully connected layers of the latent bottleneck (replaces nn.Linear behind nn.Flatten / in front of
+ *      nn.Unflatten, utils.py:132-133, 148-157, and their autograd backward) ------------------------------------- */
+
+/* nn.Linear on NHWC views.  A view of logical shape (c, h, w) is read as a row of c*h*w features with c slowest, as
+ * torch flattens an NCHW tensor; a flat operand of d features is the view (n, 1, 1, d).  The permutation between that
+ * order and NHWC is applied to the activation index inside the kernels; `weight` (out_features, in_features) and its
+ * gradient keep torch's layout.  All arithmetic is fp32 (fp32 matrix cores for batches of 32 rows and more, vector ALUs
+ * below); every sum has a fixed order, so a call repeated on the same data gives the same bits. */
+typedef struct bp_linear {
+  int32_t in_features, out_features;
+  int32_t in_c, in_h, in_w;    /* logical shape of the input:  in_c * in_h * in_w   == in_features  */
+  int32_t out_c, out_h, out_w; /* logical shape of the output: out_c * out_h * out_w == out_features */
+  int32_t has_bias;
+} bp_linear;
+
+/* Every entry point checks its arguments before launching: views that do not match the descriptor (shape, element
+ * type, different batch sizes, n <= 0), a NULL where a pointer is needed or a bias pointer that contradicts has_bias
+ * give BP_EINVAL, a short workspace BP_EWORKSPACE; nothing is written then.  Views with cstride != c and coff != 0 are
+ * served; channels outside a view are never touched.  No allocation, no synchronisation: capturable.
+ *
+ * Bytes of partial sums the forward needs for n rows: its sum over in_features is split into slabs over workgroups
+ * (the split depends on the layer only, not on n), and a second launch adds the slabs in ascending order.  0 for an
+ * invalid descriptor or n <= 0. */
+size_t bp_linear_workspace(int32_t n, const bp_linear* desc);
+
+/* y_raw[n][g] = sum_f act(x[n][f]) * weight[g][f] (+ bias[g]).  `x_pw`: the input slot's pending pointwise, applied
+ * at load by the channel of feature f (NULL: identity).  The output is RAW: an activation behind the layer stays
+ * pending on the output slot's record.  bias non-NULL exactly when desc->has_bias. */
+int bp_linear_forward(const bp_linear* desc, const bp_view* x, const bp_pointwise* x_pw, const float* weight,
+                      const float* bias, const bp_view* y, void* workspace, size_t workspace_bytes, void* stream);
+
+/* dx[n][f] = sum_g dy[n][g] * weight[g][f]: d(loss)/d(act(x)) from dy = d(loss)/d(y_raw), g ascending. */
+int bp_linear_backward_data(const bp_linear* desc, const bp_view* dy, const float* weight, const bp_view* dx,
+                            void* stream);
+
+/* dweight[g][f] = sum_n dy[n][g] * act(x[n][f]) and dbias[g] = sum_n dy[n][g], n ascending, each element written once
+ * (overwritten, not accumulated).  dbias non-NULL exactly when desc->has_bias. */
+int bp_linear_backward_weight(const bp_linear* desc, const bp_view* x, const bp_pointwise* x_pw, const bp_view* dy,
+                              float* dweight, float* dbias, void* stream);
+
 /* ---- latent heads: reparametrisation sampler + KL (cvae.py:63-66, 76-77, 126-130) ----------- */
 typedef struct bp_latent {
   int32_t n;      /* batch M                         */
