@@ -142,6 +142,7 @@ SIGNATURES = {
     "bp_paint_load_scales2_mode": (C.c_int, [C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,
                                              C.c_size_t, _VP, _VP, _P]),
     "bp_paint_store_scales_mode": (C.c_int, [C.c_int32, _VP, _PWP, C.c_int32, C.c_int32, _P, _P, _P]),
+    "bp_paint_store_fields": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _VP, _PWP, C.c_int32, _P, _P, _P]),
     "bp_philox_normal": (C.c_int, [C.c_uint64, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "bp_philox_normal_dev": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "bp_plane_cut_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
@@ -149,6 +150,8 @@ SIGNATURES = {
                                C.c_size_t, _P, _P]),
     "bp_plane_blend": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P,
                                  C.c_int32, C.c_double, _P, _P, _P, C.c_int32, C.c_int32, _P]),
+    "bp_plane_blend_fields": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_int32, _P, C.c_int32, C.c_double, _P, _P, _P, C.c_int32, C.c_int32, _P]),
     "bp_plane_finish": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
     "bp_plane_project_order_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "bp_plane_project_order": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_double, C.c_int32, _P, C.c_size_t, _P, C.c_int32,

@@ -8,6 +8,9 @@
 //   bp_paint_load_mode / bp_paint_load2_mode / bp_paint_store_mode   the same with any of the six range-compression modes
 //                     (range_compress.hpp) and records of four float64 per tile; the three above are these at mode
 //                     shift-log, reading their two-double tables
+//   bp_paint_store_fields   the store of a head with several label fields: per field bp_paint_store_mode's (one level)
+//                     or bp_paint_store_scales_mode's (several) expression with the field's own mode and records, in one
+//                     launch
 //   bp_paint_load_cam / bp_paint_store_cam   the same pair for the conditional GAN: its "shift-log-cam" transform into the
 //                     tanh range, log(x / sigma + 1) / k0 - k1 (painter.CGANPainter.transform), and the generator's tanh
 //                     head followed by the inverse, both evaluated in double as the host's NumPy expressions are
@@ -68,6 +71,56 @@ __global__ __launch_bounds__(RB) void paint_store_kernel(const float* src, int s
   if (softplus) v = softplus_f(v);
   // e.g. (np.exp(x * k) - 1) * std: float32 product, float32 exp, float32 subtraction, double product
   dst[i] = rc_inverse<M>(rc_record(xf, n), v);
+}
+
+// Modes of up to FIELDS_MAX label fields, four bits each, as a kernel argument (the entry point's array is the host's)
+constexpr int FIELDS_MAX = 64;
+constexpr int LEVELS_MAX = 16;
+struct FieldModes {
+  unsigned w[FIELDS_MAX / 8];
+};
+
+__device__ __forceinline__ float rc_inverse_of(int mode, const RcRec& r, float v) {
+  switch (mode) {
+    case RC_SHIFT_LOG: return rc_inverse<RC_SHIFT_LOG>(r, v);
+    case RC_LOG: return rc_inverse<RC_LOG>(r, v);
+    case RC_SHIFT_LOG_2P: return rc_inverse<RC_SHIFT_LOG_2P>(r, v);
+    case RC_LOG_TANH: return rc_inverse<RC_LOG_TANH>(r, v);
+    case RC_X_1PX: return rc_inverse<RC_X_1PX>(r, v);
+    default: return rc_inverse<RC_INV_X>(r, v);
+  }
+}
+
+// The head of a painter with several label fields: field f owns channels [f * levels, (f + 1) * levels) and plane
+// n * fields + f of the (n, fields, H, W) destination.  One thread per PIXEL (n, y, x) of the head, in pixel order: it
+// reads the fields * levels contiguous channels of its pixel -- a wave reads whole cache lines, and a head value is
+// fetched by one thread of the launch -- and writes one element to each field's plane, so that the lanes of a wave
+// write consecutive floats of a plane, field by field (the coalesced NCHW side of paint_store_kernel, its 32-bit index
+// arithmetic).  Per field the expression is paint_store_kernel's (levels == 1) or paint_store_scales_kernel's
+// (levels > 1) with that field's record.  The field loop is uniform over the wave, so the field's mode -- a run-time
+// value of the plane -- is a scalar branch; a workgroup that straddles tiles reads each lane's own records.
+__global__ __launch_bounds__(RB) void paint_store_fields_kernel(const float* src, int src_cs, int src_co, int fields,
+                                                                int levels, int used, FieldModes modes, PW pw,
+                                                                int softplus, const double* records, float* dst,
+                                                                unsigned hw, unsigned pixels) {
+#pragma clang fp contract(off)
+  const unsigned i = blockIdx.x * RB + threadIdx.x;             // pixel n * hw + yx
+  if (i >= pixels) return;
+  const unsigned nu = (hw & (hw - 1u)) == 0u ? i >> (__ffs((int)hw) - 1) : i / hw;              // (see paint_load_kernel)
+  const unsigned yx = i - nu * hw;
+  const float* s = src + (int64_t)i * src_cs + src_co;
+  for (int f = 0; f < fields; ++f) {
+    const int c0 = f * levels;
+    float v = 0.f;
+    for (int ch = 0; ch < used; ++ch) {
+      float t = pw_apply(pw, c0 + ch, s[c0 + ch]);
+      if (softplus) t = softplus_f(t);
+      v = ch == 0 ? t : v + t;                                  // ((c0 + c1) + c2) ...: NumPy's order for sum(axis=0)
+    }
+    const int mode = (int)((modes.w[f >> 3] >> ((f & 7) * 4)) & 15u);
+    const unsigned pl = nu * (unsigned)fields + (unsigned)f;    // plane of the destination; < n * fields
+    dst[(int64_t)pl * hw + yx] = rc_inverse_of(mode, rc_record(rc_table4(records), (int64_t)pl), v);
+  }
 }
 
 // The CGAN's pair.  Same thread-to-element maps as the two kernels above (NHWC order on the way in, NCHW order on the
@@ -207,6 +260,26 @@ int bp_paint_load2_mode(int32_t mode, const float* raw_nchw, int32_t c, const do
 int bp_paint_store_mode(int32_t mode, const bp_view* src, const bp_pointwise* pw, int32_t softplus, const double* records,
                         float* dst_nchw, void* stream) {
   return paint_store_any(mode, src, pw, softplus, rc_table4(records), dst_nchw, stream);
+}
+
+int bp_paint_store_fields(const int32_t* modes, int32_t fields, int32_t levels, int32_t include_original,
+                          const bp_view* src, const bp_pointwise* pw, int32_t softplus, const double* records,
+                          float* dst_nchw, void* stream) {
+  if (!modes || !bp_view_ok_any(src) || !records || !dst_nchw) return BP_EINVAL;
+  if (fields < 1 || levels < 1 || (int64_t)fields * levels != src->c) return BP_EINVAL;
+  for (int f = 0; f < fields; ++f)
+    if (modes[f] < 0 || modes[f] >= RC_MODES) return BP_EINVAL;
+  if (src->dtype != BP_F32 || levels > LEVELS_MAX || fields > FIELDS_MAX) return BP_EUNSUPPORTED;
+  const int64_t hw = (int64_t)src->h * src->w, pixels = (int64_t)src->n * hw;
+  if (pixels * src->c >= (int64_t)1 << 31) return BP_EUNSUPPORTED;
+  FieldModes fm{};
+  for (int f = 0; f < fields; ++f) fm.w[f >> 3] |= (unsigned)modes[f] << ((f & 7) * 4);
+  const int used = include_original && levels > 1 ? 1 : levels;       // (one level: the channel itself either way)
+  hipLaunchKernelGGL(paint_store_fields_kernel, dim3(nblocks(pixels)), dim3(RB), 0, bp_stream(stream), src->ptr,
+                     src->cstride, src->coff, (int)fields, (int)levels, used, fm, bp_pw(pw), softplus ? 1 : 0, records,
+                     dst_nchw, (unsigned)hw, (unsigned)pixels);
+  BP_CHECK_LAUNCH();
+  return BP_OK;
 }
 
 // The shift-log forms: the same kernels at RC_SHIFT_LOG over the tables of two doubles, {sigma, k} / {k, sigma}

@@ -6,6 +6,9 @@
 //                    mode="reflect") in float64 (prefilter along axis 0, then axis 1; tensor-product sampling)
 //   bp_plane_blend   acc += w * p, wsum += w for a batch of painted tiles, tile by tile in tile order, each product
 //                    formed in double from the float32 tile (the host loop's order: no atomics, no fused multiply-add)
+//   bp_plane_blend_fields  the same for the (n, fields, tile, tile) tiles of a painter with several label fields into
+//                    one accumulator plane per field, each field with its own regularisation mask: one launch over
+//                    (field, pixel)
 //   bp_plane_finish  acc / wsum (0 / 0 = NaN where no tile reaches, as in the reference)
 // The whole file is compiled without floating-point contraction: the host expressions these kernels restate round
 // every product and every sum separately.
@@ -201,6 +204,36 @@ __global__ __launch_bounds__(RB) void blend_kernel(const float* tiles, int n, in
   wsum[o] = s;
 }
 
+// blend_kernel for tiles of `fields` label fields, (n, fields, tile, tile): blockIdx.y is the field, whose accumulators
+// are plane blockIdx.y of acc / wsum and whose tile t is tiles[t * fields + f] with stats row t * fields + f; per field
+// the loop, its order and its arithmetic are blend_kernel's
+__global__ __launch_bounds__(RB) void blend_fields_kernel(const float* tiles, int n, int fields, int tile, const int* dst,
+                                                          int bx0, int by0, int bw, unsigned total, const double* weight,
+                                                          int reg, double reg_std, const double* stats, double* acc,
+                                                          double* wsum, int rows, int cols) {
+  const unsigned i = blockIdx.x * RB + threadIdx.x;
+  if (i >= total) return;
+  const int f = blockIdx.y;
+  const unsigned ry = i / (unsigned)bw;
+  const int x = bx0 + (int)ry, y = by0 + (int)(i - ry * (unsigned)bw);
+  const int64_t o = (int64_t)f * rows * cols + (int64_t)x * cols + y;
+  double a = acc[o], s = wsum[o];
+  const size_t tt = (size_t)tile * tile;
+  for (int t = 0; t < n; ++t) {
+    const int lx = x - dst[2 * t], ly = y - dst[2 * t + 1];
+    if (lx < 0 || lx >= tile || ly < 0 || ly >= tile) continue;
+    const int l = lx * tile + ly;
+    const size_t tf = (size_t)t * fields + f;
+    const double p = (double)tiles[tf * tt + l];
+    double w = weight[l];
+    if (reg && fabs(p - stats[2 * tf]) > stats[2 * tf + 1] * reg_std) w = 0.0;
+    a += w * p;
+    s += w;
+  }
+  acc[o] = a;
+  wsum[o] = s;
+}
+
 __global__ __launch_bounds__(RB) void finish_kernel(const double* acc, const double* wsum, int64_t count, double* out) {
   const int64_t i = (int64_t)blockIdx.x * RB + threadIdx.x;
   if (i < count) out[i] = acc[i] / wsum[i];
@@ -282,6 +315,29 @@ int bp_plane_blend(const float* tiles, int32_t n, int32_t tile, const int32_t* d
   hipLaunchKernelGGL(blend_kernel, dim3(nblocks(total)), dim3(RB), 0, sm, tiles, n, tile, dst, bx0, by0, by1 - by0,
                      (unsigned)total, weight, regularise ? 1 : 0, regularise_std, (const double*)stats, acc, wsum,
                      cols);
+  BP_CHECK_LAUNCH();
+  return BP_OK;
+}
+
+int bp_plane_blend_fields(const float* tiles, int32_t n, int32_t fields, int32_t tile, const int32_t* dst, int32_t bx0,
+                          int32_t by0, int32_t bx1, int32_t by1, const double* weight, int32_t regularise,
+                          double regularise_std, double* stats, double* acc, double* wsum, int32_t rows, int32_t cols,
+                          void* stream) {
+  if (!tiles || !dst || !weight || !acc || !wsum || n <= 0 || fields <= 0 || tile <= 0 || rows <= 0 || cols <= 0 ||
+      (regularise && !stats) || bx0 < 0 || by0 < 0 || bx1 > rows || by1 > cols || bx0 >= bx1 || by0 >= by1)
+    return BP_EINVAL;
+  if ((int64_t)rows * cols >= ((int64_t)1 << 31) || (int64_t)n * fields * tile * tile >= ((int64_t)1 << 31) ||
+      fields > 65535)                                                          // (grid y)
+    return BP_EUNSUPPORTED;
+  const hipStream_t sm = bp_stream(stream);
+  if (regularise) {       // a field's tile is a contiguous (tile, tile) image: tile_stats_kernel's row t * fields + f
+    hipLaunchKernelGGL(tile_stats_kernel, dim3(n * fields), dim3(RB), 0, sm, tiles, tile * tile, stats);
+    BP_CHECK_LAUNCH();
+  }
+  const int64_t total = (int64_t)(bx1 - bx0) * (by1 - by0);
+  hipLaunchKernelGGL(blend_fields_kernel, dim3(nblocks(total), fields), dim3(RB), 0, sm, tiles, n, fields, tile, dst, bx0,
+                     by0, by1 - by0, (unsigned)total, weight, regularise ? 1 : 0, regularise_std, (const double*)stats,
+                     acc, wsum, rows, cols);
   BP_CHECK_LAUNCH();
   return BP_OK;
 }

@@ -79,8 +79,11 @@ def paint_plane(painter, delta, tile_relative_size, n_pixel_tile, z, min_tile_ov
     every call: like the reference (fresh ``torch.randn`` per tile, cvae.py:64) two planes never share their latent
     noise unless asked to, and ``torch.manual_seed`` makes a whole light cone reproducible.  Pass an explicit ``seed``
     (+ distinct ``first_tile_id`` ranges) to reproduce one plane.  Painters / transforms the device pipeline has no
-    form for (no transform, several label fields, L != 1) go through
-    ``paint_batch`` as before.
+    form for (no transform, L != 1) go through ``paint_batch`` as before.
+
+    A painter with F > 1 label fields paints (N, F, H, W) tiles on either path and the result is (F, n_plane, n_plane):
+    field j's plane is blended from field j's tiles alone, with its own ``regularise_std`` mask; ``out`` has that
+    shape too.
 
     ``on_device=True`` (opt-in; needs ``painter.can_paint_stream(z)``, NotImplementedError otherwise, raised before any
     random number is drawn or any graph is captured): the plane is uploaded once -- or used in place if ``delta`` is a
@@ -117,11 +120,20 @@ def paint_plane(painter, delta, tile_relative_size, n_pixel_tile, z, min_tile_ov
                                        seed=seed)
     if painted is None:
         painted = painter.paint_batch(np.stack(tiles), z, batch_size=batch_size)
+    if np.ndim(painted) == 4:                    # (N, F, H, W): one plane per label field, each with its own mask
+        return np.stack([_blend_host(painted[:, f], slices, n_plane, falloff, sigma, regularise_std)
+                         for f in range(painted.shape[1])])
+    return _blend_host(painted, slices, n_plane, falloff, sigma, regularise_std)
+
+
+def _blend_host(painted, slices, n_plane, falloff, sigma, regularise_std):
+    """The blend of ``paint_plane`` (process_SLICS.py:205-220): the painted tiles of ONE field, in tile order, weighted by
+    ``make_weight_map`` (zeroed beyond ``regularise_std`` tile standard deviations), accumulated and divided."""
     plane = np.zeros((n_plane, n_plane))
     weight = np.zeros((n_plane, n_plane))
     it = iter(painted)
-    for j in range(len(origins)):
-        for k in range(len(origins)):
+    for j in range(len(slices)):
+        for k in range(len(slices)):
             p = next(it)
             w = make_weight_map(p.shape, falloff=falloff, sigma=sigma)
             if regularise_std is not None:
@@ -319,8 +331,22 @@ def _streams(painter, z):
     return hasattr(painter, "paint_stream") and getattr(painter, "can_paint_stream", lambda z=0.0: True)(z)
 
 
+def _field_index(painter, field):
+    """Which label field of ``painter`` a light cone projects: None for a painter with one label field (``field`` may
+    name it), the index of ``field`` for a painter with several -- ValueError without a name or for a name the painter
+    does not paint.  Draws no random number."""
+    fields = list(getattr(painter, "label_fields", None) or [])
+    if field is not None and fields and field not in fields:
+        raise ValueError(f"field {field!r} is not one of the painter's label fields {fields}")
+    if len(fields) > 1:
+        if field is None:
+            raise ValueError(f"a painter with the label fields {fields} needs field=<one of them>")
+        return fields.index(field)
+    return None
+
+
 def paint_small_plane(painter, massplane, shift, delta_size, tile_size, mass_size, n_pixel_tile, z, seed=None,
-                      tile_id=0, subtract_minimum=False):
+                      tile_id=0, subtract_minimum=False, field=None):
     """Paint a plane whose footprint ``delta_size`` is smaller than the network's tile ``tile_size`` (the low-redshift
     branch of ``process_SLICS``, process_SLICS.py:149-176): ONE tile, expanded to the network's size around the
     footprint, is cut with wrap-around at ``shift`` from the periodic mass plane of ``mass_size`` (all three sizes in
@@ -331,8 +357,10 @@ def paint_small_plane(painter, massplane, shift, delta_size, tile_size, mass_siz
     One tile per plane: cut and zoom stay on the host.  A painter with a device pipeline for this redshift
     (``can_paint_stream``) paints through ``paint_stream`` with the Philox key (``seed``, ``tile_id``); ``seed=None``
     draws a fresh key from torch's global generator.  Any other painter goes through ``paint``.  The plane is returned
-    as float64, like ``paint_plane``'s."""
+    as float64, like ``paint_plane``'s.  ``field``: the label field to return, needed for a painter with several
+    (ValueError without it, before any random number is drawn)."""
     import scipy.ndimage
+    j = _field_index(painter, field)
     tile = get_tile(massplane, shift, tile_relative_size=delta_size / mass_size,
                     expansion_factor=tile_size / delta_size)
     if subtract_minimum:
@@ -348,6 +376,8 @@ def paint_small_plane(painter, massplane, shift, delta_size, tile_size, mass_siz
                                        tile_ids=np.array([tile_id], dtype=np.int64), seed=seed)[0]
     else:
         painted = painter.paint(input=tile, z=z, transform=True, inverse_transform=True)
+    if j is not None:
+        painted = painted[j]
     centre = (1 - delta_size / tile_size) / 2
     # (float64 like paint_plane's planes: the projection then scales a float32 tile in double on either path)
     return get_tile(np.asarray(painted, dtype=np.float64), shift=(centre, centre),
@@ -356,7 +386,7 @@ def paint_small_plane(painter, massplane, shift, delta_size, tile_size, mass_siz
 
 def paint_light_cone(painter, planes, z, delta_size, tile_size, n_pixel_tile, resolution, scales, min_tile_overlap=0.5,
                      falloff=0.05, sigma=0.5, regularise_std=None, batch_size=64, order=3, subtract_minimum=False,
-                     on_device=False, seed=None, out=None, return_planes=False):
+                     on_device=False, seed=None, out=None, return_planes=False, field=None):
     """Mass planes in, one y map out (``process_SLICS`` followed by ``create_y_map``'s loop, process_SLICS.py:147-220 and
     55-64): plane i of the light cone is painted at redshift ``z[i]`` and projected into the (resolution, resolution)
     map with the factor ``scales[i]`` (``y_map_scales``) at once; no list of painted planes is kept.
@@ -379,10 +409,17 @@ def paint_light_cone(painter, planes, z, delta_size, tile_size, n_pixel_tile, re
     or nothing with ``out`` (a CUDA float64 (resolution, resolution) tensor that is accumulated into and returned).
     Small planes are painted as on the host path and uploaded.
 
+    ``field``: a painter with several label fields paints all of them from one latent draw, and the map is made of
+    ONE: ``field`` names it (ValueError without it or for a name the painter does not paint, before any random number is
+    drawn).  That field's plane is the one projected and, with ``return_planes``, kept; on the device it is a slice of
+    the (F, n_plane, n_plane) buffer ``paint_plane`` blends into.  A painter with one label field needs no ``field``.
+
     Returns the map, or (map, painted planes as host arrays) with ``return_planes=True``."""
     z, delta_size = list(z), list(delta_size)
     if not len(z) == len(delta_size) == len(scales):
         raise ValueError("z, delta_size and scales need one entry per plane")
+    j = _field_index(painter, field)
+    n_f = len(painter.label_fields) if j is not None else 1
     if out is not None and not on_device:
         raise ValueError("out= needs on_device=True")
     # eligibility is decided UP FRONT, as in paint_plane: no random number is drawn for a light cone that cannot run
@@ -419,19 +456,22 @@ def paint_light_cone(painter, planes, z, delta_size, tile_size, n_pixel_tile, re
             tile_id += geo["n_side"] ** 2
             if on_device:
                 n_plane = geo["n_plane"]
-                if buf is None or buf.numel() < n_plane * n_plane:
+                if buf is None or buf.numel() < n_f * n_plane * n_plane:
                     buf = None                                   # (let go of the smaller one first)
-                    buf = torch.empty(n_plane * n_plane, dtype=torch.float64, device=dev)
+                    buf = torch.empty(n_f * n_plane * n_plane, dtype=torch.float64, device=dev)
+                shape = (n_plane, n_plane) if j is None else (n_f, n_plane, n_plane)
                 plane = paint_plane(painter, entry, rel, n_pixel_tile, z[i], on_device=True,
-                                    out=buf[:n_plane * n_plane].view(n_plane, n_plane), **kw)
+                                    out=buf[:n_f * n_plane * n_plane].view(shape), **kw)
             else:
                 plane = paint_plane(painter, entry, rel, n_pixel_tile, z[i], **kw)
+            if j is not None:
+                plane = plane[j]                                 # (a contiguous slice of the fields' planes)
         else:
             massplane, shift, mass_size = entry
             if on_device:                                        # paint_stream copies on streams of its own
                 torch.cuda.current_stream(dev).synchronize()
             plane = paint_small_plane(painter, massplane, shift, delta_size[i], tile_size, mass_size, n_pixel_tile,
-                                      z[i], seed=seed, tile_id=tile_id, subtract_minimum=subtract_minimum)
+                                      z[i], seed=seed, tile_id=tile_id, subtract_minimum=subtract_minimum, field=field)
             tile_id += 1
             if on_device:
                 host = plane

@@ -82,22 +82,29 @@ def conv_up(in_channel, channels, scales, **kw_args):
     return _chain(in_channel, channels, scales, type="transp conv", **kw_args)
 
 
-def fiducial_architecture(tile_size=512, predict_var=False, n_res=4, n_scale=1, p_y_in=None, prior=True):
+def fiducial_architecture(tile_size=512, predict_var=False, n_res=4, n_scale=1, p_y_in=None, prior=True, n_fields=1):
     """The "CVAE fiducial" network: trained_models/CVAE/fiducial/architecture.txt
     (mean head only); ``predict_var=True`` gives the two-head superset that
     scripts/CVAE_single_scale.py:97-138 builds.  dim_z = tile_size/32.
 
     ``n_scale``: channels per field of a multi-scale painter (the ``n_feature_per_field`` of its data set: the levels
     of ``data_transforms.create_split_scale_transform``, the original included where it is kept), from which the
-    script derives dim_y, dim_x = n_x_features (one label field) and the generator's stem
+    script derives dim_y, dim_x = n_x_features (times ``n_fields``, below) and the generator's stem
     (CVAE_single_scale.py:92-95,113); the stems that read y -- prior_z_y, q_y_in -- and q_x_in take that many channels
     plus the aux label, and the heads end in n_x_features channels.
 
     ``p_y_in``: a layer list for the generator's conditioning stem (cvae.py:106), passed through; it reads the
     n_scale + 1 channels of y with the aux label, keeps the resolution, and the generator's first convolution then takes
     its output channels beside h_z.  None (default): the identity, as in the reference's configurations.
-    ``prior=False`` leaves ``prior_z_y`` out: the standard-normal prior of cvae.py:83-85."""
-    n_aux_label, n_x_feature = 1, n_scale
+    ``prior=False`` leaves ``prior_z_y`` out: the standard-normal prior of cvae.py:83-85.
+
+    ``n_fields``: the number of label fields painted from one latent draw (``len(label_fields)`` of the data set):
+    dim_x[0] = n_x_features = n_fields * n_scale (CVAE_single_scale.py:92), field j in channels
+    [j * n_scale, (j + 1) * n_scale); q_x_in and the heads are sized to match, dim_y and the stems that read y are
+    not touched."""
+    if n_fields < 1:
+        raise ValueError("n_fields must be at least 1")
+    n_aux_label, n_x_feature = 1, n_fields * n_scale
     c_hy = n_aux_label + n_scale
     for layer in p_y_in or []:
         if layer[0].lower() in ("conv", "sn conv", "transp conv"):

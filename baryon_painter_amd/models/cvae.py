@@ -1009,7 +1009,13 @@ class CVAE(torch.nn.Module):
         ``modes`` (a painter whose fields are not both "shift-log"): the (input, label) range-compression mode numbers
         (data_transforms.MODE_IDS).  The load and store nodes are then the ``_mode`` entry points, which hold the mode as
         a constant of the graph, and ``xf_in`` / ``xf_out`` are (n, 4) float64: the records of
-        ``data_transforms.DeviceRangeCompress.records``.  Without it nothing changes."""
+        ``data_transforms.DeviceRangeCompress.records``.  Without it nothing changes.
+
+        Several label fields (F > 1, a head of dim_x[0] = F * levels channels, field j in channels
+        [j * levels, (j + 1) * levels)): ``modes = (input mode, (mode of field 0, ...))``, whatever the modes are.  ``out``
+        is then (n, F, H, W), ``xf_out`` (n, 4 F) -- the fields' records side by side -- and the store node is
+        ``bp_paint_store_fields``: one launch for the whole head.  With ``scales`` the model needs dim_y[0] = levels and
+        dim_x[0] = F * levels."""
         if self.training:
             raise RuntimeError("paint_graph is an eval-mode (paint) path: call model.train(False) first")
         key = (n, "pipeline")
@@ -1017,7 +1023,10 @@ class CVAE(torch.nn.Module):
             scales = {"n_scale": int(scales["n_scale"]), "step_size": scales["step_size"],
                       "include_original": bool(scales["include_original"]), "truncate": scales.get("truncate", 3.0)}
             key = (n, "pipeline", "scales") + tuple(scales.values())
-        if modes is not None:
+        if modes is not None and isinstance(modes[1], (tuple, list)):
+            modes = (int(modes[0]), tuple(int(m) for m in modes[1]))
+            key = key + ("modes", modes[0], "fields") + modes[1]
+        elif modes is not None:
             modes = (int(modes[0]), int(modes[1]))
             key = key + ("modes",) + modes
         g = self._graphs.get(key)
@@ -1043,11 +1052,18 @@ class CVAE(torch.nn.Module):
         cy, H, W = self.dim_y
         cx = self.dim_x[0]
         dev = self.device
+        fields = len(modes[1]) if modes is not None and isinstance(modes[1], tuple) else 1
+        levels = 1
         if scales is not None:
             levels = scales["n_scale"] + int(scales["include_original"])
-            if not pipeline or cy != levels or cx != levels:
+            if not pipeline or cy != levels or cx != fields * levels:
                 raise ValueError(f"a {levels}-level split-scale transform needs dim_y[0] = dim_x[0] = {levels}, the "
-                                 f"model has {cy} and {cx}")
+                                 f"model has {cy} and {cx}" if fields == 1 else
+                                 f"{fields} label fields of a {levels}-level split-scale transform need dim_y[0] = "
+                                 f"{levels} and dim_x[0] = {fields * levels}, the model has {cy} and {cx}")
+        if fields > 1 and (not pipeline or cx != fields * levels):
+            raise ValueError(f"{fields} label fields of {levels} channel(s) need dim_x[0] = {fields * levels}, the model "
+                             f"has {cx}")
         st = {"y": None if pipeline else torch.zeros((n, cy, H, W), device=dev),
               "aux": torch.zeros((n, self.n_aux), device=dev) if self.use_aux_label and not pipeline else None,
               "out": None if pipeline else torch.zeros((n, cx, H, W), device=dev),
@@ -1062,10 +1078,12 @@ class CVAE(torch.nn.Module):
             per_tile = math.prod(self.dim_z)
             st["eps"] = torch.zeros((1, n, per_tile), device=dev)
             # parameter block of a slot: one contiguous device buffer = one host-to-device copy per batch
-            block = PG.ParamBlock(PG.paint_fields(n, 2 if modes is None else 4, max(self.n_aux, 1)))
+            block = PG.ParamBlock(PG.paint_fields(n, 2 if modes is None else 4, max(self.n_aux, 1),
+                                                  xf_out_width=4 * fields if fields > 1 else None))
             st["param_block"], st["block_layout"], st["block_bytes"] = block, block.layout, block.nbytes
             st["slots"] = [PG.new_slot((n, 1 if scales is not None else cy, H, W),
-                                       (n, 1 if scales is not None else cx, H, W), block, dev) for _ in range(2)]
+                                       (n, fields if fields > 1 else 1 if scales is not None else cx, H, W), block, dev)
+                           for _ in range(2)]
         parts = int(os.environ.get("BP_PAINT_STREAMS", "4"))
         while parts > 1 and (n % parts != 0 or n // parts < 8):
             parts -= 1
@@ -1101,6 +1119,14 @@ class CVAE(torch.nn.Module):
             def entry(name, mode):
                 return getattr(lib, name) if modes is None else functools.partial(getattr(lib, name + "_mode"), mode)
             m_in, m_out = modes if modes is not None else (None, None)
+            if fields > 1:
+                # one store launch for the whole head: every field's mode is a constant of the graph
+                field_modes = (C.c_int32 * fields)(*m_out)
+                inc = int(scales["include_original"]) if scales is not None else 0
+
+                def store_fields(plan, xf, out, sm):
+                    return lib.bp_paint_store_fields(field_modes, fields, levels, inc, C.byref(plan.mu_head.view), None,
+                                                     1 if plan.mu_softplus else 0, xf, out, sm)
             if scales is not None:
                 what = " (scales)"
                 load_fn, store_fn = entry("bp_paint_load_scales2", m_in), entry("bp_paint_store_scales", m_out)
@@ -1126,6 +1152,8 @@ class CVAE(torch.nn.Module):
 
                 def store(plan, xf, out, sm):
                     return store_fn(C.byref(plan.mu_head.view), None, 1 if plan.mu_softplus else 0, xf, out, sm)
+            if fields > 1:
+                store, what = store_fields, what + f" ({fields} fields)"
 
         def paint_pipeline(plan, lo, sl):
             sm = _stream()

@@ -36,12 +36,14 @@ class ParamBlock:
         return out
 
 
-def paint_fields(n, xf_width, aux_width=1):
+def paint_fields(n, xf_width, aux_width=1, xf_out_width=None):
     """The fields of a paint pipeline's block for batches of ``n`` tiles: ``xf_in`` / ``xf_out`` (n, xf_width) float64
     parameter rows of the transform and its inverse, ``tile_ids`` (n,) int64, ``seed`` (1,) int64 Philox key, ``aux``
     (n, aux_width) float32 value of the conditioning plane.  Both models carry all five, so that one caller fills either
-    model's block."""
-    return [("xf_in", torch.float64, (n, xf_width)), ("xf_out", torch.float64, (n, xf_width)),
+    model's block.  ``xf_out_width``: the width of ``xf_out`` where it differs (a CVAE with several label fields: the
+    fields' rows side by side)."""
+    return [("xf_in", torch.float64, (n, xf_width)),
+            ("xf_out", torch.float64, (n, xf_width if xf_out_width is None else xf_out_width)),
             ("tile_ids", torch.int64, (n,)), ("seed", torch.int64, (1,)), ("aux", torch.float32, (n, aux_width))]
 
 

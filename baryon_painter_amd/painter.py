@@ -46,8 +46,9 @@ class Painter:
     def release_paint_buffers(self):
         """Free what the device paint paths keep between calls: ``paint_stream``'s page-locked host staging buffers -- two
         parameter blocks plus up to four (batch, 1, H, W) fp32 buffers, 256 MiB of pinned memory at batch 64 of 512^2
-        tiles, which otherwise live as long as the painter (page-locking them costs tens of milliseconds per call, hence
-        the cache) -- and ``_paint_plane_device``'s accumulators and scratch."""
+        tiles ((batch, F, H, W) on the output side of a painter with F label fields), which otherwise live as long as the
+        painter (page-locking them costs tens of milliseconds per call, hence the cache) -- and
+        ``_paint_plane_device``'s accumulators and scratch."""
         self.__dict__.pop("_paint_host_buffers", None)
         self.__dict__.pop("_plane_device_buffers", None)
 
@@ -65,7 +66,10 @@ class Painter:
             [default: i], int64), so the result does not depend on ``batch_size`` or on how tiles are dealt to ranks;
             the seed travels in the per-batch parameter block: one captured graph serves every seed;
           * ``rank`` / ``world_size``: this process paints the contiguous block of tiles that is its share (one
-            process per GPU, no collective: tiles are independent) and returns (block, (lo, hi))."""
+            process per GPU, no collective: tiles are independent) and returns (block, (lo, hi));
+          * a CVAE painter with F > 1 label fields returns (N, F, H, W): field j from head channels
+            [j * nf, (j + 1) * nf) through ``label_fields[j]``'s inverse, all fields stored by one launch
+            (``bp_paint_store_fields``); ``out``, where given, has that shape."""
         model = self.model
         model.train(False)
         H, W = self._tile_shape()
@@ -88,7 +92,9 @@ class Painter:
         the device plane into a slot's ``raw`` (bp_plane_cut), the batch's parameter block is copied in from a per-plane
         device copy, the graph is replayed, and the slot's ``out`` is blended into float64 accumulators
         (bp_plane_blend); bp_plane_finish divides.  Returns the (n_plane, n_plane) float64 plane, or ``out`` (a CUDA
-        float64 tensor of that shape) filled in place."""
+        float64 tensor of that shape) filled in place.  A painter with F > 1 label fields blends its (B, F, tile, tile)
+        ``out`` with bp_plane_blend_fields, each field into a plane of its own with its own regularisation mask: the
+        plane, and ``out``, is (F, n_plane, n_plane)."""
         model = self.model
         model.train(False)
         tile, W = self._tile_shape()
@@ -332,8 +338,21 @@ class CVAEPainter(Painter):
             return x.cpu().numpy(), y.cpu().numpy(), x_pred.cpu().numpy()
 
     # ------------------------------------------------------------------------------ inference
+    def _inverse_fields(self, head, z):
+        """One tile's head (F * nf, H, W) of a painter with F > 1 label fields -> (F, H, W) physical tiles: field j owns
+        channels [j * nf, (j + 1) * nf) and is inverted as ``label_fields[j]`` (the reference's slicing,
+        validation_plotting.py:109-110)."""
+        F = len(self.label_fields)
+        if head.shape[0] % F:
+            raise ValueError(f"a head of {head.shape[0]} channels does not split into {F} label fields")
+        nf = head.shape[0] // F
+        return np.stack([self.inverse_transform(head[j * nf:(j + 1) * nf][None] if nf == 1 else head[j * nf:(j + 1) * nf],
+                                                field=f, z=z) for j, f in enumerate(self.label_fields)])
+
     def paint(self, input, z=0.0, transform=True, inverse_transform=True):
-        """Paint one tile (painter.py:371-392): dark-matter tile (H,W) at redshift z -> pressure."""
+        """Paint one tile (painter.py:371-392): dark-matter tile (H,W) at redshift z -> pressure.  A painter with F > 1
+        label fields returns (F, H, W), field j from head channels [j * nf, (j + 1) * nf) (where the reference raises
+        NotImplementedError, painter.py:388-389); ``inverse_transform=False`` gives the (1, F * nf, H, W) head."""
         self.model.train(False)
         with torch.no_grad():
             y = self.transform(input, field=self.input_field, z=z) if transform and self.transform is not None \
@@ -347,7 +366,7 @@ class CVAEPainter(Painter):
             prediction = self.model.sample_P(yt, aux_label=aux).cpu().numpy()
         if inverse_transform and self.inverse_transform is not None:
             if len(self.label_fields) > 1:
-                raise NotImplementedError("Painting with more than one output field is not supported yet.")
+                return self._inverse_fields(prediction[0], z)
             if prediction.shape[1] != 1:       # a multi-scale head: the inverse takes one tile's (cx, H, W) channels
                 return self.inverse_transform(prediction[0], field=self.label_fields[0], z=z)
             return self.inverse_transform(prediction, field=self.label_fields[0], z=z)
@@ -356,7 +375,8 @@ class CVAEPainter(Painter):
     def paint_batch(self, inputs, z, transform=True, inverse_transform=True, batch_size=64, use_graph=True):
         """Throughput form of ``paint``: many tiles (N,H,W) with redshifts (N,) in batches through the
         same eval-mode forward (BASELINE.json configs[4]); per-tile results equal ``paint``'s up to
-        the prior noise draw."""
+        the prior noise draw.  (N, H, W), or (N, F, H, W) for a painter with F > 1 label fields, each field through
+        its own inverse (``_inverse_fields``)."""
         self.model.train(False)
         inputs = np.asarray(inputs)
         zs = np.broadcast_to(np.asarray(z, dtype=np.float64), (inputs.shape[0],))
@@ -376,7 +396,9 @@ class CVAEPainter(Painter):
                 graphed = use_graph and self.model._eps_override is None and yt.shape[0] == batch_size
                 sample = self.model.sample_P_graphed if graphed else self.model.sample_P
                 pred = sample(yt, aux_label=aux).cpu().numpy()
-                if inverse_transform and self.inverse_transform is not None:
+                if inverse_transform and self.inverse_transform is not None and len(self.label_fields) > 1:
+                    pred = np.stack([self._inverse_fields(p, float(zz)) for p, zz in zip(pred, zc)])
+                elif inverse_transform and self.inverse_transform is not None:
                     pred = np.stack([self.inverse_transform(p[None] if p.shape[0] == 1 else p,
                                                             field=self.label_fields[0], z=float(zz))
                                      for p, zz in zip(pred, zc)])
@@ -390,7 +412,10 @@ class CVAEPainter(Painter):
         ``CVAE.paint_graph``'s block, the description of a multi-scale painter's split-scale transform (``paint_graph``'s
         ``scales``) or None, and ``modes``: None where both fields are "shift-log" (rows {sigma, k} / {k, sigma}, the
         pipeline as it always was), else the (input, label) mode numbers (rows: the four-double records of
-        csrc/range_compress.hpp).  Anything else has no device form.  The chains with one:
+        csrc/range_compress.hpp).  With F > 1 label fields ``xf_out`` is (n, F, 4), the records of each field, and
+        ``modes`` is (input mode, (mode of field 0, ...)): the four-double form on both sides whatever the modes are;
+        every field's inverse chain must have a device form, and all of them share the split-scale parameters.
+        Anything else has no device form.  The chains with one:
           single scale   any order of ONE range compression and the shape-only steps;
           multi scale    forward  [range compression, as_float32 (optional), split-scale, shape-only steps ...]
                          inverse  [inverse split-scale, inverse range compression, shape-only steps ...]
@@ -415,19 +440,29 @@ class CVAEPainter(Painter):
 
         def has_split(compiled):
             return compiled is not None and T.has_split_scale(getattr(compiled, "func", None))
-        if len(self.label_fields) != 1:
-            raise NotImplementedError("Painting with more than one output field is not supported yet.")
+        if len(self.label_fields) < 1:
+            raise NotImplementedError("a painter without a label field has nothing to paint")
         scales = None
+        outs = []                                      # per label field: (range compression, the field's statistics)
         if has_split(self.transform) or has_split(self.inverse_transform):
             (rc_in, st_in), fs = find_scales(self.transform, 0, self.input_field)
-            (rc_out, st_out), bs = find_scales(self.inverse_transform, 1, self.label_fields[0])
-            if (fs.n_scale, fs.include_original) != (bs.n_scale, bs.include_original):
-                raise NotImplementedError("the split-scale transform and its inverse differ in n_scale / include_original")
+            for f in self.label_fields:
+                out_f, bs = find_scales(self.inverse_transform, 1, f)
+                outs.append(out_f)
+                if (fs.n_scale, fs.include_original) != (bs.n_scale, bs.include_original):
+                    raise NotImplementedError("the split-scale transform and its inverse differ in n_scale / "
+                                              "include_original")
             scales = {"n_scale": fs.n_scale, "step_size": fs.step_size, "include_original": fs.include_original,
                       "truncate": fs.truncate}
         else:
             rc_in, st_in = find(self.transform, 0, self.input_field)
-            rc_out, st_out = find(self.inverse_transform, 1, self.label_fields[0])
+            outs = [find(self.inverse_transform, 1, f) for f in self.label_fields]
+        if len(outs) > 1:
+            # several label fields: records on both sides, one (n, 4) table per field side by side, and every field's mode
+            xf_out = np.stack([rc.records(st, zs) for rc, st in outs], axis=1)
+            return ({"xf_in": rc_in.records(st_in, zs), "xf_out": xf_out, "aux": np.asarray(zs, dtype=np.float64)}, scales,
+                    (rc_in.mode, tuple(rc.mode for rc, _ in outs)))
+        rc_out, st_out = outs[0]
         xf_in, xf_out = rc_in.records(st_in, zs), rc_out.records(st_out, zs)      # (vectorised: no Python call per tile)
         modes = (rc_in.mode, rc_out.mode)
         if rc_in.name == rc_out.name == "shift-log":
@@ -441,16 +476,26 @@ class CVAEPainter(Painter):
         return f"Shape mismatch between input and model: {shape} vs {self.model.dim_y}"
 
     def _device_paint_parameters(self, zs):
-        """``_transform_parameters(zs)`` where this painter has a device form -- one label field, one of the six range
-        compressions on either side and L = 1, with or without a prior network or a p_y_in network; single-channel
+        """``_transform_parameters(zs)`` where this painter has a device form -- one of the six range compressions on
+        either side (one per label field) and L = 1, with or without a prior network or a p_y_in network; single-channel
         tiles, or a split-scale transform in the orders ``_transform_parameters`` names whose levels are the model's
-        dim_y[0] = dim_x[0], without a p_y_in network -- and NotImplementedError where it has none.  No side effects."""
+        dim_y[0] = dim_x[0], without a p_y_in network; with F > 1 label fields dim_x[0] = F * dim_y[0] -- and
+        NotImplementedError where it has none.  No side effects."""
         model = self.model
         if getattr(model, "L", 1) != 1:
             raise NotImplementedError("the captured paint pipeline needs L = 1 (paint / paint_batch take any L)")
         params, scales, modes = self._transform_parameters(zs)
         cy, cx = model.dim_y[0], model.dim_x[0]
-        if scales is None:
+        F = len(self.label_fields)
+        if F > 1:
+            levels = 1 if scales is None else scales["n_scale"] + int(scales["include_original"])
+            if scales is not None and getattr(model, "has_p_y_in", False):
+                raise NotImplementedError("the device paint path takes split-scale tiles only for models without a "
+                                          "p_y_in network")
+            if cy != levels or cx != F * levels:
+                raise NotImplementedError(f"the device paint path needs dim_y[0] = {levels} and dim_x[0] = {F * levels} "
+                                          f"for {F} label fields of {levels} channel(s), the model has {cy} and {cx}")
+        elif scales is None:
             if cy != 1:
                 raise NotImplementedError("the device paint path takes single-channel input tiles (or a split-scale "
                                           "transform's levels)")
@@ -523,7 +568,7 @@ def _fill_block(hv, params, ids, a, b, B):
     """Tiles [a, b) of ``params`` / ``ids`` into the views of one block of ``B`` rows."""
     m = b - a
     hv["xf_in"][:m] = params["xf_in"][a:b]
-    hv["xf_out"][:m] = params["xf_out"][a:b]
+    hv["xf_out"][:m] = params["xf_out"][a:b].reshape(m, -1)       # (several label fields: (m, F, 4) -> (m, 4 F))
     hv["aux"][:m, 0] = params["aux"][a:b]
     hv["tile_ids"][:m] = ids[a:b]
     if m < B:                                     # a short last batch: pad with its last tile's parameters
@@ -537,6 +582,11 @@ def _paint_graph(model, B, scales, modes):
     return model.paint_graph(B, **kw)
 
 
+def _n_fields(modes):
+    """The number of label fields ``modes`` speaks of: (input mode, (mode of field 0, ...)) for several, 1 otherwise."""
+    return len(modes[1]) if modes is not None and isinstance(modes[1], (tuple, list)) else 1
+
+
 def _seed_word(seed):
     return np.array(int(seed) & 0xFFFFFFFFFFFFFFFF, dtype=np.uint64).astype(np.int64)
 
@@ -547,12 +597,18 @@ def _paint_stream_pipeline(painter, model, inputs, tile_shape, lo, hi, B, params
     (``CVAEPainter.paint_stream``).  ``params`` and ``ids`` hold those tiles only.  Returns the (hi - lo, H, W) float32
     result (``out`` if given).  ``scales``: a multi-scale CVAE painter's split-scale description (``CVAE.paint_graph``);
     raw tiles and painted tiles are single-channel either way.  ``modes``: a CVAE painter's (input, label)
-    range-compression modes where they are not both shift-log (``CVAE.paint_graph``)."""
+    range-compression modes where they are not both shift-log (``CVAE.paint_graph``), or (input mode, (mode of field 0,
+    ...)) of a painter with F > 1 label fields: the result, the slots' ``out`` and the pinned output buffers are then
+    (.., F, H, W), and ``out``, where given, must have the result's shape."""
     H, W = tile_shape
     dev = model.device
+    F = _n_fields(modes)
+    shape = (hi - lo, F, H, W) if F > 1 else (hi - lo, H, W)
+    if F > 1 and out is not None and tuple(out.shape) != shape:
+        raise ValueError(f"out must have the shape {shape} of {F} label fields, got {tuple(out.shape)}")
     g = _paint_graph(model, B, scales, modes)
     torch_in = isinstance(inputs, torch.Tensor)
-    result = out if out is not None else np.empty((hi - lo, H, W), np.float32)
+    result = out if out is not None else np.empty(shape, np.float32)
     torch_out = isinstance(result, torch.Tensor)
     main = torch.cuda.current_stream(dev)
     up, down = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
@@ -562,7 +618,7 @@ def _paint_stream_pipeline(painter, model, inputs, tile_shape, lo, hi, B, params
     # pinned host buffers are kept between calls (page-locking 4 x 64 MiB costs tens of milliseconds per call);
     # release_paint_buffers() frees them; the tile buffers are only allocated for NumPy inputs / outputs
     cache = painter.__dict__.setdefault("_paint_host_buffers", {})
-    key = (B, H, W, g["block_bytes"], str(dev))
+    key = (B, H, W, g["block_bytes"], str(dev)) + ((F,) if F > 1 else ())
     if key not in cache:
         cache.clear()
         cache[key] = [{"h_blk": torch.zeros(g["block_bytes"], dtype=torch.uint8).pin_memory(), "h_in": None,
@@ -575,7 +631,7 @@ def _paint_stream_pipeline(painter, model, inputs, tile_shape, lo, hi, B, params
         if not torch_in and hb["h_in"] is None:
             hb["h_in"] = torch.empty((B, 1, H, W), dtype=torch.float32).pin_memory()
         if not torch_out and hb["h_out"] is None:
-            hb["h_out"] = torch.empty((B, 1, H, W), dtype=torch.float32).pin_memory()
+            hb["h_out"] = torch.empty((B, F, H, W), dtype=torch.float32).pin_memory()
         slots.append({"g": gs, "h_blk": h_blk, "hv": hv, "h_in": hb["h_in"], "h_out": hb["h_out"],
                       "ev_up": torch.cuda.Event(), "ev_done": torch.cuda.Event(), "ev_down": torch.cuda.Event(),
                       "pending": None})
@@ -586,7 +642,7 @@ def _paint_stream_pipeline(painter, model, inputs, tile_shape, lo, hi, B, params
         a, b = sl["pending"]
         sl["ev_down"].synchronize()
         if not torch_out:
-            result[a - lo:b - lo] = sl["h_out"][:b - a, 0].numpy()
+            result[a - lo:b - lo] = sl["h_out"][:b - a].numpy() if F > 1 else sl["h_out"][:b - a, 0].numpy()
         sl["pending"] = None
 
     starts = list(range(lo, hi, B))
@@ -631,7 +687,7 @@ def _paint_stream_pipeline(painter, model, inputs, tile_shape, lo, hi, B, params
             sl["ev_done"].record(main)
             down.wait_event(sl["ev_done"])
             with torch.cuda.stream(down):
-                dst = result[a - lo:b - lo].reshape(m, 1, H, W) if torch_out else sl["h_out"][:m]
+                dst = result[a - lo:b - lo].reshape(m, F, H, W) if torch_out else sl["h_out"][:m]
                 dst.copy_(gs["out"][:m], non_blocking=True)
                 sl["ev_down"].record(down)
             sl["pending"] = (a, b)
@@ -644,12 +700,16 @@ def _paint_stream_pipeline(painter, model, inputs, tile_shape, lo, hi, B, params
 def _paint_plane_pipeline(painter, model, tile, delta, geo, B, params, tile_ids, seed, weight_map, regularise_std, out,
                           scales=None, modes=None):
     """One plane through ``model.paint_graph(B)`` on the device (``CVAEPainter._paint_plane_device``): cut, parameter
-    block, replay, blend per batch on ONE stream, then the division."""
+    block, replay, blend per batch on ONE stream, then the division.  ``modes`` of F > 1 label fields: the slots' ``out``
+    is (B, F, tile, tile), blended by ``bp_plane_blend_fields`` into one accumulator plane per field; the result (and
+    ``out``) is (F, n_plane, n_plane)."""
     import ctypes as C
     from . import _lib as L
     dev = model.device
     cut, n_plane = geo["cut"], geo["n_plane"]
     n = len(geo["origins"])
+    F = _n_fields(modes)
+    shape = (F, n_plane, n_plane) if F > 1 else (n_plane, n_plane)
     if isinstance(delta, torch.Tensor):
         if delta.device != torch.device(dev):
             raise ValueError(f"delta lives on {delta.device}, the painter on {dev}")
@@ -659,9 +719,9 @@ def _paint_plane_pipeline(painter, model, tile, delta, geo, B, params, tile_ids,
     if d.dim() != 2 or d.dtype not in (torch.float32, torch.float64):
         raise TypeError("delta must be a 2-d float32 or float64 plane")
     if out is not None and (not isinstance(out, torch.Tensor) or out.device != torch.device(dev) or
-                            out.dtype != torch.float64 or tuple(out.shape) != (n_plane, n_plane) or
+                            out.dtype != torch.float64 or tuple(out.shape) != shape or
                             not out.is_contiguous()):
-        raise ValueError(f"out must be a contiguous float64 ({n_plane}, {n_plane}) tensor on {dev}")
+        raise ValueError(f"out must be a contiguous float64 ({', '.join(str(v) for v in shape)}) tensor on {dev}")
     g = _paint_graph(model, B, scales, modes)
     # per-plane parameter blocks, one per batch, built like paint_stream's pinned ones and uploaded once: a batch
     # then costs one device-to-device copy of its block into the slot
@@ -676,16 +736,16 @@ def _paint_plane_pipeline(painter, model, tile, delta, geo, B, params, tile_ids,
     # accumulators and the resampling scratch are kept between calls (release_paint_buffers() frees them)
     cache = painter.__dict__.setdefault("_plane_device_buffers", {})
     ws = int(lib.bp_plane_cut_workspace(B, cut, tile))
-    key = (n_plane, B, ws, str(dev))
+    key = (n_plane, B, ws, str(dev)) + ((F,) if F > 1 else ())
     if key not in cache:
         cache.clear()
-        cache[key] = {"acc": torch.empty((n_plane, n_plane), dtype=torch.float64, device=dev),
-                      "wsum": torch.empty((n_plane, n_plane), dtype=torch.float64, device=dev),
+        cache[key] = {"acc": torch.empty(shape, dtype=torch.float64, device=dev),
+                      "wsum": torch.empty(shape, dtype=torch.float64, device=dev),
                       "scratch": torch.empty(max(ws // 8, 1), dtype=torch.float64, device=dev),
-                      "stats": torch.empty(2 * B, dtype=torch.float64, device=dev)}
+                      "stats": torch.empty(2 * B * F, dtype=torch.float64, device=dev)}
     buf = cache[key]
     acc, wsum = buf["acc"], buf["wsum"]
-    result = out if out is not None else torch.empty((n_plane, n_plane), dtype=torch.float64, device=dev)
+    result = out if out is not None else torch.empty(shape, dtype=torch.float64, device=dev)
     with torch.no_grad():
         blocks_d = blocks.to(dev)
         org_d = torch.from_numpy(geo["origins"]).to(dev)
@@ -706,12 +766,13 @@ def _paint_plane_pipeline(painter, model, tile, delta, geo, B, params, tile_ids,
             gs["block"].copy_(blocks_d[bi])
             gs["graph"].replay()
             box = geo["dst"][a:b]
-            L.check(lib.bp_plane_blend(L.ptr(gs["out"]), m, tile, C.c_void_p(dst_d.data_ptr() + 8 * a),
-                                       int(box[:, 0].min()), int(box[:, 1].min()), int(box[:, 0].max()) + tile,
-                                       int(box[:, 1].max()) + tile, L.ptr(w_d), 1 if reg else 0,
-                                       float(regularise_std) if reg else 0.0, L.ptr(buf["stats"]), L.ptr(acc),
-                                       L.ptr(wsum), n_plane, n_plane, sm), "plane blend")
-        L.check(lib.bp_plane_finish(L.ptr(acc), L.ptr(wsum), n_plane * n_plane, L.ptr(result), sm), "plane finish")
+            blend = (lib.bp_plane_blend, (m,)) if F == 1 else (lib.bp_plane_blend_fields, (m, F))
+            L.check(blend[0](L.ptr(gs["out"]), *blend[1], tile, C.c_void_p(dst_d.data_ptr() + 8 * a),
+                             int(box[:, 0].min()), int(box[:, 1].min()), int(box[:, 0].max()) + tile,
+                             int(box[:, 1].max()) + tile, L.ptr(w_d), 1 if reg else 0,
+                             float(regularise_std) if reg else 0.0, L.ptr(buf["stats"]), L.ptr(acc),
+                             L.ptr(wsum), n_plane, n_plane, sm), "plane blend")
+        L.check(lib.bp_plane_finish(L.ptr(acc), L.ptr(wsum), F * n_plane * n_plane, L.ptr(result), sm), "plane finish")
         if out is not None:
             return out
         return result.cpu().numpy()

@@ -412,6 +412,21 @@ int bp_paint_load_scales2_mode(int32_t mode, const float* raw_nchw, const double
                                const bp_view* out2, void* stream);
 int bp_paint_store_scales_mode(int32_t mode, const bp_view* src, const bp_pointwise* pw, int32_t softplus,
                                int32_t include_original, const double* records, float* dst_nchw, void* stream);
+/* The store of a head that paints several label fields at once (painter.CVAEPainter with len(label_fields) > 1): field
+ * f owns channels [f * levels, (f + 1) * levels) of `src` (src->c == fields * levels) and plane f of dst
+ * (n, fields, H, W).  Per field the arithmetic is bp_paint_store_mode's for levels == 1 and
+ * bp_paint_store_scales_mode's for levels > 1 -- activation and softplus per channel, channel 0 (include_original) or
+ * the float32 sum ((c0 + c1) + c2) ..., then the inverse of mode modes[f] with the field's record -- and the bits are
+ * those of these entry points on the field's channel-slice view (pw, where given, holds fields * levels channels).
+ *   modes   : HOST array of `fields` int32 (BP_RC_*), held as a constant of the launch
+ *   records : device, (n, fields, 4) float64: DeviceRangeCompress.records of each field
+ * include_original has no effect at levels == 1.  One launch; a head value is read by one thread.  Before anything is
+ * written: BP_EINVAL for a null pointer or a malformed view, fields < 1, levels < 1, src->c != fields * levels or a mode
+ * outside 0 ... 5; then BP_EUNSUPPORTED for a bf16 view, more than 16 levels, more than 64 fields or
+ * n * H * W * src->c >= 2^31.  No atomics, no host synchronisation. */
+int bp_paint_store_fields(const int32_t* modes, int32_t fields, int32_t levels, int32_t include_original,
+                          const bp_view* src, const bp_pointwise* pw, int32_t softplus, const double* records,
+                          float* dst_nchw, void* stream);
 /* eps (L, n, per_tile) standard normal for the sampler of cvae.py:64-65 from Philox4x32-10 keyed on `seed`, counter
  * (element group, l, tile id): a tile's noise depends on (seed, its GLOBAL id) only, not on batch, stream or rank
  * (torch.randn on the device in the reference: same distribution, no reproducible stream to match). */
@@ -439,6 +454,13 @@ int bp_philox_normal_dev(const uint64_t* seed_dev, const int64_t* tile_ids, int3
  *                    regularise != 0: w = 0 where |p - mean| > std * regularise_std, with the tile's mean and
  *                    population std in float64 (fixed-order reduction into stats, 2n doubles).  No atomics: the same
  *                    tiles give the same bits as the host loop
+ *   bp_plane_blend_fields: bp_plane_blend for tiles (n, fields, tile, tile) of a painter with several label fields:
+ *                    field f's tiles tiles[t][f] are blended in tile order into plane f of acc / wsum
+ *                    (fields, rows, cols), with the field's own tile means and stds (stats: 2 * n * fields doubles, row
+ *                    t * fields + f) where regularise != 0.  One launch over (field, pixel of the bounding box); the
+ *                    bits of each plane are bp_plane_blend's on that field's tiles in a contiguous buffer.  BP_EINVAL
+ *                    as bp_plane_blend and for fields < 1; BP_EUNSUPPORTED for n * fields * tile^2 >= 2^31 or more
+ *                    than 65535 fields.  bp_plane_finish divides all planes at once (count = fields * rows * cols)
  *   bp_plane_finish: out = acc / wsum (IEEE: 0 / 0 = NaN where no tile reaches) */
 enum { BP_F64 = 2 }; /* bp_plane_cut's float64 planes (views are BP_F32 / BP_BF16 only) */
 size_t bp_plane_cut_workspace(int32_t n, int32_t cut, int32_t tile);
@@ -447,6 +469,10 @@ int bp_plane_cut(const void* plane, int32_t dtype, int32_t rows, int32_t cols, c
 int bp_plane_blend(const float* tiles, int32_t n, int32_t tile, const int32_t* dst, int32_t bx0, int32_t by0,
                    int32_t bx1, int32_t by1, const double* weight, int32_t regularise, double regularise_std,
                    double* stats, double* acc, double* wsum, int32_t rows, int32_t cols, void* stream);
+int bp_plane_blend_fields(const float* tiles, int32_t n, int32_t fields, int32_t tile, const int32_t* dst, int32_t bx0,
+                          int32_t by0, int32_t bx1, int32_t by1, const double* weight, int32_t regularise,
+                          double regularise_std, double* stats, double* acc, double* wsum, int32_t rows, int32_t cols,
+                          void* stream);
 int bp_plane_finish(const double* acc, const double* wsum, int64_t count, double* out, void* stream);
 
 /* ---- Compton-y map of a light cone (lightcone.project_planes(on_device=True), process_SLICS.py:55-64) -----------
