@@ -169,6 +169,7 @@ SIGNATURES = {
     "bp_loglik_forward": (C.c_int, [C.POINTER(Loglik), _P, _VP, _VP, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "bp_loglik_backward": (C.c_int, [C.POINTER(Loglik), _P, _VP, _VP, _P, _VP, _VP, _P]),
     "bp_unary_forward": (C.c_int, [_VP, _PWP, C.c_int32, _VP, _P]),
+    "bp_unary_backward": (C.c_int, [_VP, _VP, _VP, C.c_int32, _VP, _P]),
     "bp_bce_logits": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_float, _P, _P, C.c_size_t, _P]),
     "bp_bce_logits_grad": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_float, C.c_float, _VP, _P]),
     "bp_l1_sum": (C.c_int, [_VP, _P, _P, _P, C.c_size_t, _P]),

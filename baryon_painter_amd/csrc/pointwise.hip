@@ -780,6 +780,17 @@ __global__ __launch_bounds__(RB) void loglik_backward_kernel(LoglikBwdArgs a) {
 // ---------------------------------------------------------------- GAN heads (CGAN rows g1-g5 of SURVEY.md 8a)
 // out = tanh(act(in)) or sigmoid(act(in)), view -> view (e.g. the generator's Tanh output written
 // straight into the pressure channel of the discriminator's input concatenation).
+// The same functions are the CVAE's saturating layers (graph.UnaryUnit): kind 3 is torch's Softplus(beta=1,
+// threshold=20), and bp_unary_backward takes f' from the SAVED OUTPUT y = f(v):
+//   tanh 1 - y^2;  sigmoid y (1 - y);  softplus 1 - exp(-y) = sigmoid(v), as -expm1f(-y): above the threshold y = v
+//   and the expression rounds to 1 by itself, so nothing branches on the input, which the backward never reads.
+__device__ __forceinline__ float unary_f(int kind, float v) {
+  return kind == 1 ? tanhf(v) : (kind == 2 ? 1.f / (1.f + expf(-v)) : (kind == 3 ? softplus_f(v) : v));
+}
+__device__ __forceinline__ float unary_df(int kind, float y) {
+  return kind == 1 ? 1.f - y * y : (kind == 2 ? y * (1.f - y) : (kind == 3 ? -expm1f(-y) : 1.f));
+}
+
 __global__ __launch_bounds__(RB) void unary_forward_kernel(ViewD in, PW pw, int kind, ViewD out, int64_t total) {
   const int64_t i = (int64_t)blockIdx.x * RB + threadIdx.x;
   if (i >= total) return;
@@ -787,7 +798,77 @@ __global__ __launch_bounds__(RB) void unary_forward_kernel(ViewD in, PW pw, int 
   const int ch = i % c;
   const int64_t p = i / c;
   const float v = pw_apply(pw, ch, in.p[p * in.cs + in.co + ch]);
-  out.p[p * out.cs + out.co + ch] = kind == 1 ? tanhf(v) : (kind == 2 ? 1.f / (1.f + expf(-v)) : v);
+  out.p[p * out.cs + out.co + ch] = unary_f(kind, v);
+}
+
+__global__ __launch_bounds__(RB) void unary_backward_kernel(ViewD dout, ViewD dout2, ViewD y, int kind, ViewD din,
+                                                            int64_t total) {
+  const int64_t i = (int64_t)blockIdx.x * RB + threadIdx.x;
+  if (i >= total) return;
+  const int c = y.c;
+  const int ch = i % c;
+  const int64_t p = i / c;
+  float g = dout.p[p * dout.cs + dout.co + ch];
+  if (dout2.p) g += dout2.p[p * dout2.cs + dout2.co + ch];
+  din.p[p * din.cs + din.co + ch] = g * unary_df(kind, y.p[p * y.cs + y.co + ch]);
+}
+
+// Streaming forms: every lane moves 16 bytes.  A tensor is seen as `npix` rows of `cq` quads, quad g of row p at
+// ptr[p * cs + co + 4 * g]: the channel quads of a pixel (c, cstride, coff multiples of 4), or, for dense views of any
+// channel count, the flat array cut into rows of one quad (cs = 4, co = 0, cq = 1) with the last total % 4 elements
+// done one by one behind them.  One quad per thread: thread t has row t / cq, quad column t % cq, and loads the four
+// pointwise triples of its column (channels (4 g + j) % c) once.  Threads beyond the last row idle.
+struct QuadView {
+  float* p; int cs, co;
+};
+struct UnaryFast {
+  int c, cq, kind;
+  int64_t npix, tail0, total;      // elements [tail0, total): the flat form's scalar tail
+};
+// The grid is not capped (unlike the *_fast_kernel reductions above, these kernels keep nothing across rows): measured,
+// a capped grid that strides over the rows is slower than the scalar kernel on a strided channel slice.
+
+__global__ __launch_bounds__(RB) void unary_forward_fast_kernel(QuadView in, PW pw, QuadView out, UnaryFast a) {
+  const int64_t t = (int64_t)blockIdx.x * RB + threadIdx.x;
+  const int64_t p = t / a.cq;
+  const int g = (int)(t - p * a.cq);
+  if (p < a.npix) {
+    PW4 p4;
+    p4.on = pw.scale != nullptr;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int ch = (4 * g + j) % a.c;
+      p4.sc[j] = p4.on ? pw.scale[ch] : 1.f;
+      p4.sf[j] = p4.on ? pw.shift[ch] : 0.f;
+      p4.sl[j] = p4.on ? pw.slope[ch] : 1.f;
+    }
+    const float4 v = pw4_apply4(p4, *reinterpret_cast<const float4*>(in.p + p * in.cs + in.co + 4 * g));
+    *reinterpret_cast<float4*>(out.p + p * out.cs + out.co + 4 * g) =
+        make_float4(unary_f(a.kind, v.x), unary_f(a.kind, v.y), unary_f(a.kind, v.z), unary_f(a.kind, v.w));
+  }
+  const int64_t e = a.tail0 + t;
+  if (e < a.total) out.p[e] = unary_f(a.kind, pw_apply(pw, (int)(e % a.c), in.p[e]));
+}
+
+__global__ __launch_bounds__(RB) void unary_backward_fast_kernel(QuadView dout, QuadView dout2, QuadView y, QuadView din,
+                                                                 UnaryFast a) {
+  const int64_t t = (int64_t)blockIdx.x * RB + threadIdx.x;
+  const int64_t p = t / a.cq;
+  const int g = (int)(t - p * a.cq);
+  if (p < a.npix) {
+    float4 d = *reinterpret_cast<const float4*>(dout.p + p * dout.cs + dout.co + 4 * g);
+    if (dout2.p) d = add_t(d, *reinterpret_cast<const float4*>(dout2.p + p * dout2.cs + dout2.co + 4 * g));
+    const float4 v = *reinterpret_cast<const float4*>(y.p + p * y.cs + y.co + 4 * g);
+    *reinterpret_cast<float4*>(din.p + p * din.cs + din.co + 4 * g) =
+        make_float4(d.x * unary_df(a.kind, v.x), d.y * unary_df(a.kind, v.y), d.z * unary_df(a.kind, v.z),
+                    d.w * unary_df(a.kind, v.w));
+  }
+  const int64_t e = a.tail0 + t;
+  if (e < a.total) {
+    float d = dout.p[e];
+    if (dout2.p) d += dout2.p[e];
+    din.p[e] = d * unary_df(a.kind, y.p[e]);
+  }
 }
 
 // Binary cross entropy on logits: target 1 -> softplus(-x), target 0 -> softplus(x); partial sums.
@@ -1465,11 +1546,72 @@ int bp_loglik_backward(const bp_loglik* ll, const float* x_nchw, const bp_view* 
   return BP_OK;
 }
 
+// Which streaming form a set of views (all of one grid) allows: 1 = channel quads, 2 = flat (dense views; with a
+// pointwise only where a quad holds whole periods of the channels: c = 1 or 2), 0 = neither: the scalar kernel.
+static int unary_fast_form(const bp_view* const* vs, int nv, bool with_pw, UnaryFast* a, QuadView* q) {
+  const bp_view* v0 = vs[0];
+  const int64_t total = bp_view_pixels(v0) * v0->c;
+  bool quads = v0->c % 4 == 0 && v0->c / 4 <= RB, flat = !with_pw || v0->c <= 2;
+  for (int i = 0; i < nv; ++i) {
+    if (!vs[i]) continue;
+    quads = quads && bp_view_vec4(vs[i]);
+    flat = flat && vs[i]->cstride == vs[i]->c && reinterpret_cast<uintptr_t>(vs[i]->ptr) % 16 == 0;
+  }
+  if (!quads && !flat) return 0;
+  a->c = v0->c; a->total = total;
+  if (quads) { a->cq = v0->c / 4; a->npix = bp_view_pixels(v0); a->tail0 = total; }
+  else { a->cq = 1; a->npix = total / 4; a->tail0 = 4 * a->npix; }
+  for (int i = 0; i < nv; ++i) {
+    q[i] = QuadView{nullptr, 0, 0};
+    if (vs[i]) q[i] = quads ? QuadView{vs[i]->ptr, vs[i]->cstride, vs[i]->coff} : QuadView{vs[i]->ptr, 4, 0};
+  }
+  return quads ? 1 : 2;
+}
+static inline unsigned unary_fast_blocks(const UnaryFast& a) {
+  const int64_t nb = (a.npix * a.cq + RB - 1) / RB;      // (< 2^31: the callers refuse totals beyond that many blocks)
+  return (unsigned)(nb < 1 ? 1 : nb);
+}
+
 int bp_unary_forward(const bp_view* in, const bp_pointwise* pw, int32_t kind, const bp_view* out, void* stream) {
-  if (!bp_view_ok(in) || !bp_view_ok(out) || !same_grid(in, out) || kind < 0 || kind > 2) return BP_EINVAL;
+  if (!bp_view_ok_any(in) || !bp_view_ok_any(out) || !same_grid(in, out) || kind < 0 || kind > 3) return BP_EINVAL;
+  if (is_bf16(in) || is_bf16(out)) return BP_EUNSUPPORTED;
   const int64_t total = bp_view_pixels(in) * in->c;
+  if ((total + RB - 1) / RB >= (int64_t)1 << 31) return BP_EUNSUPPORTED;
+  const bp_view* vs[2] = {in, out};
+  UnaryFast a{}; QuadView q[2];
+  a.kind = kind;
+  if (unary_fast_form(vs, 2, bp_pw(pw).scale != nullptr, &a, q)) {
+    hipLaunchKernelGGL(unary_forward_fast_kernel, dim3(unary_fast_blocks(a)), dim3(RB), 0, bp_stream(stream), q[0],
+                       bp_pw(pw), q[1], a);
+    BP_CHECK_LAUNCH();
+    return BP_OK;
+  }
   hipLaunchKernelGGL(unary_forward_kernel, dim3(nblocks(total)), dim3(RB), 0, bp_stream(stream), vd(in), bp_pw(pw),
                      kind, vd(out), total);
+  BP_CHECK_LAUNCH();
+  return BP_OK;
+}
+
+int bp_unary_backward(const bp_view* dout, const bp_view* dout2, const bp_view* y, int32_t kind, const bp_view* d_in,
+                      void* stream) {
+  if (!bp_view_ok_any(dout) || !bp_view_ok_any(y) || !bp_view_ok_any(d_in) || !same_grid(dout, y) ||
+      !same_grid(d_in, y) || kind < 0 || kind > 3)
+    return BP_EINVAL;
+  if (dout2 && (!bp_view_ok_any(dout2) || !same_grid(dout2, y))) return BP_EINVAL;
+  if (is_bf16(dout) || is_bf16(dout2) || is_bf16(y) || is_bf16(d_in)) return BP_EUNSUPPORTED;
+  const int64_t total = bp_view_pixels(y) * y->c;
+  if ((total + RB - 1) / RB >= (int64_t)1 << 31) return BP_EUNSUPPORTED;
+  const bp_view* vs[4] = {y, dout, dout2, d_in};
+  UnaryFast a{}; QuadView q[4];
+  a.kind = kind;
+  if (unary_fast_form(vs, 4, false, &a, q)) {
+    hipLaunchKernelGGL(unary_backward_fast_kernel, dim3(unary_fast_blocks(a)), dim3(RB), 0, bp_stream(stream), q[1],
+                       q[2], q[0], q[3], a);
+    BP_CHECK_LAUNCH();
+    return BP_OK;
+  }
+  hipLaunchKernelGGL(unary_backward_kernel, dim3(nblocks(total)), dim3(RB), 0, bp_stream(stream), vd(dout), vd(dout2),
+                     vd(y), kind, vd(d_in), total);
   BP_CHECK_LAUNCH();
   return BP_OK;
 }

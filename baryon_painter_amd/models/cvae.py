@@ -20,7 +20,7 @@ import torch
 from .. import _lib as L
 from .arch import conv_block, conv_down, conv_up, res_block  # noqa: F401  (reference: ``from .utils import *``)
 from .graph import PW, ConvUnit, PackBatch, PlanBase, Slot, build_holders, compile_sequential, dense_blocks, \
-    latent_shape, probe_output, _stream
+    latent_shape, probe_output, unary_layers, _stream
 from . import paint_graph as PG
 
 pi = math.pi
@@ -70,14 +70,14 @@ class _Plan(PlanBase):
             sx0 = cat.sub(0, cqx, pw=cat.pw.slice(0, cqx))
             sy0 = cat.sub(cqx, cqx + cqy, pw=cat.pw.slice(cqx, cqx + cqy))
             ux, sx, tr = compile_sequential(self, "q_x_in.", a["q_x_in"], model.q_x_in, self.x_in,
-                                            out_slot=sx0, out_pw=sx0.pw, need_input_grad=False)
+                                            out_slot=sx0, out_pw=sx0.pw, need_input_grad=False, unary=True)
             self._no_trailing(tr, "q_x_in")
             uy, sy, tr = compile_sequential(self, "q_y_in.", a["q_y_in"], model.q_y_in, self.y2,
-                                            out_slot=sy0, out_pw=sy0.pw, need_input_grad=False)
+                                            out_slot=sy0, out_pw=sy0.pw, need_input_grad=False, unary=True)
             self._no_trailing(tr, "q_y_in")
             if sx is not sx0 or sy is not sy0:
                 raise NotImplementedError("q_x_in / q_y_in must end in a convolution")
-            uo, so, tr = compile_sequential(self, "q_out.", a["q_x_y_out"], model.q_out, cat, dense="tail")
+            uo, so, tr = compile_sequential(self, "q_out.", a["q_x_y_out"], model.q_out, cat, dense="tail", unary=True)
             self._latent_trailing(tr, "q_x_y_out")
             self.q_units = [ux, uy, uo]
             self.q_head = so
@@ -88,7 +88,7 @@ class _Plan(PlanBase):
         self.p_units, self.p_head = [], None
         if model.prior_network is not None:
             up, sp, tr = compile_sequential(self, "prior_network.", a["prior_z_y"], model.prior_network,
-                                            self.y2, need_input_grad=False, dense="tail")
+                                            self.y2, need_input_grad=False, dense="tail", unary=True)
             self._latent_trailing(tr, "prior_z_y")
             self.p_units, self.p_head = up, sp
             if sp.shape() != (n, zh, zw, 2 * zc):
@@ -130,7 +130,7 @@ class _Plan(PlanBase):
             self.hy_slot = self.p_in.sub(c_hz, ccat, pw=hy_pw)
             hy_out = self.hy_slot if Lr == 1 else Slot.new(n, H, W, c_hy, dev, pw=hy_pw)
             uy, sy, tr = compile_sequential(self, "p_y_in.", a["p_y_in"], model.p_y_in, self.y2,
-                                            out_slot=hy_out, out_pw=hy_pw, need_input_grad=False)
+                                            out_slot=hy_out, out_pw=hy_pw, need_input_grad=False, unary=True)
             self._no_trailing(tr, "p_y_in")
             if sy is not hy_out:
                 raise NotImplementedError("p_y_in must end in a convolution (+ batch-norm / activation)")
@@ -139,25 +139,27 @@ class _Plan(PlanBase):
         else:
             self.hy_slot = self.p_in.sub(c_hz, ccat)
         uz, sz, tr = compile_sequential(self, "p_z_in.", a["p_z_in"], model.p_z_in, self.z,
-                                        out_slot=hz_slot, out_pw=hz_slot.pw, dense="head")
+                                        out_slot=hz_slot, out_pw=hz_slot.pw, dense="head", unary=True)
         self._no_trailing(tr, "p_z_in")
         if sz is not hz_slot:
             raise NotImplementedError("p_z_in must end in a convolution (or be one dense block)")
-        ub, sb, tr = compile_sequential(self, "p_y_z_in.", a["p_y_z_in"], model.p_y_z_in, self.p_in)
+        ub, sb, tr = compile_sequential(self, "p_y_z_in.", a["p_y_z_in"], model.p_y_z_in, self.p_in, unary=True)
         self._no_trailing(tr, "p_y_z_in")
         if ub and isinstance(ub[0], ConvUnit) and not y_net:
             ub[0].restrict_dgrad(0, c_hz, target=hz_slot)   # y and the aux label are data: only h_z carries a gradient
+        else:
+            hz_slot.dense_grad = False      # (any other first consumer writes d/d p_in as a whole: h_z's is its slice)
         # (with a p_y_in network every channel of p_in carries one: the data gradient covers all c_hz + c_hy)
         self.g_units = [uz, ub]
         self.h = sb
-        um, sm, tr = compile_sequential(self, "p_mu_out.", a["p_y_z_out"][0], model.p_mu_out, sb)
+        um, sm, tr = compile_sequential(self, "p_mu_out.", a["p_y_z_out"][0], model.p_mu_out, sb, unary=True,
+                                        fused_tail=("softplus",))
         self.mu_softplus = self._head_trailing(tr, "p_y_z_out[0]")
         self.mu_units, self.mu_head = um, sm
         self.var_units, self.var_head = [], None
         if model.predict_var:
-            uv, sv, tr = compile_sequential(self, "p_var_out.", a["p_y_z_out"][1], model.p_var_out, sb)
-            if self._head_trailing(tr, "p_y_z_out[1]"):
-                raise NotImplementedError("softplus on the variance head")
+            uv, sv, tr = compile_sequential(self, "p_var_out.", a["p_y_z_out"][1], model.p_var_out, sb, unary=True)
+            self._no_trailing(tr, "p_y_z_out[1]")      # (tanh / sigmoid / softplus on this head are units: graph.UnaryUnit)
             self.var_units, self.var_head = uv, sv
         if sm.shape() != (nL, H, W, cx):
             raise ValueError(f"p_y_z_out produces {sm.shape()}, dim_x needs {(nL, H, W, cx)}")
@@ -265,7 +267,12 @@ class _Plan(PlanBase):
                               or (self._HEAD_TAIL and name in ("p_mu_out.2", "p_var_out.2")))
 
     def bf16_out(self, name):
-        return self.bf16 and (name.startswith("p_y_z_in.") or (self._HEAD_TAIL and name in ("p_mu_out.0", "p_var_out.0")))
+        return self.bf16 and self.bf16_out_of(name)
+
+    @classmethod
+    def bf16_out_of(cls, name):
+        """Whether the unit of that name writes a bf16 slot in a ``dtype="bf16"`` model."""
+        return name.startswith("p_y_z_in.") or (cls._HEAD_TAIL and name in ("p_mu_out.0", "p_var_out.0"))
 
     # ---- helpers
     side_branch = None
@@ -682,6 +689,55 @@ def check_dense_language(architecture, sync=None):
     probe_output(a["p_z_in"], zc, zh, zw)
 
 
+_UNARY = ("tanh", "sigmoid", "softplus")
+_NETS = {"q_x_in": ("q_x_in.", None), "q_y_in": ("q_y_in.", None), "q_x_y_out": ("q_out.", "tail"),
+         "p_y_in": ("p_y_in.", None), "p_z_in": ("p_z_in.", "head"), "p_y_z_in": ("p_y_z_in.", None),
+         "prior_z_y": ("prior_network.", "tail")}
+
+
+def check_unary_language(architecture, dtype="f32"):
+    """Where tanh / sigmoid / softplus layers (``graph.UnaryUnit``) may stand in a Type-1 architecture, checked on the
+    host before anything is allocated: anywhere among the convolutional layers of the eight nets, except inside a
+    residual block's branch, next to a dense block, and -- in a ``dtype="bf16"`` model -- where the unit would read or
+    write a bf16 slot (``_Plan.bf16_out_of`` of the convolution in front of it): anywhere in the generator trunk
+    p_y_z_in, and in a head first or behind its first convolution.  The heads' later convolutions write fp32: a bf16
+    model's heads may hold these layers behind them, and END in them.  NotImplementedError names the layer.
+    Architectures without such a layer pass unexamined."""
+    a = architecture
+    if a.get("type") != "Type-1":
+        return
+    lists = [(k, a.get(k)) + _NETS[k] + ((),) for k in _NETS]
+    lists += [(f"p_y_z_out[{i}]", seq, ("p_mu_out.", "p_var_out.")[i], None, (("softplus",), ())[i])
+              for i, seq in enumerate(a["p_y_z_out"][:2])]
+    for key, seq, prefix, where, fused in lists:
+        names = [layer[0].lower() for layer in seq or []]
+        for i, layer in enumerate(seq or []):
+            if names[i] == "residual block":
+                for j, inner in enumerate(layer[1][0]):
+                    if inner[0].lower() in _UNARY:
+                        raise NotImplementedError(f"{key}: {prefix}{i}.res_block.{j}: '{inner[0].lower()}' inside a "
+                                                  "residual block is not supported by the HIP path")
+        if not any(n in _UNARY for n in names):
+            continue
+        try:
+            idx = unary_layers(seq, prefix, dense_blocks(seq, prefix, where), fused)
+        except NotImplementedError as e:
+            raise NotImplementedError(f"{key}: {e}") from None
+        if dtype != "bf16" or not idx:
+            continue
+        if key != "p_y_z_in" and not key.startswith("p_y_z_out"):
+            continue                    # (the recognition / prior networks, p_y_in and p_z_in are fp32 in both modes)
+        convs = [i for i, n in enumerate(names) if n in ("conv", "transp conv", "residual block")]
+        for i in idx:
+            # a unit keeps the type of the slot it reads: its producer's, or, first in a head, the trunk's output
+            prod = [j for j in convs if j < i]
+            if key == "p_y_z_in" or not prod or names[prod[-1]] == "residual block" \
+                    or _Plan.bf16_out_of(f"{prefix}{prod[-1]}"):
+                raise NotImplementedError(f"{key}: {prefix}{i}: '{names[i]}' on a bf16 activation is not supported by the "
+                                          "HIP path (dtype='bf16' keeps the generator trunk and the slot behind a "
+                                          "head's first convolution in bf16; behind the later ones it is)")
+
+
 DEFER_MAX_BYTES = int(os.environ.get("BP_DEFER_MAX_MB", "1048576")) << 20
 
 
@@ -734,6 +790,7 @@ class CVAE(torch.nn.Module):
             raise RuntimeError("baryon_painter_amd.CVAE runs on an AMD GPU only (device='cuda:N'); "
                                "there is no CPU implementation of the hot path.")
         check_dense_language(architecture, sync)        # (host only: refusals come before any device allocation)
+        check_unary_language(architecture, dtype)
         self._lib = L.load()
         self.impl = {"auto": L.IMPL_AUTO, "direct": L.IMPL_DIRECT, "mfma": L.IMPL_MFMA}[impl]
         self.sync = sync

@@ -975,6 +975,90 @@ class LinearUnit:
             plan.prof_end(t0, self, "backward_data")
 
 
+UNARY_KINDS = {"tanh": 1, "sigmoid": 2, "softplus": 3}      # bp_unary_forward / bp_unary_backward
+
+
+class UnaryUnit:
+    """tanh | sigmoid | softplus as a layer of its own  (utils.py:68-73, 140-145).  A saturating function is no pending
+    (scale, shift, slope) record, so unlike a ReLU it materialises: the unit reads ``inp`` through ``inp.pw`` (a
+    conv + batch-norm [+ relu] in front of it stays pending, as for any consumer) and writes ``out`` -- a new slot or the
+    caller's concat slice -- with no pointwise pending.  The backward takes f' from that saved output alone
+    (bp_unary_backward) and hands d/d(activated inp) to the producer, which applies its own activation / batch-norm
+    backward.  No parameters, no statistics, nothing to pack; fp32 slots only."""
+
+    bf16 = False
+    _sub = None
+    ws_name = "ws"
+
+    def __init__(self, plan, name, kind, inp, out_slot=None, out_pw=None, need_dgrad=True):
+        self.plan, self.name, self.kind = plan, name, kind
+        self.code = UNARY_KINDS[kind]
+        self.inp, self.need_dgrad = inp, need_dgrad
+        if inp.dt != L.F32 or (out_slot is not None and out_slot.dt != L.F32):
+            raise NotImplementedError(f"{name}: '{kind}' on a bf16 activation is not supported by the HIP path")
+        if out_pw is not None:               # (the slice of a concatenation's record: nothing is pending on these channels)
+            out_pw.scale.fill_(1.0)
+            out_pw.shift.fill_(0.0)
+            out_pw.slope.fill_(1.0)
+        if out_slot is None:
+            self.out = Slot.new(inp.n, inp.h, inp.w, inp.c, plan.device, pw=None)
+        else:
+            if out_slot.shape() != inp.shape():
+                raise ValueError(f"{name}: concat slot shape {out_slot.shape()} != {inp.shape()}")
+            self.out = out_slot
+            self.out.pw = None
+        self.out.producer = self
+        self.dx = None
+
+    def macs(self, kind="forward"):
+        return 0
+
+    def algorithmic_bytes(self, kind, nstreams=1):
+        """Forward: one read, one write; backward: d/d out (once per contribution), the saved output, d/d in."""
+        one = self.out.n * self.out.h * self.out.w * self.out.c * 4
+        return 2 * one if kind == "forward" else (3 + (self.out.grad2 is not None)) * one
+
+    def maybe_pack(self):
+        pass
+
+    def maybe_bn_eval(self):
+        pass
+
+    def forward(self, training):
+        plan = self.plan
+        t0 = plan.prof_begin()
+        L.check(plan.lib.bp_unary_forward(C.byref(self.inp.view), self.inp.pw_struct(), self.code,
+                                          C.byref(self.out.view), _stream()), f"{self.name} {self.kind}")
+        plan.prof_end(t0, self, "forward")
+
+    def forward_steps(self, training):
+        self.forward(training)
+        return
+        yield                        # (a generator that never asks for a collective)
+
+    def prepare_backward(self):
+        if not self.need_dgrad:          # (a unit on data: the layer behind it computes no data gradient either)
+            self.dx = None
+            return
+        self.out.ensure_grad()
+        self.dx = self.inp.claim_grad()
+
+    def backward(self, grads):
+        if self.dx is None:
+            return
+        plan, out = self.plan, self.out
+        t0 = plan.prof_begin()
+        L.check(plan.lib.bp_unary_backward(C.byref(out.grad), None if out.grad2 is None else C.byref(out.grad2),
+                                           C.byref(out.view), self.code, C.byref(self.dx), _stream()),
+                f"{self.name} {self.kind} backward")
+        plan.prof_end(t0, self, "unary_backward", 3 + (out.grad2 is not None))
+
+    def backward_steps(self, grads):
+        self.backward(grads)
+        return
+        yield
+
+
 class PackBatch:
     """All weight re-layouts of a plan in one launch (``bp_conv_pack_jobs``) instead of two per layer.
 
@@ -1184,22 +1268,45 @@ def dense_blocks(architecture, prefix, where):
 
 
 # ------------------------------------------------------------------ sequential compiler
+def unary_layers(architecture, prefix, dense_blocks_of, fused_tail=()):
+    """Indices of the tanh / sigmoid / softplus layers of a list that compile to a ``UnaryUnit`` (``compile_sequential``
+    with ``unary=True``): all of them, except a last layer named in ``fused_tail`` (the mean head's trailing softplus
+    stays a flag of the loss and store kernels).  Needs no device.  Next to a dense block they stay refused, as
+    NotImplementedError naming the layer."""
+    layers = _layer_list(architecture)
+    idx = [i for i, (n, _) in enumerate(layers) if n in UNARY_KINDS]
+    if idx and idx[-1] == len(layers) - 1 and layers[-1][0] in fused_tail:
+        idx = idx[:-1]
+    for start, b in dense_blocks_of.items():
+        for i in idx:
+            if i == start - 1 or i == b["end"]:
+                raise NotImplementedError(f"{prefix}{i}: '{layers[i][0]}' next to the dense block {prefix}"
+                                          f"{b['linears'][0][0]} is not supported by the HIP path")
+    return idx
+
+
 def compile_sequential(plan, prefix, architecture, holders, inp, out_slot=None, out_pw=None,
-                       need_input_grad=True, dense=None):
+                       need_input_grad=True, dense=None, unary=False, fused_tail=()):
     """Group the layer list into units.  Returns (units, output slot, trailing) where
     ``trailing`` lists parameter-free layers after the last convolution that are not
     expressible as a pending pointwise (softplus / tanh / sigmoid / unflatten / flatten).
-    ``dense``: where a dense block may stand in this net ("tail" / "head" / None, see ``dense_blocks``)."""
+    ``dense``: where a dense block may stand in this net ("tail" / "head" / None, see ``dense_blocks``).
+    ``unary``: tanh / sigmoid / softplus become ``UnaryUnit`` s wherever they stand among the convolutional layers
+    (first, between, behind a residual block, last, several in a row) instead of being refused or handed back in
+    ``trailing``; the last of them, if it is the net's last producer, writes ``out_slot``.  ``fused_tail``: names that
+    still go to ``trailing`` when they are the very last layer.  Off by default: the CGAN plans read their tanh /
+    sigmoid from ``trailing``."""
     units, trailing = [], []
     if architecture is None:
         return units, inp, trailing
     layers = _layer_list(architecture)
     blocks = dense_blocks(architecture, prefix, dense)
+    unary_at = unary_layers(architecture, prefix, blocks, fused_tail) if unary else []
     # index of the last conv-like layer, and of the last layer that produces a tensor -- that one or a linear layer
     # behind it: its output may go to a concat slot
     conv_like = [i for i, (n, _) in enumerate(layers) if n in _CONV_LIKE]
     last_conv = conv_like[-1] if conv_like else -1
-    last_producer = max([last_conv] + [b["linears"][-1][0] for b in blocks.values()])
+    last_producer = max([last_conv] + [b["linears"][-1][0] for b in blocks.values()] + unary_at)
     cur = inp
     i = 0
     first = True
@@ -1260,6 +1367,15 @@ def compile_sequential(plan, prefix, architecture, holders, inp, out_slot=None, 
             units.append(u)
             cur = u.out
             i += 1
+        elif i in unary_at:
+            is_last = (i == last_producer)
+            u = UnaryUnit(plan, f"{prefix}{i}", name, cur, out_slot=out_slot if is_last else None,
+                          out_pw=out_pw if is_last else None, need_dgrad=(need_input_grad or not first))
+            units.append(u)
+            cur = u.out
+            i += 1
+            if not u.need_dgrad:
+                continue                 # (a function of the data alone: the next layer is still the first with a gradient)
         elif name in ("softplus", "tanh", "sigmoid", "unflatten", "flatten"):
             if i < last_conv:
                 raise NotImplementedError(f"{prefix}{i}: '{name}' between convolutions is not supported "

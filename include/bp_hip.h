@@ -590,9 +590,22 @@ int bp_loglik_backward(const bp_loglik* ll, const float* x_nchw, const bp_view* 
                        const bp_view* d_var_raw, void* stream);
 
 /* ---- GAN heads (the CGAN of trained_models/README.md:95-144; no code in the reference) ------ */
-/* out = f(act(in)), kind 0 identity, 1 tanh (generator output, README.md:128), 2 sigmoid. */
+/* out = f(act(in)), kind 0 identity, 1 tanh (generator output, README.md:128), 2 sigmoid, 3 softplus.  Also the
+ * saturating layers of the CVAE's layer language (models/utils.py:68-73, 140-145; graph.UnaryUnit).  With
+ * v = act(in) = the pointwise of `pw` (NULL: v = in), all in float32:
+ *   kind 1: tanhf(v)    kind 2: 1 / (1 + expf(-v))    kind 3: v > 20 ? v : log1pf(expf(v))  (torch.nn.Softplus(1, 20))
+ * bp_unary_backward: d_in = (dout + dout2) * f'(y) from the SAVED OUTPUT y = f(v) alone (dout2 may be NULL):
+ *   kind 0: 1    kind 1: 1 - y*y    kind 2: y * (1 - y)    kind 3: -expm1f(-y)  (= sigmoid(v); 1 above the threshold)
+ * d_in is d(loss)/d(act(in)): the producer of `in` applies its own activation derivative.  d_in may be dout.
+ * Views of one grid (n, h, w, c), channel slices of wider buffers included; nothing outside [coff, coff + c) is
+ * written.  Each lane moves 16 bytes where every view allows it (c, cstride, coff multiples of 4, or all views dense,
+ * and 16-byte aligned bases); any other view runs one element per thread with the same arithmetic per element.  No
+ * atomics, no workspace, no host synchronisation.  fp32 views only: BP_EUNSUPPORTED (nothing written) for a bf16 view;
+ * BP_EINVAL for views that are not one grid or a kind outside 0..3. */
 int bp_unary_forward(const bp_view* in, const bp_pointwise* pw, int32_t kind, const bp_view* out,
                      void* stream);
+int bp_unary_backward(const bp_view* dout, const bp_view* dout2, const bp_view* y, int32_t kind,
+                      const bp_view* d_in, void* stream);
 /* sum over samples [n0,n1) of BCE(sigmoid(raw), target) evaluated on the logits; and its gradient
  * d_raw = scale * (sigmoid(raw) - target) for those samples. */
 int bp_bce_logits(const bp_view* raw, int32_t n0, int32_t n1, float target, double* sum,
