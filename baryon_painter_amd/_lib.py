@@ -145,6 +145,7 @@ SIGNATURES = {
     "bp_paint_store_fields": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _VP, _PWP, C.c_int32, _P, _P, _P]),
     "bp_philox_normal": (C.c_int, [C.c_uint64, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "bp_philox_normal_dev": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "bp_likelihood_draw": (C.c_int, [_VP, C.c_int32, _VP, _P, _P, _P, _VP, _P]),
     "bp_plane_cut_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "bp_plane_cut": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P,
                                C.c_size_t, _P, _P]),

@@ -16,6 +16,9 @@
 //                     head followed by the inverse, both evaluated in double as the host's NumPy expressions are
 //   bp_philox_normal  the prior noise of cvae.py:64-65 from a counter-based generator keyed on (seed, GLOBAL tile id):
 //                     a tile's sample does not depend on which batch, stream or rank paints it
+//   bp_likelihood_draw  a draw x_mu + sqrt(x_var) e from the likelihood of a two-head CVAE, e from the same generator on
+//                     a noise lattice keyed on (seed, noise id, lattice pixel, channel): what the store kernels read
+//                     in place of the mean head when a painter paints with pixel noise
 // Float semantics are those of the host path (the reference's NumPy expressions on float32 tiles, evaluated in
 // double where NumPy promotes to double), so device and host transforms agree to the last float32 bit except for
 // libm differences of exp (<= 1 ulp of the exponential).
@@ -205,6 +208,64 @@ __global__ __launch_bounds__(RB) void philox_normal_kernel(unsigned long long se
     if (4 * g + r < per_tile) o[r] = (float)z[r];
 }
 
+// A draw from the likelihood, out = t + sqrt(var) e: t the mean head (softplus as in paint_store_kernel), var the
+// exponential of the variance head, e a pixel of a NOISE LATTICE -- the r-th normal (philox_normal_kernel's Box-Muller,
+// in double) of the Philox block with the counter (X + ((ch / 4) << 24), 2^31 | Y, id), r = ch % 4, (Y, X) = the
+// sample's origin + (y, x).  Bit 31 of word 1 keeps these blocks apart from the latent draws (l < 2^31) under one key.
+// One thread per Philox block = one pixel and one group of four channels, in pixel order: the lanes of a wave read and
+// write the (up to four) consecutive channels of consecutive pixels.  Only the half-blocks whose normals the group
+// uses go through the double-precision logarithm and sine / cosine (one channel: one logarithm and one cosine).
+// Contraction is off: the product and the sum each round once, as the host's float32 restatement does.  A zero product
+// (var = 0) leaves t as it is, the sign of a zero and a NaN's payload included.
+__global__ __launch_bounds__(RB) void likelihood_draw_kernel(const float* mu, int mu_cs, int mu_co, int softplus,
+                                                             const float* lv, int lv_cs, int lv_co,
+                                                             const unsigned long long* seed_dev, const long long* ids,
+                                                             const int* origins, float* out, int out_cs, int out_co,
+                                                             int c, unsigned groups, unsigned w, unsigned hw,
+                                                             unsigned total) {
+#pragma clang fp contract(off)
+  const unsigned i = blockIdx.x * RB + threadIdx.x;             // pixel * groups + g
+  if (i >= total) return;
+  const unsigned p = groups == 1u ? i : i / groups;             // pixel n * hw + yx
+  const unsigned g = i - p * groups;
+  const unsigned nu = (hw & (hw - 1u)) == 0u ? p >> (__ffs((int)hw) - 1) : p / hw;              // (see paint_load_kernel)
+  const unsigned yx = p - nu * hw;
+  const unsigned y = yx / w, x = yx - y * w;
+  const unsigned oy = origins ? (unsigned)origins[2 * nu] : 0u, ox = origins ? (unsigned)origins[2 * nu + 1] : 0u;
+  const unsigned long long seed = *seed_dev, id = (unsigned long long)ids[nu];
+  unsigned ctr[4] = {(ox + x) + (g << 24), 0x80000000u | (oy + y), (unsigned)id, (unsigned)(id >> 32)};
+  unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    philox_round(ctr, k0, k1);
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  const int cnt = min(4, c - 4 * (int)g);                       // channels of this group: uniform over the wave if c <= 4
+  const double two32 = 4294967296.0, twopi = 6.283185307179586476925286766559;
+  double z[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    if (2 * h < cnt) {
+      const double u1 = ((double)ctr[2 * h] + 1.0) / two32, u2 = (double)ctr[2 * h + 1] / two32;
+      const double rad = sqrt(-2.0 * log(u1));
+      z[2 * h] = rad * cos(twopi * u2);
+      if (2 * h + 1 < cnt) z[2 * h + 1] = rad * sin(twopi * u2);
+    }
+  }
+  const float* m = mu + (int64_t)p * mu_cs + mu_co + 4 * g;
+  const float* v = lv + (int64_t)p * lv_cs + lv_co + 4 * g;
+  float* o = out + (int64_t)p * out_cs + out_co + 4 * g;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    if (r < cnt) {
+      float t = m[r];
+      if (softplus) t = softplus_f(t);
+      const float s = expf(0.5f * v[r]) * (float)z[r];
+      o[r] = s == 0.f ? t : t + s;
+    }
+  }
+}
+
 static inline unsigned nblocks(int64_t total) { return (unsigned)((total + RB - 1) / RB); }
 
 }  // namespace
@@ -345,6 +406,25 @@ int bp_philox_normal_dev(const uint64_t* seed_dev, const int64_t* tile_ids, int3
   hipLaunchKernelGGL(philox_normal_kernel, dim3(nblocks(total)), dim3(RB), 0, bp_stream(stream), 0ull,
                      reinterpret_cast<const unsigned long long*>(seed_dev),
                      reinterpret_cast<const long long*>(tile_ids), n, L, per_tile, eps);
+  BP_CHECK_LAUNCH();
+  return BP_OK;
+}
+
+int bp_likelihood_draw(const bp_view* mu, int32_t softplus, const bp_view* log_var, const uint64_t* seed_dev,
+                       const int64_t* noise_ids, const int32_t* origins, const bp_view* out, void* stream) {
+  if (!bp_view_ok_any(mu) || !bp_view_ok_any(log_var) || !bp_view_ok_any(out) || !seed_dev || !noise_ids)
+    return BP_EINVAL;
+  for (const bp_view* v : {log_var, out})
+    if (v->n != mu->n || v->h != mu->h || v->w != mu->w || v->c != mu->c) return BP_EINVAL;
+  if (mu->dtype != BP_F32 || log_var->dtype != BP_F32 || out->dtype != BP_F32) return BP_EUNSUPPORTED;
+  const int64_t hw = (int64_t)mu->h * mu->w, pixels = (int64_t)mu->n * hw;
+  if (pixels * mu->c >= (int64_t)1 << 31) return BP_EUNSUPPORTED;
+  const int64_t groups = (mu->c + 3) / 4, total = pixels * groups;      // <= pixels * c < 2^31
+  hipLaunchKernelGGL(likelihood_draw_kernel, dim3(nblocks(total)), dim3(RB), 0, bp_stream(stream), mu->ptr, mu->cstride,
+                     mu->coff, softplus ? 1 : 0, log_var->ptr, log_var->cstride, log_var->coff,
+                     reinterpret_cast<const unsigned long long*>(seed_dev), reinterpret_cast<const long long*>(noise_ids),
+                     origins, out->ptr, out->cstride, out->coff, (int)mu->c, (unsigned)groups, (unsigned)mu->w,
+                     (unsigned)hw, (unsigned)total);
   BP_CHECK_LAUNCH();
   return BP_OK;
 }

@@ -66,8 +66,17 @@ def plane_geometry(n_delta, tile_relative_size, n_pixel_tile, min_tile_overlap=0
             "dst": np.asarray(dst, np.int32).reshape(-1, 2)}
 
 
+def _need_pixel_noise(painter):
+    """ValueError unless ``painter`` can paint draws from its likelihood (``Painter._need_pixel_noise``).  Draws no
+    random number, captures nothing."""
+    if not hasattr(painter, "_need_pixel_noise"):
+        raise ValueError(f"pixel_noise=True: {type(painter).__name__} cannot draw from a likelihood")
+    painter._need_pixel_noise()
+
+
 def paint_plane(painter, delta, tile_relative_size, n_pixel_tile, z, min_tile_overlap=0.5, falloff=0.05,
-                sigma=0.5, regularise_std=None, batch_size=64, seed=None, first_tile_id=0, on_device=False, out=None):
+                sigma=0.5, regularise_std=None, batch_size=64, seed=None, first_tile_id=0, on_device=False, out=None,
+                pixel_noise=False):
     """Paint a periodic mass plane tile by tile and blend (the inner loop of ``process_SLICS``,
     process_SLICS.py:198-220): tiles are cut with wrap-around, resampled to the network's tile size
     if necessary, painted in batches, weighted by ``make_weight_map`` and accumulated.
@@ -92,10 +101,22 @@ def paint_plane(painter, delta, tile_relative_size, n_pixel_tile, z, min_tile_ov
     (n_plane, n_plane) tensor that receives the plane instead (nothing is downloaded; ``out`` is returned).  The cut
     without resampling and the blend give the host path's bits; the resampling is within 1 ulp (float32) of SciPy's;
     with ``regularise_std`` the tile statistics are float64 sums where NumPy sums float32, so a pixel within about 1e-6
-    of the threshold may be kept by one path and dropped by the other."""
+    of the threshold may be kept by one path and dropped by the other.
+
+    ``pixel_noise=True`` (a CVAEPainter whose model has a variance head; ValueError otherwise, before any random number
+    is drawn or any graph is captured), on either path: every tile is a draw from the likelihood, x_mu + sqrt(x_var) e
+    in network units, instead of its mean.  The plane has ONE noise lattice, ``first_tile_id`` under the key ``seed``,
+    and every tile reads its window of it at its destination origin in the painted plane (``plane_geometry``'s ``dst``),
+    so that overlapping tiles carry the same e at the same plane pixel: independent draws would be averaged by the
+    feathered blend, which would lower the scatter wherever tiles overlap (about half the plane at
+    ``min_tile_overlap=0.5``).  The blend runs in physical units, behind the non-linear inverse transform: a blended
+    pixel is a weighted mean of two monotone functions of one normal (each tile's own mean and variance at that
+    pixel), not exactly one draw."""
+    if pixel_noise:
+        _need_pixel_noise(painter)
     if on_device:
         return _paint_plane_device(painter, delta, tile_relative_size, n_pixel_tile, z, min_tile_overlap, falloff,
-                                   sigma, regularise_std, batch_size, seed, first_tile_id, out)
+                                   sigma, regularise_std, batch_size, seed, first_tile_id, out, pixel_noise)
     if out is not None:
         raise ValueError("out= needs on_device=True")
     n_plane = int(n_pixel_tile / tile_relative_size)
@@ -109,6 +130,10 @@ def paint_plane(painter, delta, tile_relative_size, n_pixel_tile, z, min_tile_ov
                 t = scipy.ndimage.zoom(t, zoom=n_pixel_tile / t.shape[0], mode="reflect")
             tiles.append(np.asarray(t, dtype=np.float32))
     painted = None
+    noise = {}
+    if pixel_noise:                              # one lattice, every tile's window at its place in the painted plane
+        noise = dict(pixel_noise=True, noise_ids=np.full(len(tiles), first_tile_id, dtype=np.int64),
+                     noise_origins=np.asarray([(s[0].start, s[1].start) for row in slices for s in row], dtype=np.int32))
     # eligibility is decided UP FRONT (no capture attempted, no random number consumed): an error raised later, deep
     # inside the device pipeline, then propagates instead of silently selecting the slow host path
     if hasattr(painter, "paint_stream") and getattr(painter, "can_paint_stream", lambda z=0.0: True)(z):
@@ -117,9 +142,11 @@ def paint_plane(painter, delta, tile_relative_size, n_pixel_tile, z, min_tile_ov
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         ids = first_tile_id + np.arange(len(tiles), dtype=np.int64)
         painted = painter.paint_stream(np.stack(tiles), z, batch_size=min(batch_size, len(tiles)), tile_ids=ids,
-                                       seed=seed)
+                                       seed=seed, **noise)
     if painted is None:
-        painted = painter.paint_batch(np.stack(tiles), z, batch_size=batch_size)
+        if pixel_noise:
+            noise["seed"] = seed                 # (None: paint_batch draws a fresh key)
+        painted = painter.paint_batch(np.stack(tiles), z, batch_size=batch_size, **noise)
     if np.ndim(painted) == 4:                    # (N, F, H, W): one plane per label field, each with its own mask
         return np.stack([_blend_host(painted[:, f], slices, n_plane, falloff, sigma, regularise_std)
                          for f in range(painted.shape[1])])
@@ -145,7 +172,7 @@ def _blend_host(painted, slices, n_plane, falloff, sigma, regularise_std):
 
 
 def _paint_plane_device(painter, delta, tile_relative_size, n_pixel_tile, z, min_tile_overlap, falloff, sigma,
-                        regularise_std, batch_size, seed, first_tile_id, out):
+                        regularise_std, batch_size, seed, first_tile_id, out, pixel_noise=False):
     if not (hasattr(painter, "_paint_plane_device") and painter.can_paint_stream(z)):
         raise NotImplementedError("paint_plane(on_device=True) needs a painter with a device paint pipeline "
                                   "(CVAEPainter / CGANPainter .can_paint_stream)")
@@ -161,8 +188,9 @@ def _paint_plane_device(painter, delta, tile_relative_size, n_pixel_tile, z, min
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())
     ids = first_tile_id + np.arange(n_tiles, dtype=np.int64)
     w = make_weight_map((n_pixel_tile, n_pixel_tile), falloff=falloff, sigma=sigma)
+    kw = {"pixel_noise": True} if pixel_noise else {}
     return painter._paint_plane_device(delta, geo, z, w, batch_size=min(batch_size, n_tiles), tile_ids=ids, seed=seed,
-                                       regularise_std=regularise_std, out=out)
+                                       regularise_std=regularise_std, out=out, **kw)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -346,7 +374,7 @@ def _field_index(painter, field):
 
 
 def paint_small_plane(painter, massplane, shift, delta_size, tile_size, mass_size, n_pixel_tile, z, seed=None,
-                      tile_id=0, subtract_minimum=False, field=None):
+                      tile_id=0, subtract_minimum=False, field=None, pixel_noise=False):
     """Paint a plane whose footprint ``delta_size`` is smaller than the network's tile ``tile_size`` (the low-redshift
     branch of ``process_SLICS``, process_SLICS.py:149-176): ONE tile, expanded to the network's size around the
     footprint, is cut with wrap-around at ``shift`` from the periodic mass plane of ``mass_size`` (all three sizes in
@@ -358,9 +386,14 @@ def paint_small_plane(painter, massplane, shift, delta_size, tile_size, mass_siz
     (``can_paint_stream``) paints through ``paint_stream`` with the Philox key (``seed``, ``tile_id``); ``seed=None``
     draws a fresh key from torch's global generator.  Any other painter goes through ``paint``.  The plane is returned
     as float64, like ``paint_plane``'s.  ``field``: the label field to return, needed for a painter with several
-    (ValueError without it, before any random number is drawn)."""
+    (ValueError without it, before any random number is drawn).  ``pixel_noise``: the tile is a draw from the likelihood
+    (``paint_plane``) on the lattice ``tile_id`` at origin (0, 0), on either path (``paint`` under the same ``seed``)."""
     import scipy.ndimage
     j = _field_index(painter, field)
+    noise = {}
+    if pixel_noise:
+        _need_pixel_noise(painter)
+        noise = {"pixel_noise": True}
     tile = get_tile(massplane, shift, tile_relative_size=delta_size / mass_size,
                     expansion_factor=tile_size / delta_size)
     if subtract_minimum:
@@ -373,9 +406,11 @@ def paint_small_plane(painter, massplane, shift, delta_size, tile_size, mass_siz
             import torch
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         painted = painter.paint_stream(np.asarray(tile, dtype=np.float32)[None], z, batch_size=1,
-                                       tile_ids=np.array([tile_id], dtype=np.int64), seed=seed)[0]
+                                       tile_ids=np.array([tile_id], dtype=np.int64), seed=seed, **noise)[0]
     else:
-        painted = painter.paint(input=tile, z=z, transform=True, inverse_transform=True)
+        if pixel_noise:
+            noise.update(seed=seed, noise_id=tile_id)
+        painted = painter.paint(input=tile, z=z, transform=True, inverse_transform=True, **noise)
     if j is not None:
         painted = painted[j]
     centre = (1 - delta_size / tile_size) / 2
@@ -386,7 +421,7 @@ def paint_small_plane(painter, massplane, shift, delta_size, tile_size, mass_siz
 
 def paint_light_cone(painter, planes, z, delta_size, tile_size, n_pixel_tile, resolution, scales, min_tile_overlap=0.5,
                      falloff=0.05, sigma=0.5, regularise_std=None, batch_size=64, order=3, subtract_minimum=False,
-                     on_device=False, seed=None, out=None, return_planes=False, field=None):
+                     on_device=False, seed=None, out=None, return_planes=False, field=None, pixel_noise=False):
     """Mass planes in, one y map out (``process_SLICS`` followed by ``create_y_map``'s loop, process_SLICS.py:147-220 and
     55-64): plane i of the light cone is painted at redshift ``z[i]`` and projected into the (resolution, resolution)
     map with the factor ``scales[i]`` (``y_map_scales``) at once; no list of painted planes is kept.
@@ -414,11 +449,18 @@ def paint_light_cone(painter, planes, z, delta_size, tile_size, n_pixel_tile, re
     drawn).  That field's plane is the one projected and, with ``return_planes``, kept; on the device it is a slice of
     the (F, n_plane, n_plane) buffer ``paint_plane`` blends into.  A painter with one label field needs no ``field``.
 
+    ``pixel_noise=True`` is passed to every plane (``paint_plane`` / ``paint_small_plane``: ValueError for a painter
+    without a variance head, before any random number is drawn): a tiled plane's noise lattice is its first tile id.
+
     Returns the map, or (map, painted planes as host arrays) with ``return_planes=True``."""
     z, delta_size = list(z), list(delta_size)
     if not len(z) == len(delta_size) == len(scales):
         raise ValueError("z, delta_size and scales need one entry per plane")
     j = _field_index(painter, field)
+    noise = {}
+    if pixel_noise:
+        _need_pixel_noise(painter)
+        noise = {"pixel_noise": True}
     n_f = len(painter.label_fields) if j is not None else 1
     if out is not None and not on_device:
         raise ValueError("out= needs on_device=True")
@@ -452,7 +494,7 @@ def paint_light_cone(painter, planes, z, delta_size, tile_size, n_pixel_tile, re
             rel = tile_size / delta_size[i]
             geo = plane_geometry(entry.shape[0], rel, n_pixel_tile, min_tile_overlap)
             kw = dict(min_tile_overlap=min_tile_overlap, falloff=falloff, sigma=sigma, regularise_std=regularise_std,
-                      batch_size=batch_size, seed=seed, first_tile_id=tile_id)
+                      batch_size=batch_size, seed=seed, first_tile_id=tile_id, **noise)
             tile_id += geo["n_side"] ** 2
             if on_device:
                 n_plane = geo["n_plane"]
@@ -471,7 +513,8 @@ def paint_light_cone(painter, planes, z, delta_size, tile_size, n_pixel_tile, re
             if on_device:                                        # paint_stream copies on streams of its own
                 torch.cuda.current_stream(dev).synchronize()
             plane = paint_small_plane(painter, massplane, shift, delta_size[i], tile_size, mass_size, n_pixel_tile,
-                                      z[i], seed=seed, tile_id=tile_id, subtract_minimum=subtract_minimum, field=field)
+                                      z[i], seed=seed, tile_id=tile_id, subtract_minimum=subtract_minimum, field=field,
+                                      **noise)
             tile_id += 1
             if on_device:
                 host = plane

@@ -466,6 +466,25 @@ class _Plan(PlanBase):
         for u in self.var_units:
             u.forward(training)
 
+    draw = None                              # the slot of run_draw, once it has been asked for
+
+    def draw_slot(self):
+        if self.var_head is None:
+            raise ValueError("a draw from the likelihood needs a variance head")
+        if self.draw is None:
+            self.draw = Slot.new(self.mu_head.n, self.mu_head.h, self.mu_head.w, self.mu_head.c, self.device)
+        return self.draw
+
+    def run_draw(self, seed, ids, origins):
+        """A draw from the likelihood, x_mu + sqrt(x_var) e, into the plan's ``draw`` slot (fp32 whatever the model's
+        dtype, allocated on first use) behind ``run_generator``: ``bp_likelihood_draw`` with the device tensors ``seed``
+        (1,) int64, ``ids`` (n,) int64 and ``origins`` (n, 2) int32 or None.  The slot then stands in for the mean head
+        with ``softplus = 0``."""
+        self.draw_slot()
+        L.check(self.lib.bp_likelihood_draw(C.byref(self.mu_head.view), 1 if self.mu_softplus else 0,
+                                            C.byref(self.var_head.view), L.ptr(seed), L.ptr(ids), L.ptr(origins),
+                                            C.byref(self.draw.view), _stream()), "likelihood draw")
+
     def mark(self, name):
         """Phase mark on the main stream (BP_PHASE_EVENTS=1; tools/phase_times.py): a timed event in ``self.marks``."""
         if self.marks is not None:
@@ -978,12 +997,29 @@ class CVAE(torch.nn.Module):
         self.z_log_var = plan.stats4[1]
         return elbo
 
-    def sample_P(self, y, return_var=False, aux_label=None, z=None):
-        """cvae.py:149-162 (always under no_grad)."""
+    def _need_var_head(self, what):
+        if not self.predict_var:
+            raise ValueError(f"{what}: this model has no variance head (p_y_z_out has one entry): its likelihood has "
+                             "unit variance in network units, which is never the scatter that is wanted")
+
+    def sample_P(self, y, return_var=False, aux_label=None, z=None, pixel_noise=None):
+        """cvae.py:149-162 (always under no_grad).
+
+        ``pixel_noise`` = {"seed": int, "ids": (n,) int64, "origins": (n, 2) int32 {row, col} or None} (a model with a
+        variance head; ValueError otherwise, before any plan is built): a DRAW from the likelihood, x_mu + sqrt(x_var) e,
+        is returned in place of the mean x_mu (network units, NCHW).  e is the noise lattice of ``bp_likelihood_draw``:
+        Philox under the key ``seed``, counter (id of the sample, origin + pixel, channel)."""
         with torch.no_grad():
             y = torch.as_tensor(y, device=self.device, dtype=torch.float32)
             self._check_inputs(None, y)
             n = y.shape[0]
+            noise = None
+            if pixel_noise is not None:
+                self._need_var_head("sample_P(pixel_noise=...)")
+                ids, org = PG.noise_lattice(pixel_noise["ids"], pixel_noise.get("origins"), n, *self.dim_x[1:])
+                noise = (torch.from_numpy(PG.seed_word(pixel_noise["seed"]).reshape(1)).to(self.device),
+                         torch.from_numpy(ids).to(self.device),
+                         None if org is None else torch.from_numpy(org).to(self.device))
             aux = self._aux(aux_label, n)
             plan = self._paint_plan(n)
             plan.load_inputs(y, aux, training=self.training)
@@ -1002,7 +1038,11 @@ class CVAE(torch.nn.Module):
             lib, st = self._lib, _stream()
             cx, H, W = self.dim_x
             mu = torch.empty((n, cx, H, W), device=self.device)
-            self._head_to_nchw(plan.mu_head, plan.mu_softplus, mu)
+            if noise is not None:
+                plan.run_draw(*noise)
+                self._head_to_nchw(plan.draw, False, mu)
+            else:
+                self._head_to_nchw(plan.mu_head, plan.mu_softplus, mu)
             if self.predict_var and return_var:
                 lv = torch.empty((n, cx, H, W), device=self.device)
                 self._head_to_nchw(plan.var_head, False, lv)
@@ -1043,7 +1083,7 @@ class CVAE(torch.nn.Module):
         g["graph"].replay()
         return g["out"].clone()
 
-    def paint_graph(self, n, scales=None, modes=None):
+    def paint_graph(self, n, scales=None, modes=None, pixel_noise=False):
         """The captured paint pipeline for batches of ``n`` RAW tiles (configs[4]).  Returns a dict with ``slots``: TWO
         input / parameter / output buffer sets, each with its own captured graph over the SAME launch plans, so that a
         caller uploads batch b+1 straight into one slot and downloads batch b-1 straight out of it while the other
@@ -1072,9 +1112,19 @@ class CVAE(torch.nn.Module):
         [j * levels, (j + 1) * levels)): ``modes = (input mode, (mode of field 0, ...))``, whatever the modes are.  ``out``
         is then (n, F, H, W), ``xf_out`` (n, 4 F) -- the fields' records side by side -- and the store node is
         ``bp_paint_store_fields``: one launch for the whole head.  With ``scales`` the model needs dim_y[0] = levels and
-        dim_x[0] = F * levels."""
+        dim_x[0] = F * levels.
+
+        ``pixel_noise=True`` (a model with a variance head; ValueError otherwise, before anything is built): a graph of
+        its own that paints a DRAW from the likelihood, x_mu + sqrt(x_var) e.  The block gains ``noise_ids`` (n,) int64
+        and ``noise_org`` (n, 2) int32 {row, col} behind its five fields (``bp_likelihood_draw``'s noise lattice, under
+        the key ``seed``; the caller keeps origins >= 0, columns < 2^24 and rows < 2^31: ``paint_graph.noise_lattice``),
+        and a replay runs ``bp_likelihood_draw`` between the generator and the store, which then reads the draw in
+        place of the mean head (every head channel of a split-scale painter gets its own draw before the store sums
+        them).  Without it nothing changes."""
         if self.training:
             raise RuntimeError("paint_graph is an eval-mode (paint) path: call model.train(False) first")
+        if pixel_noise:
+            self._need_var_head("paint_graph(pixel_noise=True)")
         key = (n, "pipeline")
         if scales is not None:
             scales = {"n_scale": int(scales["n_scale"]), "step_size": scales["step_size"],
@@ -1086,9 +1136,11 @@ class CVAE(torch.nn.Module):
         elif modes is not None:
             modes = (int(modes[0]), int(modes[1]))
             key = key + ("modes",) + modes
+        if pixel_noise:
+            key = key + ("noise",)
         g = self._graphs.get(key)
         if g is None:
-            g = self._capture_paint_graph(n, pipeline=True, scales=scales, modes=modes)
+            g = self._capture_paint_graph(n, pipeline=True, scales=scales, modes=modes, pixel_noise=bool(pixel_noise))
             self._graphs[key] = g
         for u in g["units"]:
             u.maybe_pack()
@@ -1101,7 +1153,7 @@ class CVAE(torch.nn.Module):
         for key in [k for k in self._graphs if isinstance(k, tuple) and len(k) > 2 and k[2] == "scales"]:
             del self._graphs[key]
 
-    def _capture_paint_graph(self, n, given_z=False, pipeline=False, scales=None, modes=None):
+    def _capture_paint_graph(self, n, given_z=False, pipeline=False, scales=None, modes=None, pixel_noise=False):
         """Eval-mode layers do not couple the tiles of a batch (batch-norm runs on its running statistics), so the
         batch is painted as BP_PAINT_STREAMS (default 4) sub-batches on as many streams inside one graph: kernels of different layers share
         the CUs and fill each other's stalls (the effect the training step gets from its weight-gradient
@@ -1136,7 +1188,7 @@ class CVAE(torch.nn.Module):
             st["eps"] = torch.zeros((1, n, per_tile), device=dev)
             # parameter block of a slot: one contiguous device buffer = one host-to-device copy per batch
             block = PG.ParamBlock(PG.paint_fields(n, 2 if modes is None else 4, max(self.n_aux, 1),
-                                                  xf_out_width=4 * fields if fields > 1 else None))
+                                                  xf_out_width=4 * fields if fields > 1 else None, noise=pixel_noise))
             st["param_block"], st["block_layout"], st["block_bytes"] = block, block.layout, block.nbytes
             st["slots"] = [PG.new_slot((n, 1 if scales is not None else cy, H, W),
                                        (n, fields if fields > 1 else 1 if scales is not None else cx, H, W), block, dev)
@@ -1147,8 +1199,11 @@ class CVAE(torch.nn.Module):
         h = n // parts
         plans = [self._paint_plan(h)] + [_Plan(self, h, False, False, samples=1) for _ in range(parts - 1)]
         st["plans"] = plans
+        # (what paint_graph re-packs before a replay when weights changed.  The variance head runs in every replay, but
+        #  only a draw from the likelihood reads it: its units are listed for such a graph, and stay out of the others)
         st["units"] = PlanBase.flat_units([u for plan in plans
                                            for us in [plan.p_units] + plan.g_units + [plan.mu_units, plan.y_units]
+                                           + ([plan.var_units] if pixel_noise else [])
                                            for u in us])
         others = [torch.cuda.Stream(device=dev) for _ in range(parts - 1)]
         if scales is not None:
@@ -1172,6 +1227,16 @@ class CVAE(torch.nn.Module):
             # The load and store steps of this capture, chosen once: the legacy shift-log entry points (two-double rows)
             # or, with ``modes``, their ``_mode`` forms, which hold the mode as a constant of the graph.
             lib, y_net = self._lib, bool(plans[0].y_units)
+            if pixel_noise:
+                for plan in plans:
+                    plan.draw_slot()
+
+            def head(plan):
+                """What the store reads, (view, softplus): the mean head, or the draw (bp_likelihood_draw has applied
+                the softplus)."""
+                if pixel_noise:
+                    return C.byref(plan.draw.view), 0
+                return C.byref(plan.mu_head.view), 1 if plan.mu_softplus else 0
 
             def entry(name, mode):
                 return getattr(lib, name) if modes is None else functools.partial(getattr(lib, name + "_mode"), mode)
@@ -1182,8 +1247,8 @@ class CVAE(torch.nn.Module):
                 inc = int(scales["include_original"]) if scales is not None else 0
 
                 def store_fields(plan, xf, out, sm):
-                    return lib.bp_paint_store_fields(field_modes, fields, levels, inc, C.byref(plan.mu_head.view), None,
-                                                     1 if plan.mu_softplus else 0, xf, out, sm)
+                    src, sp = head(plan)
+                    return lib.bp_paint_store_fields(field_modes, fields, levels, inc, src, None, sp, xf, out, sm)
             if scales is not None:
                 what = " (scales)"
                 load_fn, store_fn = entry("bp_paint_load_scales2", m_in), entry("bp_paint_store_scales", m_out)
@@ -1194,8 +1259,8 @@ class CVAE(torch.nn.Module):
                                    C.byref(plan.hy_slot.view), sm)
 
                 def store(plan, xf, out, sm):
-                    return store_fn(C.byref(plan.mu_head.view), None, 1 if plan.mu_softplus else 0,
-                                    sc["include_original"], xf, out, sm)
+                    src, sp = head(plan)
+                    return store_fn(src, None, sp, sc["include_original"], xf, out, sm)
             else:
                 what = ""
                 # the transformed tile goes where the generator needs it: with a p_y_in network that is y2 alone
@@ -1208,7 +1273,8 @@ class CVAE(torch.nn.Module):
                     return load_fn(raw, cy, xf, auxp, plan.caux, *dst, sm)
 
                 def store(plan, xf, out, sm):
-                    return store_fn(C.byref(plan.mu_head.view), None, 1 if plan.mu_softplus else 0, xf, out, sm)
+                    src, sp = head(plan)
+                    return store_fn(src, None, sp, xf, out, sm)
             if fields > 1:
                 store, what = store_fields, what + f" ({fields} fields)"
 
@@ -1226,6 +1292,8 @@ class CVAE(torch.nn.Module):
                                                    eps.shape[-1], L.ptr(eps), sm), "philox")
             plan.run_latent(eps.reshape(1, h, *self.dim_z), use_q=False)
             plan.run_generator(False)
+            if pixel_noise:
+                plan.run_draw(sl["seed"], sl["noise_ids"][lo:lo + h], sl["noise_org"][lo:lo + h])
             L.check(store(plan, L.ptr(sl["xf_out"][lo:lo + h]), L.ptr(sl["out"][lo:lo + h]), sm), "paint store" + what)
 
         def paint(plan, lo, sl):

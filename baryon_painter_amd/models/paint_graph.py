@@ -36,15 +36,51 @@ class ParamBlock:
         return out
 
 
-def paint_fields(n, xf_width, aux_width=1, xf_out_width=None):
+def paint_fields(n, xf_width, aux_width=1, xf_out_width=None, noise=False):
     """The fields of a paint pipeline's block for batches of ``n`` tiles: ``xf_in`` / ``xf_out`` (n, xf_width) float64
     parameter rows of the transform and its inverse, ``tile_ids`` (n,) int64, ``seed`` (1,) int64 Philox key, ``aux``
     (n, aux_width) float32 value of the conditioning plane.  Both models carry all five, so that one caller fills either
     model's block.  ``xf_out_width``: the width of ``xf_out`` where it differs (a CVAE with several label fields: the
-    fields' rows side by side)."""
-    return [("xf_in", torch.float64, (n, xf_width)),
-            ("xf_out", torch.float64, (n, xf_width if xf_out_width is None else xf_out_width)),
-            ("tile_ids", torch.int64, (n,)), ("seed", torch.int64, (1,)), ("aux", torch.float32, (n, aux_width))]
+    fields' rows side by side).  ``noise`` (a pipeline that paints draws from the likelihood, ``bp_likelihood_draw``):
+    ``noise_ids`` (n,) int64 and ``noise_org`` (n, 2) int32 {row, col} follow behind the five."""
+    fields = [("xf_in", torch.float64, (n, xf_width)),
+              ("xf_out", torch.float64, (n, xf_width if xf_out_width is None else xf_out_width)),
+              ("tile_ids", torch.int64, (n,)), ("seed", torch.int64, (1,)), ("aux", torch.float32, (n, aux_width))]
+    if noise:
+        fields += [("noise_ids", torch.int64, (n,)), ("noise_org", torch.int32, (n, 2))]
+    return fields
+
+
+def seed_word(seed):
+    """The Philox key ``seed`` (any Python int, taken modulo 2^64) as the int64 a block's ``seed`` field holds."""
+    import numpy as np
+    return np.array(int(seed) & 0xFFFFFFFFFFFFFFFF, dtype=np.uint64).astype(np.int64)
+
+
+def noise_lattice(ids, origins, n, h, w):
+    """``ids`` (n,) int64 and ``origins`` (n, 2) int32 {row, col} (None: None, all zero) of ``bp_likelihood_draw`` for
+    ``n`` tiles of ``h`` x ``w`` pixels, as NumPy arrays, checked for what the kernel leaves to its caller: origins are
+    not negative, lattice columns stay below 2^24 and rows below 2^31 (ValueError).  Needs no GPU."""
+    import numpy as np
+    ids = np.asarray(ids)
+    if ids.shape != (n,) or ids.dtype.kind not in "iu":
+        raise ValueError(f"noise ids must be {n} integers, got shape {ids.shape} of {ids.dtype}")
+    ids = ids.astype(np.int64)
+    if origins is None:
+        org = None
+    else:
+        org = np.asarray(origins)
+        if org.shape != (n, 2) or org.dtype.kind not in "iu":
+            raise ValueError(f"noise origins must be ({n}, 2) integers {{row, col}}, got shape {org.shape} of {org.dtype}")
+        org = org.astype(np.int64)
+        if (org < 0).any():
+            raise ValueError("noise origins must not be negative")
+        if (org[:, 0] + h > 2 ** 31).any() or (org[:, 1] + w > 2 ** 24).any():
+            raise ValueError("the noise lattice has 2^31 rows and 2^24 columns: an origin puts a tile beyond them")
+        org = np.ascontiguousarray(org, dtype=np.int32)
+    if h > 2 ** 31 or w > 2 ** 24:
+        raise ValueError("the noise lattice has 2^31 rows and 2^24 columns: the tile is larger")
+    return np.ascontiguousarray(ids), org
 
 
 def new_slot(raw_shape, out_shape, block, device):

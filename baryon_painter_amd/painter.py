@@ -52,7 +52,13 @@ class Painter:
         self.__dict__.pop("_paint_host_buffers", None)
         self.__dict__.pop("_plane_device_buffers", None)
 
-    def paint_stream(self, inputs, z, batch_size=64, tile_ids=None, seed=0, rank=0, world_size=1, out=None):
+    def _need_pixel_noise(self):
+        """ValueError unless this painter can paint draws from its likelihood (``pixel_noise=True``): a CVAE with a
+        variance head.  No side effects: nothing is captured, no random number is drawn."""
+        raise ValueError(f"pixel_noise=True: {type(self).__name__} has no likelihood with a variance head to draw from")
+
+    def paint_stream(self, inputs, z, batch_size=64, tile_ids=None, seed=0, rank=0, world_size=1, out=None,
+                     pixel_noise=False, noise_ids=None, noise_origins=None):
         """Paint MANY raw tiles: ``inputs`` (N, H, W) float32 host array (NumPy, memory map, or a pinned torch tensor),
         redshifts ``z`` (scalar or (N,)) -> (N, H, W) float32 physical tiles.  The production form of ``paint``
         (process_SLICS.py:201-218 calls it tile by tile):
@@ -69,9 +75,17 @@ class Painter:
             process per GPU, no collective: tiles are independent) and returns (block, (lo, hi));
           * a CVAE painter with F > 1 label fields returns (N, F, H, W): field j from head channels
             [j * nf, (j + 1) * nf) through ``label_fields[j]``'s inverse, all fields stored by one launch
-            (``bp_paint_store_fields``); ``out``, where given, has that shape."""
+            (``bp_paint_store_fields``); ``out``, where given, has that shape;
+          * ``pixel_noise=True`` (a CVAE painter with a variance head; ValueError otherwise, before any capture): every
+            tile is a DRAW from the likelihood, x_mu + sqrt(x_var) e in network units in front of the inverse
+            transform, not its mean.  e of tile i is a window of a noise lattice (``bp_likelihood_draw``) under the key
+            ``seed``: lattice ``noise_ids[i]`` [default: ``tile_ids[i]``], window origin ``noise_origins[i]`` =
+            (row, col) >= 0 [default: (0, 0)].  Like the latent noise it does not depend on batches or ranks; tiles that
+            share an id see the same e where their windows overlap."""
         model = self.model
         model.train(False)
+        if pixel_noise:
+            self._need_pixel_noise()
         H, W = self._tile_shape()
         N = len(inputs)
         if tuple(inputs.shape[1:]) != (H, W):
@@ -81,11 +95,14 @@ class Painter:
         per = (N + world_size - 1) // world_size
         lo, hi = min(rank * per, N), min((rank + 1) * per, N)
         params, scales, modes = self._device_paint_parameters(zs[lo:hi])     # (NotImplementedError before any capture)
+        if pixel_noise:
+            params = _with_noise(params, ids if noise_ids is None else noise_ids, noise_origins, N, H, W, lo, hi)
         result = _paint_stream_pipeline(self, model, inputs, (H, W), lo, hi, int(batch_size), params, ids[lo:hi], seed,
                                         out, scales, modes)
         return (result, (lo, hi)) if world_size > 1 else result
 
-    def _paint_plane_device(self, delta, geo, z, weight_map, batch_size, tile_ids, seed, regularise_std=None, out=None):
+    def _paint_plane_device(self, delta, geo, z, weight_map, batch_size, tile_ids, seed, regularise_std=None, out=None,
+                            pixel_noise=False):
         """The device form of ``lightcone.paint_plane`` (on_device=True): ``geo`` is ``lightcone.plane_geometry``'s,
         ``weight_map`` the host's ``make_weight_map`` (float64, uploaded as it is), ``tile_ids`` / ``seed`` / ``batch_size``
         those the host path hands to ``paint_stream``.  Per batch, on ONE stream: the tiles are cut (and resampled) from
@@ -94,7 +111,8 @@ class Painter:
         (bp_plane_blend); bp_plane_finish divides.  Returns the (n_plane, n_plane) float64 plane, or ``out`` (a CUDA
         float64 tensor of that shape) filled in place.  A painter with F > 1 label fields blends its (B, F, tile, tile)
         ``out`` with bp_plane_blend_fields, each field into a plane of its own with its own regularisation mask: the
-        plane, and ``out``, is (F, n_plane, n_plane)."""
+        plane, and ``out``, is (F, n_plane, n_plane).  ``pixel_noise``: as on the host path, every tile draws from the
+        lattice ``tile_ids[0]`` at its destination origin ``geo["dst"]``."""
         model = self.model
         model.train(False)
         tile, W = self._tile_shape()
@@ -102,7 +120,14 @@ class Painter:
             raise NotImplementedError("device planes need square tiles")
         if tuple(weight_map.shape) != (tile, tile):
             raise ValueError(f"weight map {weight_map.shape} does not match the model's {tile}^2 tiles")
+        if pixel_noise:
+            self._need_pixel_noise()
         params, scales, modes = self._device_paint_parameters(np.full(len(geo["origins"]), float(z)))
+        if pixel_noise:
+            # one lattice per plane, each tile's window at its place in the painted plane: where tiles overlap they
+            # carry the same noise, and the feathered blend does not average it away (lightcone.paint_plane)
+            n = len(geo["origins"])
+            params = _with_noise(params, np.full(n, tile_ids[0], dtype=np.int64), geo["dst"], n, tile, tile, 0, n)
         return _paint_plane_pipeline(self, model, tile, delta, geo, int(batch_size), params, tile_ids, seed, weight_map,
                                      regularise_std, out, scales, modes)
 
@@ -349,11 +374,30 @@ class CVAEPainter(Painter):
         return np.stack([self.inverse_transform(head[j * nf:(j + 1) * nf][None] if nf == 1 else head[j * nf:(j + 1) * nf],
                                                 field=f, z=z) for j, f in enumerate(self.label_fields)])
 
-    def paint(self, input, z=0.0, transform=True, inverse_transform=True):
+    def _need_pixel_noise(self):
+        self.model._need_var_head("pixel_noise=True")
+
+    @staticmethod
+    def _fresh_seed(seed):
+        """``seed``, or a fresh Philox key from torch's global generator (as ``lightcone.paint_plane`` draws one)."""
+        return int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else seed
+
+    def paint(self, input, z=0.0, transform=True, inverse_transform=True, pixel_noise=False, seed=None, noise_id=0,
+              noise_origin=(0, 0)):
         """Paint one tile (painter.py:371-392): dark-matter tile (H,W) at redshift z -> pressure.  A painter with F > 1
         label fields returns (F, H, W), field j from head channels [j * nf, (j + 1) * nf) (where the reference raises
-        NotImplementedError, painter.py:388-389); ``inverse_transform=False`` gives the (1, F * nf, H, W) head."""
+        NotImplementedError, painter.py:388-389); ``inverse_transform=False`` gives the (1, F * nf, H, W) head.
+
+        ``pixel_noise=True`` (a model with a variance head; ValueError otherwise): the tile is a draw from the
+        likelihood, x_mu + sqrt(x_var) e in network units, not its mean -- ``paint_stream``'s noise: Philox under the key
+        ``seed`` (None: a fresh key from torch's global generator) on the lattice ``noise_id``, window origin
+        ``noise_origin`` = (row, col)."""
         self.model.train(False)
+        noise = None
+        if pixel_noise:
+            self._need_pixel_noise()
+            noise = {"seed": self._fresh_seed(seed), "ids": np.array([noise_id], dtype=np.int64),
+                     "origins": np.asarray(noise_origin).reshape(1, 2)}
         with torch.no_grad():
             y = self.transform(input, field=self.input_field, z=z) if transform and self.transform is not None \
                 else input
@@ -363,7 +407,7 @@ class CVAEPainter(Painter):
                 raise ValueError(f"Shape mismatch between input and model: {input.shape} vs {self.model.dim_y}")
             yt = torch.tensor(y, device=self.compute_device, dtype=torch.float32)
             aux = torch.tensor(z, device=self.compute_device, dtype=yt.dtype)
-            prediction = self.model.sample_P(yt, aux_label=aux).cpu().numpy()
+            prediction = self.model.sample_P(yt, aux_label=aux, pixel_noise=noise).cpu().numpy()
         if inverse_transform and self.inverse_transform is not None:
             if len(self.label_fields) > 1:
                 return self._inverse_fields(prediction[0], z)
@@ -372,14 +416,26 @@ class CVAEPainter(Painter):
             return self.inverse_transform(prediction, field=self.label_fields[0], z=z)
         return prediction
 
-    def paint_batch(self, inputs, z, transform=True, inverse_transform=True, batch_size=64, use_graph=True):
+    def paint_batch(self, inputs, z, transform=True, inverse_transform=True, batch_size=64, use_graph=True,
+                    pixel_noise=False, seed=None, noise_ids=None, noise_origins=None):
         """Throughput form of ``paint``: many tiles (N,H,W) with redshifts (N,) in batches through the
         same eval-mode forward (BASELINE.json configs[4]); per-tile results equal ``paint``'s up to
         the prior noise draw.  (N, H, W), or (N, F, H, W) for a painter with F > 1 label fields, each field through
-        its own inverse (``_inverse_fields``)."""
+        its own inverse (``_inverse_fields``).
+
+        ``pixel_noise=True``: draws from the likelihood as in ``paint``, tile i on the lattice ``noise_ids[i]``
+        [default: i] at ``noise_origins[i]`` [default: (0, 0)] under the key ``seed`` (None: a fresh one); these batches
+        go through ``sample_P`` (the graphed form has no draw)."""
         self.model.train(False)
         inputs = np.asarray(inputs)
         zs = np.broadcast_to(np.asarray(z, dtype=np.float64), (inputs.shape[0],))
+        if pixel_noise:
+            from .models import paint_graph as PG
+            self._need_pixel_noise()
+            N = inputs.shape[0]
+            n_ids, n_org = PG.noise_lattice(np.arange(N, dtype=np.int64) if noise_ids is None else noise_ids,
+                                            noise_origins, N, *self.model.dim_x[1:])
+            seed = self._fresh_seed(seed)
         out = []
         with torch.no_grad():
             for s in range(0, inputs.shape[0], batch_size):
@@ -394,8 +450,13 @@ class CVAEPainter(Painter):
                 yt = torch.tensor(y, device=self.compute_device, dtype=torch.float32)
                 aux = torch.tensor(zc, device=self.compute_device, dtype=torch.float32)
                 graphed = use_graph and self.model._eps_override is None and yt.shape[0] == batch_size
-                sample = self.model.sample_P_graphed if graphed else self.model.sample_P
-                pred = sample(yt, aux_label=aux).cpu().numpy()
+                if pixel_noise:
+                    e = s + yt.shape[0]
+                    pred = self.model.sample_P(yt, aux_label=aux, pixel_noise={
+                        "seed": seed, "ids": n_ids[s:e], "origins": None if n_org is None else n_org[s:e]}).cpu().numpy()
+                else:
+                    sample = self.model.sample_P_graphed if graphed else self.model.sample_P
+                    pred = sample(yt, aux_label=aux).cpu().numpy()
                 if inverse_transform and self.inverse_transform is not None and len(self.label_fields) > 1:
                     pred = np.stack([self._inverse_fields(p, float(zz)) for p, zz in zip(pred, zc)])
                 elif inverse_transform and self.inverse_transform is not None:
@@ -562,7 +623,8 @@ class CVAEPainter(Painter):
 # The device paint pipelines, shared by the painters whose model has a ``paint_graph(B)`` (models.cvae.CVAE,
 # models.cgan.CGAN): the models differ in what their captured graph does and in the columns of the transform
 # parameters, not in how batches are fed to it.  ``params``: per tile of this call, ``xf_in`` / ``xf_out`` (n, k) float64
-# rows of the graph's ``block_layout`` and ``aux`` (n,) the value of its conditioning plane.
+# rows of the graph's ``block_layout`` and ``aux`` (n,) the value of its conditioning plane.  ``params`` that also hold
+# ``noise_ids`` (n,) int64 and ``noise_org`` (n, 2) int32 (``_with_noise``) select the graph that paints with pixel noise.
 
 def _fill_block(hv, params, ids, a, b, B):
     """Tiles [a, b) of ``params`` / ``ids`` into the views of one block of ``B`` rows."""
@@ -571,14 +633,29 @@ def _fill_block(hv, params, ids, a, b, B):
     hv["xf_out"][:m] = params["xf_out"][a:b].reshape(m, -1)       # (several label fields: (m, F, 4) -> (m, 4 F))
     hv["aux"][:m, 0] = params["aux"][a:b]
     hv["tile_ids"][:m] = ids[a:b]
+    keys = ("xf_in", "xf_out", "aux", "tile_ids")
+    if "noise_ids" in params:                     # (a pipeline that paints with pixel noise: _with_noise)
+        hv["noise_ids"][:m] = params["noise_ids"][a:b]
+        hv["noise_org"][:m] = params["noise_org"][a:b]
+        keys += ("noise_ids", "noise_org")
     if m < B:                                     # a short last batch: pad with its last tile's parameters
-        for k in ("xf_in", "xf_out", "aux", "tile_ids"):
+        for k in keys:
             hv[k][m:] = hv[k][m - 1]
 
 
-def _paint_graph(model, B, scales, modes):
+def _with_noise(params, noise_ids, noise_origins, N, H, W, lo, hi):
+    """``params`` of tiles [lo, hi) of ``N`` with the two fields of a pipeline that paints with pixel noise:
+    ``noise_ids`` / ``noise_org`` of all N tiles, checked (``paint_graph.noise_lattice``: ValueError), cut to [lo, hi)."""
+    from .models import paint_graph as PG
+    ids, org = PG.noise_lattice(noise_ids, noise_origins, N, H, W)
+    if org is None:
+        org = np.zeros((N, 2), np.int32)
+    return dict(params, noise_ids=ids[lo:hi], noise_org=org[lo:hi])
+
+
+def _paint_graph(model, B, scales, modes, pixel_noise=False):
     """``model.paint_graph(B)`` with the keywords only a CVAE's takes, where they say something."""
-    kw = {k: v for k, v in (("scales", scales), ("modes", modes)) if v is not None}
+    kw = {k: v for k, v in (("scales", scales), ("modes", modes), ("pixel_noise", pixel_noise or None)) if v is not None}
     return model.paint_graph(B, **kw)
 
 
@@ -606,7 +683,7 @@ def _paint_stream_pipeline(painter, model, inputs, tile_shape, lo, hi, B, params
     shape = (hi - lo, F, H, W) if F > 1 else (hi - lo, H, W)
     if F > 1 and out is not None and tuple(out.shape) != shape:
         raise ValueError(f"out must have the shape {shape} of {F} label fields, got {tuple(out.shape)}")
-    g = _paint_graph(model, B, scales, modes)
+    g = _paint_graph(model, B, scales, modes, "noise_ids" in params)
     torch_in = isinstance(inputs, torch.Tensor)
     result = out if out is not None else np.empty(shape, np.float32)
     torch_out = isinstance(result, torch.Tensor)
@@ -722,7 +799,7 @@ def _paint_plane_pipeline(painter, model, tile, delta, geo, B, params, tile_ids,
                             out.dtype != torch.float64 or tuple(out.shape) != shape or
                             not out.is_contiguous()):
         raise ValueError(f"out must be a contiguous float64 ({', '.join(str(v) for v in shape)}) tensor on {dev}")
-    g = _paint_graph(model, B, scales, modes)
+    g = _paint_graph(model, B, scales, modes, "noise_ids" in params)
     # per-plane parameter blocks, one per batch, built like paint_stream's pinned ones and uploaded once: a batch
     # then costs one device-to-device copy of its block into the slot
     block = g["param_block"]
@@ -965,7 +1042,10 @@ class CGANPainter(Painter):
         return ds.get_input_sample(i, transform=False), ds.get_label_sample(i, transform=False)[0], z
 
     # ------------------------------------------------------------------------------ inference
-    def paint(self, input, z=0.0, transform=True, inverse_transform=True):
+    def paint(self, input, z=0.0, transform=True, inverse_transform=True, pixel_noise=False):
+        """``pixel_noise=True`` is a ValueError: the generator has no likelihood to draw from."""
+        if pixel_noise:
+            self._need_pixel_noise()
         self.model.train(False)
         y = self.transform(input, "dm", z) if transform else np.asarray(input, np.float32)
         t = self.model.tile_size
@@ -976,12 +1056,15 @@ class CGANPainter(Painter):
             return self.inverse_transform(pred[0, 0], "pressure", z)
         return pred
 
-    def paint_batch(self, inputs, z, transform=True, inverse_transform=True, batch_size=64, use_graph=True):
+    def paint_batch(self, inputs, z, transform=True, inverse_transform=True, batch_size=64, use_graph=True,
+                    pixel_noise=False):
         """Throughput form of ``paint``: many tiles (N, H, W) with redshifts (N,) or one, in batches through the same
         eval-mode forward, with the host transforms of ``paint``.  Returns (N, H, W) float64 physical tiles, or the
         (N, 1, H, W) float32 network output with ``inverse_transform=False``.  ``use_graph`` is accepted for
         ``CVAEPainter.paint_batch``'s signature and has no effect: this forward is launched eagerly (the graph-captured
-        form is ``paint_stream``)."""
+        form is ``paint_stream``).  ``pixel_noise=True`` is a ValueError, as in ``paint``."""
+        if pixel_noise:
+            self._need_pixel_noise()
         self.model.train(False)
         inputs = np.asarray(inputs)
         t = self.model.tile_size

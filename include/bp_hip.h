@@ -436,6 +436,26 @@ int bp_philox_normal(uint64_t seed, const int64_t* tile_ids, int32_t n, int32_t 
  * (the reference draws fresh torch.randn per tile, cvae.py:64: planes of a light cone must not share their noise). */
 int bp_philox_normal_dev(const uint64_t* seed_dev, const int64_t* tile_ids, int32_t n, int32_t L, int32_t per_tile,
                          float* eps, void* stream);
+/* A draw from the likelihood of a CVAE with a variance head (painting with pixel noise): for every element
+ * (n, y, x, ch) of three fp32 views of equal (n, h, w, c), any cstride and coff,
+ *   t = softplus ? softplus(mu) : mu          (bp_paint_store's expression)
+ *   out = t + expf(0.5f * log_var) * e        (float32; the product and the sum each round once; where the product is
+ *                                              zero, out is t itself, the sign of a zero and a NaN's payload included)
+ * e is the float32 value of the r-th Box-Muller normal (in double, as bp_philox_normal's) of the Philox4x32-10 block
+ * with key *seed_dev and counter (X + ((ch / 4) << 24), 0x80000000 | Y, id low, id high), r = ch % 4,
+ * Y = origins[n][0] + y, X = origins[n][1] + x, id = noise_ids[n].  The counter is a pixel of a noise LATTICE: samples
+ * with one id whose origins put them over the same lattice pixel get the same e there (the overlapping tiles of a plane).
+ * Bit 31 of counter word 1 keeps these blocks apart from bp_philox_normal's (l < 2^31) under the same key.
+ *   seed_dev  : device, read at run time (a captured launch serves every seed)
+ *   noise_ids : device, (n) int64
+ *   origins   : device, (n, 2) int32 {row, col}, or NULL for all zero
+ * `out` may be `mu` or `log_var` itself (each element is read and written by one thread).  Before anything is
+ * launched: BP_EINVAL for a null pointer other than `origins`, a malformed view or views that differ in n, h, w or c;
+ * then BP_EUNSUPPORTED for a bf16 view or n * h * w * c >= 2^31.  THE CALLER GUARANTEES what cannot be checked without
+ * reading device memory: origins >= 0, X < 2^24 and Y < 2^31 for every element (beyond them lattice pixels share
+ * their counters).  One launch, no atomics, no workspace, no host synchronisation. */
+int bp_likelihood_draw(const bp_view* mu, int32_t softplus, const bp_view* log_var, const uint64_t* seed_dev,
+                       const int64_t* noise_ids, const int32_t* origins, const bp_view* out, void* stream);
 
 /* ---- light-cone planes (lightcone.paint_plane(on_device=True), process_SLICS.py:198-220) -----------------------
  * A periodic plane is cut into the paint graph's raw tiles, and the painted tiles are blended into float64 planes, on
