@@ -143,6 +143,8 @@ SIGNATURES = {
                                              C.c_size_t, _VP, _VP, _P]),
     "bp_paint_store_scales_mode": (C.c_int, [C.c_int32, _VP, _PWP, C.c_int32, C.c_int32, _P, _P, _P]),
     "bp_paint_store_fields": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _VP, _PWP, C.c_int32, _P, _P, _P]),
+    "bp_paint_store_moments": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _VP, _PWP, C.c_int32, _P, C.c_int32, _P, _P,
+                                         _P, _P]),
     "bp_philox_normal": (C.c_int, [C.c_uint64, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "bp_philox_normal_dev": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "bp_likelihood_draw": (C.c_int, [_VP, C.c_int32, _VP, _P, _P, _P, _VP, _P]),

@@ -11,6 +11,9 @@
 //   bp_paint_store_fields   the store of a head with several label fields: per field bp_paint_store_mode's (one level)
 //                     or bp_paint_store_scales_mode's (several) expression with the field's own mode and records, in one
 //                     launch
+//   bp_paint_store_moments  the store of an ensemble: the head holds K latent draws per tile, and the float64 mean and
+//                     population variance over the draws of what bp_paint_store_fields would store leave (and, on
+//                     request, every draw)
 //   bp_paint_load_cam / bp_paint_store_cam   the same pair for the conditional GAN: its "shift-log-cam" transform into the
 //                     tanh range, log(x / sigma + 1) / k0 - k1 (painter.CGANPainter.transform), and the generator's tanh
 //                     head followed by the inverse, both evaluated in double as the host's NumPy expressions are
@@ -79,6 +82,7 @@ __global__ __launch_bounds__(RB) void paint_store_kernel(const float* src, int s
 // Modes of up to FIELDS_MAX label fields, four bits each, as a kernel argument (the entry point's array is the host's)
 constexpr int FIELDS_MAX = 64;
 constexpr int LEVELS_MAX = 16;
+constexpr int DRAWS_MAX = 64;                                   // draws of an ensemble (bp_paint_store_moments)
 struct FieldModes {
   unsigned w[FIELDS_MAX / 8];
 };
@@ -92,6 +96,19 @@ __device__ __forceinline__ float rc_inverse_of(int mode, const RcRec& r, float v
     case RC_X_1PX: return rc_inverse<RC_X_1PX>(r, v);
     default: return rc_inverse<RC_INV_X>(r, v);
   }
+}
+
+// What a field's inverse reads at one pixel: activation and softplus per channel of the field's channels [c0, c0 + used)
+// at `s`, then the float32 sum in channel order (used == 1: the channel itself).
+__device__ __forceinline__ float field_sum(const float* s, int c0, int used, const PW& pw, int softplus) {
+#pragma clang fp contract(off)
+  float v = 0.f;
+  for (int ch = 0; ch < used; ++ch) {
+    float t = pw_apply(pw, c0 + ch, s[c0 + ch]);
+    if (softplus) t = softplus_f(t);
+    v = ch == 0 ? t : v + t;                                    // ((c0 + c1) + c2) ...: NumPy's order for sum(axis=0)
+  }
+  return v;
 }
 
 // The head of a painter with several label fields: field f owns channels [f * levels, (f + 1) * levels) and plane
@@ -113,16 +130,120 @@ __global__ __launch_bounds__(RB) void paint_store_fields_kernel(const float* src
   const unsigned yx = i - nu * hw;
   const float* s = src + (int64_t)i * src_cs + src_co;
   for (int f = 0; f < fields; ++f) {
-    const int c0 = f * levels;
-    float v = 0.f;
-    for (int ch = 0; ch < used; ++ch) {
-      float t = pw_apply(pw, c0 + ch, s[c0 + ch]);
-      if (softplus) t = softplus_f(t);
-      v = ch == 0 ? t : v + t;                                  // ((c0 + c1) + c2) ...: NumPy's order for sum(axis=0)
-    }
+    const float v = field_sum(s, f * levels, used, pw, softplus);
     const int mode = (int)((modes.w[f >> 3] >> ((f & 7) * 4)) & 15u);
     const unsigned pl = nu * (unsigned)fields + (unsigned)f;    // plane of the destination; < n * fields
     dst[(int64_t)pl * hw + yx] = rc_inverse_of(mode, rc_record(rc_table4(records), (int64_t)pl), v);
+  }
+}
+
+// An ENSEMBLE's store: the head holds draws * n samples, sample l * n + m = draw l of tile m, and what leaves is the
+// mean and the population variance over the draws of what paint_store_fields_kernel would store for each sample (p_l,
+// with tile m's record), (n, fields, H, W) each, and optionally every p_l, (n, draws, fields, H, W).
+//   S = ((p_0 + p_1) + ...) + p_{K-1},  M = S / K,  Q = ((p_0 - M)^2 + (p_1 - M)^2) + ...,  mean = (float) M,
+//   var = (float) (Q / K)      in float64, ascending l, no contraction: one thread owns a pixel's draws, no atomics.
+// Thread mapping: paint_store_fields_kernel's, over the pixels of the n TILES (V = 1), the draws of a pixel
+// `pixels * src_cs` floats apart.  V = 4: four consecutive pixels of a one-channel head with cstride 1 (the entry point
+// checks hw % 4 == 0 and the alignment of every pointer), read and written as float4.
+// KMAX > 0 (draws <= KMAX): the p_l stay in registers between the two sums.  KMAX == 0: a second pass reads and
+// evaluates them again -- the same instructions on the same values, hence the same bits.
+template <int V>
+__device__ __forceinline__ void moments_draw(const float* s, int c0, int used, const PW& pw, int softplus, int mode,
+                                             const RcRec& rec, float (&p)[V]) {
+#pragma clang fp contract(off)
+  if (V == 1) {
+    p[0] = rc_inverse_of(mode, rec, field_sum(s, c0, used, pw, softplus));
+  } else {                                                      // (one field of one channel, c0 == 0)
+    const float4 q = *reinterpret_cast<const float4*>(s);
+    const float t[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      float x = pw_apply(pw, 0, t[v]);
+      if (softplus) x = softplus_f(x);
+      p[v] = rc_inverse_of(mode, rec, x);
+    }
+  }
+}
+
+template <int V>
+__device__ __forceinline__ void moments_put(float* dst, const float (&p)[V]) {
+  if (V == 1) *dst = p[0];
+  else *reinterpret_cast<float4*>(dst) = make_float4(p[0], p[1], p[2], p[3]);
+}
+
+template <int KMAX, int V>
+__global__ __launch_bounds__(RB) void paint_store_moments_kernel(const float* src, int src_cs, int src_co, int fields,
+                                                                 int levels, int used, FieldModes modes, PW pw,
+                                                                 int softplus, const double* records, int draws,
+                                                                 float* mean, float* var, float* out, unsigned hw,
+                                                                 unsigned pixels) {
+#pragma clang fp contract(off)
+  const unsigned i = (blockIdx.x * RB + threadIdx.x) * V;       // first pixel m * hw + yx of this thread
+  if (i >= pixels) return;
+  const unsigned nu = (hw & (hw - 1u)) == 0u ? i >> (__ffs((int)hw) - 1) : i / hw;              // (see paint_load_kernel)
+  const unsigned yx = i - nu * hw;
+  const int64_t lstride = (int64_t)pixels * src_cs;             // floats between two draws of a pixel
+  const float* s0 = src + (int64_t)i * src_cs + src_co;
+  const double K = (double)draws;
+  for (int f = 0; f < fields; ++f) {
+    const int c0 = f * levels;
+    const int mode = (int)((modes.w[f >> 3] >> ((f & 7) * 4)) & 15u);
+    const unsigned pl = nu * (unsigned)fields + (unsigned)f;    // plane of mean / var; < n * fields
+    const RcRec rec = rc_record(rc_table4(records), (int64_t)pl);
+    // plane (m, l, f) of the draws: ((m * K + l) * fields + f) * hw + yx
+    float* o = out ? out + ((int64_t)nu * draws * fields + f) * hw + yx : nullptr;
+    const int64_t ostride = (int64_t)fields * hw;
+    double S[V], Q[V], M[V];
+    if constexpr (KMAX > 0) {
+      float p[KMAX][V];
+#pragma unroll
+      for (int l = 0; l < KMAX; ++l) {
+        if (l < draws) {
+          moments_draw<V>(s0 + l * lstride, c0, used, pw, softplus, mode, rec, p[l]);
+          if (o) moments_put<V>(o + l * ostride, p[l]);
+#pragma unroll
+          for (int v = 0; v < V; ++v) S[v] = l == 0 ? (double)p[l][v] : S[v] + (double)p[l][v];
+        }
+      }
+#pragma unroll
+      for (int v = 0; v < V; ++v) M[v] = S[v] / K;
+#pragma unroll
+      for (int l = 0; l < KMAX; ++l) {
+        if (l < draws) {
+#pragma unroll
+          for (int v = 0; v < V; ++v) {
+            const double d = (double)p[l][v] - M[v];
+            Q[v] = l == 0 ? d * d : Q[v] + d * d;
+          }
+        }
+      }
+    } else {
+      float p[V];
+      for (int l = 0; l < draws; ++l) {
+        moments_draw<V>(s0 + l * lstride, c0, used, pw, softplus, mode, rec, p);
+        if (o) moments_put<V>(o + l * ostride, p);
+#pragma unroll
+        for (int v = 0; v < V; ++v) S[v] = l == 0 ? (double)p[v] : S[v] + (double)p[v];
+      }
+#pragma unroll
+      for (int v = 0; v < V; ++v) M[v] = S[v] / K;
+      for (int l = 0; l < draws; ++l) {
+        moments_draw<V>(s0 + l * lstride, c0, used, pw, softplus, mode, rec, p);
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+          const double d = (double)p[v] - M[v];
+          Q[v] = l == 0 ? d * d : Q[v] + d * d;
+        }
+      }
+    }
+    float mo[V], vo[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      mo[v] = (float)M[v];
+      vo[v] = (float)(Q[v] / K);
+    }
+    moments_put<V>(mean + (int64_t)pl * hw + yx, mo);
+    moments_put<V>(var + (int64_t)pl * hw + yx, vo);
   }
 }
 
@@ -268,6 +389,19 @@ __global__ __launch_bounds__(RB) void likelihood_draw_kernel(const float* mu, in
 
 static inline unsigned nblocks(int64_t total) { return (unsigned)((total + RB - 1) / RB); }
 
+template <int V>
+static void launch_moments(int kmax, unsigned blocks, hipStream_t st, const bp_view* src, int fields, int levels, int used,
+                           const FieldModes& fm, PW pw, int softplus, const double* records, int draws, float* mean,
+                           float* var, float* out, unsigned hw, unsigned pixels) {
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(RB), 0, st, src->ptr, src->cstride, src->coff, fields, levels, used, fm,
+                       pw, softplus, records, draws, mean, var, out, hw, pixels);
+  };
+  if (kmax == 4) go(paint_store_moments_kernel<4, V>);
+  else if (kmax == 16) go(paint_store_moments_kernel<16, V>);
+  else go(paint_store_moments_kernel<0, V>);
+}
+
 }  // namespace
 
 extern "C" {
@@ -339,6 +473,35 @@ int bp_paint_store_fields(const int32_t* modes, int32_t fields, int32_t levels, 
   hipLaunchKernelGGL(paint_store_fields_kernel, dim3(nblocks(pixels)), dim3(RB), 0, bp_stream(stream), src->ptr,
                      src->cstride, src->coff, (int)fields, (int)levels, used, fm, bp_pw(pw), softplus ? 1 : 0, records,
                      dst_nchw, (unsigned)hw, (unsigned)pixels);
+  BP_CHECK_LAUNCH();
+  return BP_OK;
+}
+
+int bp_paint_store_moments(const int32_t* modes, int32_t fields, int32_t levels, int32_t include_original,
+                           const bp_view* src, const bp_pointwise* pw, int32_t softplus, const double* records,
+                           int32_t draws, float* mean_nchw, float* var_nchw, float* draws_nchw, void* stream) {
+  if (!modes || !bp_view_ok_any(src) || !records || !mean_nchw || !var_nchw) return BP_EINVAL;
+  if (fields < 1 || levels < 1 || draws < 1 || (int64_t)fields * levels != src->c || src->n % draws != 0) return BP_EINVAL;
+  for (int f = 0; f < fields; ++f)
+    if (modes[f] < 0 || modes[f] >= RC_MODES) return BP_EINVAL;
+  if (src->dtype != BP_F32 || draws > DRAWS_MAX || levels > LEVELS_MAX || fields > FIELDS_MAX) return BP_EUNSUPPORTED;
+  const int64_t hw = (int64_t)src->h * src->w, pixels = (int64_t)(src->n / draws) * hw;
+  if (pixels * draws * src->c >= (int64_t)1 << 31) return BP_EUNSUPPORTED;
+  FieldModes fm{};
+  for (int f = 0; f < fields; ++f) fm.w[f >> 3] |= (unsigned)modes[f] << ((f & 7) * 4);
+  const int used = include_original && levels > 1 ? 1 : levels;       // (one level: the channel itself either way)
+  const int kmax = draws <= 4 ? 4 : draws <= 16 ? 16 : 0;             // draws kept in registers, or two passes
+  auto aligned = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
+  // 16-byte accesses: a one-channel head with cstride 1 (NHWC and NCHW are the same bytes) whose planes are multiples
+  // of four pixels
+  const bool v4 = src->c == 1 && src->cstride == 1 && hw % 4 == 0 && aligned(src->ptr) && aligned(mean_nchw) &&
+                  aligned(var_nchw) && aligned(draws_nchw);
+  if (v4)
+    launch_moments<4>(kmax, nblocks(pixels / 4), bp_stream(stream), src, fields, levels, used, fm, bp_pw(pw),
+                      softplus ? 1 : 0, records, draws, mean_nchw, var_nchw, draws_nchw, (unsigned)hw, (unsigned)pixels);
+  else
+    launch_moments<1>(kmax, nblocks(pixels), bp_stream(stream), src, fields, levels, used, fm, bp_pw(pw),
+                      softplus ? 1 : 0, records, draws, mean_nchw, var_nchw, draws_nchw, (unsigned)hw, (unsigned)pixels);
   BP_CHECK_LAUNCH();
   return BP_OK;
 }

@@ -928,14 +928,17 @@ class CVAE(torch.nn.Module):
         self._plans[(n, want_g, want_q)] = plan
         return plan
 
-    def _paint_plan(self, n):
+    def _paint_plan(self, n, samples=1):
         """The plan ``sample_P`` runs: one latent draw per input whatever ``L`` is (cvae.py:155 passes L=1 to P), no
-        recognition network, no gradients.  With L = 1 that is the cached plan every caller shares."""
-        if self.L == 1:
+        recognition network, no gradients.  With L = 1 that is the cached plan every caller shares.  ``samples`` = K > 1
+        (an ensemble: ``sample_P(samples=K)``, ``paint_graph(draws=K)``): the plan with K draws per input, cached per
+        (n, K)."""
+        if samples == self.L == 1:
             return self._plan(n, False, False)
-        plan = self._paint_plans.get(n)
+        key = n if samples == 1 else (n, int(samples))
+        plan = self._paint_plans.get(key)
         if plan is None:
-            plan = self._paint_plans[n] = _Plan(self, n, False, False, samples=1)
+            plan = self._paint_plans[key] = _Plan(self, n, False, False, samples=int(samples))
         return plan
 
     def cuda(self, device=None):
@@ -1002,8 +1005,14 @@ class CVAE(torch.nn.Module):
             raise ValueError(f"{what}: this model has no variance head (p_y_z_out has one entry): its likelihood has "
                              "unit variance in network units, which is never the scatter that is wanted")
 
-    def sample_P(self, y, return_var=False, aux_label=None, z=None, pixel_noise=None):
+    def sample_P(self, y, return_var=False, aux_label=None, z=None, pixel_noise=None, samples=None):
         """cvae.py:149-162 (always under no_grad).
+
+        ``samples`` = K (1 ... 64): an ENSEMBLE of K latent draws per input, (n, K, cx, H, W) in network units -- the
+        plan of ``paint_graph(draws=K)`` without the transforms: prior and p_y_in once over n, the generator over n K
+        samples.  The draws come from ``_draw_eps`` ((K, n, *dim_z), l-major); ``z`` and ``return_var`` have no meaning
+        here (ValueError).  With ``pixel_noise``, draw l of a sample whose id is i < 2^40 uses the lattice i + (l << 40)
+        at the origin (0, 0) (``origins`` must be None).
 
         ``pixel_noise`` = {"seed": int, "ids": (n,) int64, "origins": (n, 2) int32 {row, col} or None} (a model with a
         variance head; ValueError otherwise, before any plan is built): a DRAW from the likelihood, x_mu + sqrt(x_var) e,
@@ -1014,14 +1023,21 @@ class CVAE(torch.nn.Module):
             self._check_inputs(None, y)
             n = y.shape[0]
             noise = None
+            K = None if samples is None else PG.check_draws(samples)
+            if K is not None and (z is not None or return_var):
+                raise ValueError("sample_P(samples=K) draws its latents from the prior and returns the draws alone")
             if pixel_noise is not None:
                 self._need_var_head("sample_P(pixel_noise=...)")
                 ids, org = PG.noise_lattice(pixel_noise["ids"], pixel_noise.get("origins"), n, *self.dim_x[1:])
+                if K is not None:
+                    if org is not None:
+                        raise ValueError("the draws of an ensemble sit at the origin (0, 0) of their lattices")
+                    ids = PG.ensemble_noise_ids(ids, K).reshape(-1)
                 noise = (torch.from_numpy(PG.seed_word(pixel_noise["seed"]).reshape(1)).to(self.device),
                          torch.from_numpy(ids).to(self.device),
                          None if org is None else torch.from_numpy(org).to(self.device))
             aux = self._aux(aux_label, n)
-            plan = self._paint_plan(n)
+            plan = self._paint_plan(n, 1 if K is None else K)
             plan.load_inputs(y, aux, training=self.training)
             if z is None:
                 plan.run_prior(self.training)
@@ -1037,12 +1053,14 @@ class CVAE(torch.nn.Module):
             plan.run_generator(self.training)
             lib, st = self._lib, _stream()
             cx, H, W = self.dim_x
-            mu = torch.empty((n, cx, H, W), device=self.device)
+            mu = torch.empty((n * plan.L, cx, H, W), device=self.device)
             if noise is not None:
                 plan.run_draw(*noise)
                 self._head_to_nchw(plan.draw, False, mu)
             else:
                 self._head_to_nchw(plan.mu_head, plan.mu_softplus, mu)
+            if K is not None:                    # (sample l * n + m is draw l of input m)
+                return mu.view(K, n, cx, H, W).transpose(0, 1).contiguous()
             if self.predict_var and return_var:
                 lv = torch.empty((n, cx, H, W), device=self.device)
                 self._head_to_nchw(plan.var_head, False, lv)
@@ -1083,7 +1101,7 @@ class CVAE(torch.nn.Module):
         g["graph"].replay()
         return g["out"].clone()
 
-    def paint_graph(self, n, scales=None, modes=None, pixel_noise=False):
+    def paint_graph(self, n, scales=None, modes=None, pixel_noise=False, draws=None, return_draws=False):
         """The captured paint pipeline for batches of ``n`` RAW tiles (configs[4]).  Returns a dict with ``slots``: TWO
         input / parameter / output buffer sets, each with its own captured graph over the SAME launch plans, so that a
         caller uploads batch b+1 straight into one slot and downloads batch b-1 straight out of it while the other
@@ -1120,16 +1138,31 @@ class CVAE(torch.nn.Module):
         the key ``seed``; the caller keeps origins >= 0, columns < 2^24 and rows < 2^31: ``paint_graph.noise_lattice``),
         and a replay runs ``bp_likelihood_draw`` between the generator and the store, which then reads the draw in
         place of the mean head (every head channel of a split-scale painter gets its own draw before the store sums
-        them).  Without it nothing changes."""
+        them).  Without it nothing changes.
+
+        ``draws`` = K (1 ... 64; a model of any ``L``): an ENSEMBLE pipeline, a graph of its own for batches of ``n`` tiles
+        with K latent draws each.  A replay runs the load, the y net if there is one, the repeat of h_y over K, the prior
+        over n, ``bp_philox_normal_dev`` with L = K (draw k of tile id t: counter (g, k, t)), the latent, the generator
+        over n K samples, the likelihood draw with ``pixel_noise``, and ``bp_paint_store_moments``.  A slot has ``mean``
+        and ``var`` (n, F, H, W) in place of ``out``, and ``draws`` (n, K, F, H, W) with ``return_draws``.  Its block
+        always holds the four-double records: ``xf_in`` (n, 4), ``xf_out`` (n, 4 F), and ``modes`` = None stands for
+        shift-log on both sides; with ``pixel_noise`` it ends in ``noise_ids`` (parts, K, n / parts) int64
+        (``paint_graph.paint_fields``; ``parts``: the graph's sub-batches of tiles, BP_PAINT_STREAMS), which the caller
+        fills from ``paint_graph.ensemble_noise_ids``: draw k of a tile whose id is i < 2^40 is on lattice i + (k << 40)
+        at the origin (0, 0).  Without ``draws`` nothing changes."""
         if self.training:
             raise RuntimeError("paint_graph is an eval-mode (paint) path: call model.train(False) first")
         if pixel_noise:
             self._need_var_head("paint_graph(pixel_noise=True)")
-        key = (n, "pipeline")
+        if draws is not None:
+            draws = PG.check_draws(draws)
+            if modes is None:
+                modes = (L.RC_SHIFT_LOG, L.RC_SHIFT_LOG)
+        key = (n, "pipeline") if draws is None else (n, "ensemble", draws)
         if scales is not None:
             scales = {"n_scale": int(scales["n_scale"]), "step_size": scales["step_size"],
                       "include_original": bool(scales["include_original"]), "truncate": scales.get("truncate", 3.0)}
-            key = (n, "pipeline", "scales") + tuple(scales.values())
+            key = key + ("scales",) + tuple(scales.values())
         if modes is not None and isinstance(modes[1], (tuple, list)):
             modes = (int(modes[0]), tuple(int(m) for m in modes[1]))
             key = key + ("modes", modes[0], "fields") + modes[1]
@@ -1138,7 +1171,12 @@ class CVAE(torch.nn.Module):
             key = key + ("modes",) + modes
         if pixel_noise:
             key = key + ("noise",)
+        if draws is not None and return_draws:
+            key = key + ("draws",)
         g = self._graphs.get(key)
+        if g is None and draws is not None:
+            g = self._graphs[key] = self._capture_ensemble_graph(n, draws, scales, modes, bool(pixel_noise),
+                                                                 bool(return_draws))
         if g is None:
             g = self._capture_paint_graph(n, pipeline=True, scales=scales, modes=modes, pixel_noise=bool(pixel_noise))
             self._graphs[key] = g
@@ -1150,8 +1188,25 @@ class CVAE(torch.nn.Module):
     def release_scale_buffers(self):
         """Drop the captured multi-scale paint pipelines (``paint_graph(n, scales=...)``) with their scratch and filter
         weights; they are captured again on next use."""
-        for key in [k for k in self._graphs if isinstance(k, tuple) and len(k) > 2 and k[2] == "scales"]:
+        for key in [k for k in self._graphs if isinstance(k, tuple) and "scales" in k[2:4]]:
             del self._graphs[key]
+
+    def _scales_context(self, scales, h, parts):
+        """What the split-scale load step of a captured pipeline needs besides its views: the pyramid's filter weights
+        and radii, and one scratch per stream of the graph (``parts`` sub-batches of ``h`` tiles)."""
+        import numpy as np
+        from ..utils import data_transforms as T
+        dev, (H, W) = self.device, self.dim_y[1:]
+        sig = T.split_scale_sigmas(scales["n_scale"], scales["step_size"])
+        radii = [0] + [T.gaussian_radius(s, scales["truncate"]) for s in sig[1:]]
+        wts = np.concatenate([np.zeros(0)] + [T.gaussian_weights(s, scales["truncate"]) for s in sig[1:]])
+        ws = int(self._lib.bp_split_scale_workspace(h, H, W))
+        return {"n_scale": scales["n_scale"], "include_original": int(scales["include_original"]),
+                "radii": (C.c_int32 * len(radii))(*radii), "ws": ws,
+                "weights": torch.from_numpy(np.ascontiguousarray(wts, np.float64)).to(dev)
+                if len(wts) else torch.zeros(1, dtype=torch.float64, device=dev),
+                # one scratch per stream of the graph; the two slots replay on one stream and share them
+                "scratch": [torch.empty(max(ws // 4, 1), device=dev) for _ in range(parts)]}
 
     def _capture_paint_graph(self, n, given_z=False, pipeline=False, scales=None, modes=None, pixel_noise=False):
         """Eval-mode layers do not couple the tiles of a batch (batch-norm runs on its running statistics), so the
@@ -1207,19 +1262,7 @@ class CVAE(torch.nn.Module):
                                            for u in us])
         others = [torch.cuda.Stream(device=dev) for _ in range(parts - 1)]
         if scales is not None:
-            import numpy as np
-            from ..utils import data_transforms as T
-            sig = T.split_scale_sigmas(scales["n_scale"], scales["step_size"])
-            radii = [0] + [T.gaussian_radius(s, scales["truncate"]) for s in sig[1:]]
-            wts = np.concatenate([np.zeros(0)] + [T.gaussian_weights(s, scales["truncate"]) for s in sig[1:]])
-            ws = int(self._lib.bp_split_scale_workspace(h, H, W))
-            sc = {"n_scale": scales["n_scale"], "include_original": int(scales["include_original"]),
-                  "radii": (C.c_int32 * len(radii))(*radii), "ws": ws,
-                  "weights": torch.from_numpy(np.ascontiguousarray(wts, np.float64)).to(dev)
-                  if len(wts) else torch.zeros(1, dtype=torch.float64, device=dev),
-                  # one scratch per stream of the graph; the two slots replay on one stream and share them
-                  "scratch": [torch.empty(max(ws // 4, 1), device=dev) for _ in range(parts)]}
-            st["scales"] = sc
+            sc = st["scales"] = self._scales_context(scales, h, parts)
             for sl in st["slots"]:
                 sl["scratch"], sl["weights"] = sc["scratch"], sc["weights"]
 
@@ -1320,6 +1363,108 @@ class CVAE(torch.nn.Module):
                 main.wait_stream(s2)
 
         st["graph"] = PG.capture(run, st.get("slots", [None]), dev)[0]
+        return st
+
+    def _capture_ensemble_graph(self, n, draws, scales, modes, pixel_noise, return_draws):
+        """``paint_graph(n, draws=K)``: ``_capture_paint_graph``'s pipeline over plans with K latent draws per tile.  The
+        BP_PAINT_STREAMS sub-batches split the n TILES (a sub-batch of h tiles is h K generator samples); everything in
+        front of the latent runs once per tile, and the store reduces over the draws."""
+        cy, H, W = self.dim_y
+        cx, dev, lib, K = self.dim_x[0], self.device, self._lib, draws
+        m_in, m_out = int(modes[0]), modes[1] if isinstance(modes[1], tuple) else (int(modes[1]),)
+        fields = len(m_out)
+        levels = 1 if scales is None else scales["n_scale"] + int(scales["include_original"])
+        if (cy != levels and scales is not None) or cx != fields * levels:
+            raise ValueError(f"{fields} label field(s) of {levels} channel(s) need dim_x[0] = {fields * levels}"
+                             + (f" and dim_y[0] = {levels}" if scales is not None else "")
+                             + f", the model has dim_y[0] = {cy} and dim_x[0] = {cx}")
+        if scales is not None and self.has_p_y_in:
+            raise NotImplementedError("the captured paint pipeline has no split-scale load step for a p_y_in network "
+                                      "(bp_paint_load_scales2 writes two destinations); paint / paint_batch take it")
+        parts = int(os.environ.get("BP_PAINT_STREAMS", "4"))
+        while parts > 1 and (n % parts != 0 or n // parts * K < 8):
+            parts -= 1
+        h = n // parts
+        per_tile = math.prod(self.dim_z)
+        block = PG.ParamBlock(PG.paint_fields(n, 4, max(self.n_aux, 1), xf_out_width=4 * fields, noise=pixel_noise,
+                                              draws=K, parts=parts))
+        outs = {"mean": (n, fields, H, W), "var": (n, fields, H, W)}
+        if return_draws:
+            outs["draws"] = (n, K, fields, H, W)
+        st = {"draws": K, "parts": parts, "eps": torch.zeros((parts, K, h, per_tile), device=dev),
+              "param_block": block, "block_layout": block.layout, "block_bytes": block.nbytes,
+              "slots": [PG.new_slot((n, 1 if scales is not None else cy, H, W), outs, block, dev) for _ in range(2)]}
+        plans = st["plans"] = [self._paint_plan(h, K)] + [_Plan(self, h, False, False, samples=K)
+                                                           for _ in range(parts - 1)]
+        st["units"] = PlanBase.flat_units([u for plan in plans
+                                           for us in [plan.p_units] + plan.g_units + [plan.mu_units, plan.y_units]
+                                           + ([plan.var_units] if pixel_noise else [])
+                                           for u in us])
+        others = [torch.cuda.Stream(device=dev) for _ in range(parts - 1)]
+        y_net = bool(plans[0].y_units)
+        if pixel_noise:
+            for plan in plans:
+                plan.draw_slot()
+        field_modes = (C.c_int32 * fields)(*m_out)
+        inc = int(scales["include_original"]) if scales is not None else 0
+        if scales is not None:
+            sc = st["scales"] = self._scales_context(scales, h, parts)
+            for sl in st["slots"]:
+                sl["scratch"], sl["weights"] = sc["scratch"], sc["weights"]
+
+        def block0(plan):
+            """Sample block 0 of the generator's h_y slice (draw 0 of the h tiles), and the K - 1 blocks behind it."""
+            s = plan.hy_slot
+            rest = L.View(plan.p_in.buf[h:].data_ptr(), h * (K - 1), s.h, s.w, s.c, s.cstride, s.coff) if K > 1 else None
+            return L.View(plan.p_in.buf.data_ptr(), h, s.h, s.w, s.c, s.cstride, s.coff), rest
+
+        def paint(plan, k, sl):
+            sm, lo = _stream(), k * h
+            plan.pack_all()
+            raw, xf = L.ptr(sl["raw"][lo:lo + h]), L.ptr(sl["xf_in"][lo:lo + h])
+            auxp = L.ptr(sl["aux"][lo:lo + h]) if self.use_aux_label else None
+            first, rest = block0(plan)
+            if scales is not None:
+                rc = lib.bp_paint_load_scales2_mode(m_in, raw, xf, auxp, plan.caux, sc["n_scale"], sc["include_original"],
+                                                    L.ptr(sc["weights"]), sc["radii"], L.ptr(sc["scratch"][k]), sc["ws"],
+                                                    C.byref(plan.y2.view), C.byref(first), sm)
+            elif y_net:
+                rc = lib.bp_paint_load_mode(m_in, raw, cy, xf, auxp, plan.caux, C.byref(plan.y2.view), sm)
+            else:
+                rc = lib.bp_paint_load2_mode(m_in, raw, cy, xf, auxp, plan.caux, C.byref(plan.y2.view), C.byref(first), sm)
+            L.check(rc, "ensemble load")
+            if y_net:
+                plan.run_y_net(False)                    # (repeats h_y over K itself)
+            elif K > 1:
+                L.check(lib.bp_repeat_samples(C.byref(first), K - 1, C.byref(rest), sm), "repeat y over the draws")
+            plan.run_prior(False)
+            eps = st["eps"][k]
+            L.check(lib.bp_philox_normal_dev(L.ptr(sl["seed"]), L.ptr(sl["tile_ids"][lo:lo + h]), h, K, per_tile,
+                                             L.ptr(eps), sm), "philox")
+            plan.run_latent(eps.view(K, h, *self.dim_z), use_q=False)
+            plan.run_generator(False)
+            if pixel_noise:
+                plan.run_draw(sl["seed"], sl["noise_ids"][k], None)
+                src, sp = C.byref(plan.draw.view), 0
+            else:
+                src, sp = C.byref(plan.mu_head.view), 1 if plan.mu_softplus else 0
+            L.check(lib.bp_paint_store_moments(field_modes, fields, levels, inc, src, None, sp,
+                                               L.ptr(sl["xf_out"][lo:lo + h]), K, L.ptr(sl["mean"][lo:lo + h]),
+                                               L.ptr(sl["var"][lo:lo + h]),
+                                               L.ptr(sl["draws"][lo:lo + h]) if return_draws else None, sm),
+                    "ensemble store")
+
+        def run(sl):
+            main = torch.cuda.current_stream(dev)
+            for k, s2 in enumerate(others):
+                s2.wait_stream(main)
+                with torch.cuda.stream(s2):
+                    paint(plans[k + 1], k + 1, sl)
+            paint(plans[0], 0, sl)
+            for s2 in others:
+                main.wait_stream(s2)
+
+        st["graph"] = PG.capture(run, st["slots"], dev)[0]
         return st
 
     # ---- the whole training step as one hipGraph (small minibatches are launch-bound: ~450 launches per step)

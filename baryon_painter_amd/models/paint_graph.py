@@ -36,19 +36,51 @@ class ParamBlock:
         return out
 
 
-def paint_fields(n, xf_width, aux_width=1, xf_out_width=None, noise=False):
+def paint_fields(n, xf_width, aux_width=1, xf_out_width=None, noise=False, draws=None, parts=1):
     """The fields of a paint pipeline's block for batches of ``n`` tiles: ``xf_in`` / ``xf_out`` (n, xf_width) float64
     parameter rows of the transform and its inverse, ``tile_ids`` (n,) int64, ``seed`` (1,) int64 Philox key, ``aux``
     (n, aux_width) float32 value of the conditioning plane.  Both models carry all five, so that one caller fills either
     model's block.  ``xf_out_width``: the width of ``xf_out`` where it differs (a CVAE with several label fields: the
     fields' rows side by side).  ``noise`` (a pipeline that paints draws from the likelihood, ``bp_likelihood_draw``):
-    ``noise_ids`` (n,) int64 and ``noise_org`` (n, 2) int32 {row, col} follow behind the five."""
+    ``noise_ids`` (n,) int64 and ``noise_org`` (n, 2) int32 {row, col} follow behind the five.  ``draws`` = K (an
+    ensemble pipeline, ``CVAE.paint_graph(draws=K)``, whose graph paints its n tiles as ``parts`` sub-batches): the five
+    fields are per TILE as ever; with ``noise``, ``noise_ids`` is (parts, K, n / parts) int64 -- per sub-batch the K n /
+    parts ids of its samples in the order ``bp_likelihood_draw`` reads them, draw-major -- and there is no ``noise_org``
+    (the draws of an ensemble sit at the origin of their lattices).  Without ``draws`` nothing changes."""
     fields = [("xf_in", torch.float64, (n, xf_width)),
               ("xf_out", torch.float64, (n, xf_width if xf_out_width is None else xf_out_width)),
               ("tile_ids", torch.int64, (n,)), ("seed", torch.int64, (1,)), ("aux", torch.float32, (n, aux_width))]
-    if noise:
+    if noise and draws is not None:
+        fields += [("noise_ids", torch.int64, (parts, draws, n // parts))]
+    elif noise:
         fields += [("noise_ids", torch.int64, (n,)), ("noise_org", torch.int32, (n, 2))]
     return fields
+
+
+DRAWS_MAX = 64          # bp_paint_store_moments' limit
+DRAW_SHIFT = 40         # draw l of an ensemble draws its pixel noise from the lattice id + (l << DRAW_SHIFT)
+
+
+def check_draws(draws):
+    """``draws`` of an ensemble as an int in 1 ... DRAWS_MAX (ValueError).  Needs no GPU."""
+    k = int(draws)
+    if k != draws or not 1 <= k <= DRAWS_MAX:
+        raise ValueError(f"an ensemble has 1 ... {DRAWS_MAX} draws per tile, got {draws}")
+    return k
+
+
+def ensemble_noise_ids(ids, draws):
+    """(draws, n) int64 lattice ids of an ensemble's pixel noise: row l = ``ids`` + (l << 40), so that draw l of a tile
+    is what a single painting with that lattice id draws.  ``ids`` (n,) must lie in [0, 2^40) (ValueError).  Needs no
+    GPU."""
+    import numpy as np
+    ids = np.asarray(ids)
+    if ids.ndim != 1 or ids.dtype.kind not in "iu":
+        raise ValueError(f"noise ids must be a vector of integers, got shape {ids.shape} of {ids.dtype}")
+    if len(ids) and (int(ids.min()) < 0 or int(ids.max()) >= 1 << DRAW_SHIFT):
+        raise ValueError(f"the noise ids of an ensemble must lie in [0, 2^{DRAW_SHIFT}): bits {DRAW_SHIFT} and above "
+                         "number the draws")
+    return ids.astype(np.int64)[None, :] + (np.arange(draws, dtype=np.int64) << DRAW_SHIFT)[:, None]
 
 
 def seed_word(seed):
@@ -85,9 +117,11 @@ def noise_lattice(ids, origins, n, h, w):
 
 def new_slot(raw_shape, out_shape, block, device):
     """One slot: ``raw``, ``out``, the uint8 ``block`` and its named views, ``xf_in`` / ``xf_out`` filled with 1.0 (a
-    valid transform for the warm-up)."""
-    sl = {"raw": torch.zeros(raw_shape, device=device), "out": torch.zeros(out_shape, device=device),
-          "block": torch.zeros(block.nbytes, device=device, dtype=torch.uint8)}
+    valid transform for the warm-up).  ``out_shape`` may be a dict name -> shape of several outputs in place of ``out``
+    (an ensemble's ``mean`` / ``var`` / ``draws``)."""
+    outs = out_shape if isinstance(out_shape, dict) else {"out": out_shape}
+    sl = {"raw": torch.zeros(raw_shape, device=device), "block": torch.zeros(block.nbytes, device=device, dtype=torch.uint8)}
+    sl.update({name: torch.zeros(shape, device=device) for name, shape in outs.items()})
     sl.update(block.views(sl["block"]))
     sl["xf_in"].fill_(1.0)
     sl["xf_out"].fill_(1.0)

@@ -467,7 +467,7 @@ class CVAEPainter(Painter):
         return np.concatenate(out, axis=0)
 
     # ---- throughput pipeline (BASELINE.json configs[4]) ---------------------------------------------------------
-    def _transform_parameters(self, zs):
+    def _transform_parameters(self, zs, records=False):
         """(params, scales, modes) for the device-side transforms, read out of the compiled host transforms: per tile
         the parameter rows ``xf_in`` / ``xf_out`` of the reference's range compression (data_transforms.py:72-108) for
         ``CVAE.paint_graph``'s block, the description of a multi-scale painter's split-scale transform (``paint_graph``'s
@@ -476,7 +476,8 @@ class CVAEPainter(Painter):
         csrc/range_compress.hpp).  With F > 1 label fields ``xf_out`` is (n, F, 4), the records of each field, and
         ``modes`` is (input mode, (mode of field 0, ...)): the four-double form on both sides whatever the modes are;
         every field's inverse chain must have a device form, and all of them share the split-scale parameters.
-        Anything else has no device form.  The chains with one:
+        ``records=True`` (an ensemble, ``paint_ensemble``): the four-double records and both mode numbers also where both
+        fields are "shift-log".  Anything else has no device form.  The chains with one:
           single scale   any order of ONE range compression and the shape-only steps;
           multi scale    forward  [range compression, as_float32 (optional), split-scale, shape-only steps ...]
                          inverse  [inverse split-scale, inverse range compression, shape-only steps ...]
@@ -526,7 +527,7 @@ class CVAEPainter(Painter):
         rc_out, st_out = outs[0]
         xf_in, xf_out = rc_in.records(st_in, zs), rc_out.records(st_out, zs)      # (vectorised: no Python call per tile)
         modes = (rc_in.mode, rc_out.mode)
-        if rc_in.name == rc_out.name == "shift-log":
+        if rc_in.name == rc_out.name == "shift-log" and not records:
             modes, xf_in, xf_out = None, xf_in[:, :2], xf_out[:, 1::-1]
         return {"xf_in": xf_in, "xf_out": xf_out, "aux": np.asarray(zs, dtype=np.float64)}, scales, modes
 
@@ -536,16 +537,17 @@ class CVAEPainter(Painter):
     def _shape_mismatch(self, shape):
         return f"Shape mismatch between input and model: {shape} vs {self.model.dim_y}"
 
-    def _device_paint_parameters(self, zs):
+    def _device_paint_parameters(self, zs, ensemble=False):
         """``_transform_parameters(zs)`` where this painter has a device form -- one of the six range compressions on
         either side (one per label field) and L = 1, with or without a prior network or a p_y_in network; single-channel
         tiles, or a split-scale transform in the orders ``_transform_parameters`` names whose levels are the model's
         dim_y[0] = dim_x[0], without a p_y_in network; with F > 1 label fields dim_x[0] = F * dim_y[0] -- and
-        NotImplementedError where it has none.  No side effects."""
+        NotImplementedError where it has none.  No side effects.  ``ensemble`` (``paint_ensemble``: the number of draws
+        is its argument, not the model's): any L, and ``_transform_parameters(zs, records=True)``."""
         model = self.model
-        if getattr(model, "L", 1) != 1:
+        if getattr(model, "L", 1) != 1 and not ensemble:
             raise NotImplementedError("the captured paint pipeline needs L = 1 (paint / paint_batch take any L)")
-        params, scales, modes = self._transform_parameters(zs)
+        params, scales, modes = self._transform_parameters(zs, records=ensemble)
         cy, cx = model.dim_y[0], model.dim_x[0]
         F = len(self.label_fields)
         if F > 1:
@@ -569,6 +571,55 @@ class CVAEPainter(Painter):
                 raise NotImplementedError(f"the device paint path needs dim_y[0] = dim_x[0] = {levels} for this "
                                           f"split-scale transform, the model has {cy} and {cx}")
         return params, scales, modes
+
+    def paint_ensemble(self, inputs, z, draws, batch_size=64, tile_ids=None, seed=0, rank=0, world_size=1,
+                       return_draws=False, pixel_noise=False, noise_ids=None):
+        """The conditional mean and scatter of the painted field at fixed dark matter: ``draws`` = K (1 ... 64) latent
+        draws per raw tile of ``inputs`` (N, H, W), reduced on the device -> (mean, var), float32 (N, H, W) each, or
+        (N, F, H, W) for F > 1 label fields; ``var`` is the population variance over the K draws (``np.var``, ddof = 0),
+        both accumulated in float64 over the float32 physical tiles a single painting stores
+        (``bp_paint_store_moments``).  ``return_draws=True`` adds the draws themselves, (N, K, [F,] H, W).
+
+        It is ``paint_stream``'s pipeline -- pinned double buffers, two slots, one parameter-block copy per batch, the
+        seed read from the device -- over ``model.paint_graph(batch_size // K, draws=K)``: ``batch_size`` counts
+        generator samples as everywhere else, so a batch carries ``batch_size // K`` tiles (K must divide it), and the
+        load, the pyramid, p_y_in and the prior network run once per TILE.  Draw k of tile id t uses the Philox counter
+        (g, k, t): draw 0 is the tile ``paint_stream`` paints for the same seed and id, and no draw depends on batches
+        or ranks.  The model may have any ``L``.  ``rank`` / ``world_size`` shard tiles as in ``paint_stream`` (the
+        result is then (arrays, (lo, hi))).  ``pixel_noise=True`` (a variance head; ValueError otherwise): every draw is
+        also a draw from the likelihood, draw k of a tile on the lattice ``noise_ids[i]`` [default: ``tile_ids[i]``] +
+        (k << 40) at the origin (0, 0); the ids must lie in [0, 2^40) (ValueError before any capture).
+
+        Planes and light cones have no ensemble form: the moments of a feathered blend of overlapping tiles are not
+        the blend of the tiles' moments."""
+        from .models import paint_graph as PG
+        K = PG.check_draws(draws)
+        B = int(batch_size)
+        if B < K or B % K:
+            raise ValueError(f"batch_size counts generator samples: {K} draws per tile must divide it, got {batch_size}")
+        N = len(inputs)
+        ids = np.arange(N, dtype=np.int64) if tile_ids is None else np.asarray(tile_ids, dtype=np.int64)
+        lattice = None
+        if pixel_noise:
+            self._need_pixel_noise()
+            lattice = np.asarray(ids if noise_ids is None else noise_ids)
+            if lattice.shape != (N,):
+                raise ValueError(f"noise ids must be {N} integers, got shape {lattice.shape}")
+            PG.ensemble_noise_ids(lattice, 1)             # (the range check, before any capture)
+        model = self.model
+        model.train(False)
+        H, W = self._tile_shape()
+        if tuple(inputs.shape[1:]) != (H, W):
+            raise ValueError(self._shape_mismatch(tuple(inputs.shape)))
+        zs = np.broadcast_to(np.asarray(z, dtype=np.float64), (N,))
+        per = (N + world_size - 1) // world_size
+        lo, hi = min(rank * per, N), min((rank + 1) * per, N)
+        params, scales, modes = self._device_paint_parameters(zs[lo:hi], ensemble=True)
+        if pixel_noise:
+            params = dict(params, noise_ids=lattice[lo:hi].astype(np.int64))
+        result = _paint_stream_pipeline(self, model, inputs, (H, W), lo, hi, B // K, params, ids[lo:hi], seed, None, scales,
+                                        modes, ensemble={"draws": K, "return_draws": bool(return_draws)})
+        return (result, (lo, hi)) if world_size > 1 else result
 
     def can_paint_stream(self, z=0.0):
         """Whether ``paint_stream`` has a device form for this painter (``_device_paint_parameters``) -- WITHOUT side
@@ -634,7 +685,15 @@ def _fill_block(hv, params, ids, a, b, B):
     hv["aux"][:m, 0] = params["aux"][a:b]
     hv["tile_ids"][:m] = ids[a:b]
     keys = ("xf_in", "xf_out", "aux", "tile_ids")
-    if "noise_ids" in params:                     # (a pipeline that paints with pixel noise: _with_noise)
+    if "noise_ids" in params and hv["noise_ids"].ndim == 3:
+        # an ensemble pipeline: (parts, K, B / parts), per sub-batch of tiles the ids of its draws, draw-major
+        from .models import paint_graph as PG
+        parts, K, h = hv["noise_ids"].shape
+        tile = np.empty(B, np.int64)
+        tile[:m] = params["noise_ids"][a:b]
+        tile[m:] = tile[m - 1]
+        hv["noise_ids"][...] = PG.ensemble_noise_ids(tile, K).reshape(K, parts, h).transpose(1, 0, 2)
+    elif "noise_ids" in params:                   # (a pipeline that paints with pixel noise: _with_noise)
         hv["noise_ids"][:m] = params["noise_ids"][a:b]
         hv["noise_org"][:m] = params["noise_org"][a:b]
         keys += ("noise_ids", "noise_org")
@@ -653,10 +712,10 @@ def _with_noise(params, noise_ids, noise_origins, N, H, W, lo, hi):
     return dict(params, noise_ids=ids[lo:hi], noise_org=org[lo:hi])
 
 
-def _paint_graph(model, B, scales, modes, pixel_noise=False):
+def _paint_graph(model, B, scales, modes, pixel_noise=False, ensemble=None):
     """``model.paint_graph(B)`` with the keywords only a CVAE's takes, where they say something."""
     kw = {k: v for k, v in (("scales", scales), ("modes", modes), ("pixel_noise", pixel_noise or None)) if v is not None}
-    return model.paint_graph(B, **kw)
+    return model.paint_graph(B, **kw, **(ensemble or {}))
 
 
 def _n_fields(modes):
@@ -669,24 +728,37 @@ def _seed_word(seed):
 
 
 def _paint_stream_pipeline(painter, model, inputs, tile_shape, lo, hi, B, params, ids, seed, out, scales=None,
-                           modes=None):
+                           modes=None, ensemble=None):
     """Tiles [lo, hi) of ``inputs`` through ``model.paint_graph(B)``: pinned double-buffered upload / replay / download
     (``CVAEPainter.paint_stream``).  ``params`` and ``ids`` hold those tiles only.  Returns the (hi - lo, H, W) float32
     result (``out`` if given).  ``scales``: a multi-scale CVAE painter's split-scale description (``CVAE.paint_graph``);
     raw tiles and painted tiles are single-channel either way.  ``modes``: a CVAE painter's (input, label)
     range-compression modes where they are not both shift-log (``CVAE.paint_graph``), or (input mode, (mode of field 0,
     ...)) of a painter with F > 1 label fields: the result, the slots' ``out`` and the pinned output buffers are then
-    (.., F, H, W), and ``out``, where given, must have the result's shape."""
+    (.., F, H, W), and ``out``, where given, must have the result's shape.  ``ensemble`` = {"draws": K,
+    "return_draws": bool} (``CVAEPainter.paint_ensemble``; ``out`` is None): ``B`` TILES per batch through
+    ``model.paint_graph(B, draws=K)``, whose slots have ``mean`` and ``var`` (and ``draws``) in place of ``out``; the
+    result is the tuple of these, (hi - lo, [F,] H, W) and (hi - lo, K, [F,] H, W) NumPy arrays."""
     H, W = tile_shape
     dev = model.device
     F = _n_fields(modes)
-    shape = (hi - lo, F, H, W) if F > 1 else (hi - lo, H, W)
+    field = (F,) if F > 1 else ()
+    shape = (hi - lo, *field, H, W)
     if F > 1 and out is not None and tuple(out.shape) != shape:
         raise ValueError(f"out must have the shape {shape} of {F} label fields, got {tuple(out.shape)}")
-    g = _paint_graph(model, B, scales, modes, "noise_ids" in params)
+    g = _paint_graph(model, B, scales, modes, "noise_ids" in params, ensemble)
     torch_in = isinstance(inputs, torch.Tensor)
-    result = out if out is not None else np.empty(shape, np.float32)
-    torch_out = isinstance(result, torch.Tensor)
+    # what leaves a slot: name -> (shape of a tile in the slot, the result it lands in)
+    if ensemble is None:
+        result = out if out is not None else np.empty(shape, np.float32)
+        outs = {"out": ((F, H, W), result)}
+    else:
+        K = ensemble["draws"]
+        outs = {"mean": ((F, H, W), np.empty(shape, np.float32)), "var": ((F, H, W), np.empty(shape, np.float32))}
+        if ensemble["return_draws"]:
+            outs["draws"] = ((K, F, H, W), np.empty((hi - lo, K, *field, H, W), np.float32))
+        result = tuple(res for _, res in outs.values())
+    torch_out = isinstance(out, torch.Tensor)
     main = torch.cuda.current_stream(dev)
     up, down = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
     # Two slots = the graph's own two buffer sets (paint_graph): uploads land where the load kernel reads, downloads
@@ -696,6 +768,8 @@ def _paint_stream_pipeline(painter, model, inputs, tile_shape, lo, hi, B, params
     # release_paint_buffers() frees them; the tile buffers are only allocated for NumPy inputs / outputs
     cache = painter.__dict__.setdefault("_paint_host_buffers", {})
     key = (B, H, W, g["block_bytes"], str(dev)) + ((F,) if F > 1 else ())
+    if ensemble is not None:
+        key = ("ensemble", K, "draws" in outs) + key
     if key not in cache:
         cache.clear()
         cache[key] = [{"h_blk": torch.zeros(g["block_bytes"], dtype=torch.uint8).pin_memory(), "h_in": None,
@@ -708,7 +782,8 @@ def _paint_stream_pipeline(painter, model, inputs, tile_shape, lo, hi, B, params
         if not torch_in and hb["h_in"] is None:
             hb["h_in"] = torch.empty((B, 1, H, W), dtype=torch.float32).pin_memory()
         if not torch_out and hb["h_out"] is None:
-            hb["h_out"] = torch.empty((B, F, H, W), dtype=torch.float32).pin_memory()
+            hb["h_out"] = {name: torch.empty((B, *tile), dtype=torch.float32).pin_memory()
+                           for name, (tile, _) in outs.items()}
         slots.append({"g": gs, "h_blk": h_blk, "hv": hv, "h_in": hb["h_in"], "h_out": hb["h_out"],
                       "ev_up": torch.cuda.Event(), "ev_done": torch.cuda.Event(), "ev_down": torch.cuda.Event(),
                       "pending": None})
@@ -719,7 +794,8 @@ def _paint_stream_pipeline(painter, model, inputs, tile_shape, lo, hi, B, params
         a, b = sl["pending"]
         sl["ev_down"].synchronize()
         if not torch_out:
-            result[a - lo:b - lo] = sl["h_out"][:b - a].numpy() if F > 1 else sl["h_out"][:b - a, 0].numpy()
+            for name, (_, res) in outs.items():
+                res[a - lo:b - lo] = sl["h_out"][name][:b - a].numpy().reshape(b - a, *res.shape[1:])
         sl["pending"] = None
 
     starts = list(range(lo, hi, B))
@@ -764,8 +840,9 @@ def _paint_stream_pipeline(painter, model, inputs, tile_shape, lo, hi, B, params
             sl["ev_done"].record(main)
             down.wait_event(sl["ev_done"])
             with torch.cuda.stream(down):
-                dst = result[a - lo:b - lo].reshape(m, F, H, W) if torch_out else sl["h_out"][:m]
-                dst.copy_(gs["out"][:m], non_blocking=True)
+                for name in outs:
+                    dst = result[a - lo:b - lo].reshape(m, F, H, W) if torch_out else sl["h_out"][name][:m]
+                    dst.copy_(gs[name][:m], non_blocking=True)
                 sl["ev_down"].record(down)
             sl["pending"] = (a, b)
         for sl in slots:

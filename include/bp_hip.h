@@ -427,6 +427,26 @@ int bp_paint_store_scales_mode(int32_t mode, const bp_view* src, const bp_pointw
 int bp_paint_store_fields(const int32_t* modes, int32_t fields, int32_t levels, int32_t include_original,
                           const bp_view* src, const bp_pointwise* pw, int32_t softplus, const double* records,
                           float* dst_nchw, void* stream);
+/* The store of an ENSEMBLE (painter.CVAEPainter.paint_ensemble): `src` is a head of draws * n samples, sample l * n + m
+ * = draw l of tile m (the order of a plan with `draws` latent samples per input), src->c == fields * levels.  With p_l
+ * the float32 value bp_paint_store_fields writes for sample l * n + m under tile m's record -- the same device
+ * functions, the same bits -- per tile m, field f and pixel, in float64 without contraction, ascending l:
+ *   S = ((p_0 + p_1) + ...) + p_{K-1},  M = S / K,  Q = ((p_0 - M)^2 + (p_1 - M)^2) + ...,  K = draws
+ *   mean_nchw = (float) M,  var_nchw = (float) (Q / K)      (n, fields, H, W) each: the population variance, np.var's
+ * Non-finite values get no special handling (an infinite draw: mean +-inf, var NaN, as NumPy); draws == 1 gives
+ * var == +0 for a finite p_0.
+ *   modes      : HOST array of `fields` int32 (BP_RC_*), as in bp_paint_store_fields
+ *   records    : device, (n, fields, 4) float64, one row per TILE
+ *   draws_nchw : NULL, or (n, draws, fields, H, W), tile-major: receives every p_l
+ * One launch, one thread per tile pixel (four pixels and 16-byte accesses for a one-channel head with cstride 1, planes
+ * of a multiple of four pixels and 16-byte aligned pointers); up to 16 draws stay in registers between the two sums,
+ * more are read and evaluated a second time.  No atomics, no workspace, no host synchronisation: the same inputs give
+ * the same bits.  Before anything is written: BP_EINVAL for a null pointer other than pw or draws_nchw, a malformed
+ * view, fields < 1, levels < 1, draws < 1, src->c != fields * levels, src->n % draws != 0 or a mode outside 0 ... 5;
+ * then BP_EUNSUPPORTED for a bf16 view, draws > 64, levels > 16, fields > 64 or src->n * H * W * src->c >= 2^31. */
+int bp_paint_store_moments(const int32_t* modes, int32_t fields, int32_t levels, int32_t include_original,
+                           const bp_view* src, const bp_pointwise* pw, int32_t softplus, const double* records,
+                           int32_t draws, float* mean_nchw, float* var_nchw, float* draws_nchw, void* stream);
 /* eps (L, n, per_tile) standard normal for the sampler of cvae.py:64-65 from Philox4x32-10 keyed on `seed`, counter
  * (element group, l, tile id): a tile's noise depends on (seed, its GLOBAL id) only, not on batch, stream or rank
  * (torch.randn on the device in the reference: same distribution, no reproducible stream to match). */
