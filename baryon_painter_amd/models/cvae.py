@@ -1083,8 +1083,7 @@ class CVAE(torch.nn.Module):
         key = n if z is None else (n, "z")
         g = self._graphs.get(key)
         if g is None:
-            g = self._capture_paint_graph(n, given_z=z is not None)
-            self._graphs[key] = g
+            g = self._graphs[key] = self._capture_sample_graph(n, z is not None)
         for u in g["units"]:
             u.maybe_pack()                       # eager, a no-op unless the weights changed
             u.maybe_bn_eval()                    # ... or the running statistics
@@ -1106,7 +1105,8 @@ class CVAE(torch.nn.Module):
         input / parameter / output buffer sets, each with its own captured graph over the SAME launch plans, so that a
         caller uploads batch b+1 straight into one slot and downloads batch b-1 straight out of it while the other
         slot's graph paints batch b -- no device-to-device staging copy.  A slot holds
-          ``raw`` (n, cy, H, W) untransformed input tiles, ``out`` (n, cx, H, W) painted physical tiles,
+          ``raw`` (n, 1, H, W) untransformed input tiles, ``out`` (n, 1, H, W) painted physical tiles (the models it
+          takes: ``paint_graph.paint_levels``),
           ``block`` one uint8 device buffer with the typed views ``xf_in`` / ``xf_out`` (n, 2) float64 {sigma, k} /
           {k, sigma} of the shift-log transform and its inverse, ``tile_ids`` (n,) int64 global tile numbers, ``seed``
           (1,) int64 Philox key (read by the kernel at run time: one graph serves every seed), ``aux`` (n, 1) float32
@@ -1174,12 +1174,8 @@ class CVAE(torch.nn.Module):
         if draws is not None and return_draws:
             key = key + ("draws",)
         g = self._graphs.get(key)
-        if g is None and draws is not None:
-            g = self._graphs[key] = self._capture_ensemble_graph(n, draws, scales, modes, bool(pixel_noise),
-                                                                 bool(return_draws))
         if g is None:
-            g = self._capture_paint_graph(n, pipeline=True, scales=scales, modes=modes, pixel_noise=bool(pixel_noise))
-            self._graphs[key] = g
+            g = self._graphs[key] = self._capture_pipeline(n, draws, scales, modes, bool(pixel_noise), bool(return_draws))
         for u in g["units"]:
             u.maybe_pack()
             u.maybe_bn_eval()
@@ -1208,263 +1204,174 @@ class CVAE(torch.nn.Module):
                 # one scratch per stream of the graph; the two slots replay on one stream and share them
                 "scratch": [torch.empty(max(ws // 4, 1), device=dev) for _ in range(parts)]}
 
-    def _capture_paint_graph(self, n, given_z=False, pipeline=False, scales=None, modes=None, pixel_noise=False):
-        """Eval-mode layers do not couple the tiles of a batch (batch-norm runs on its running statistics), so the
-        batch is painted as BP_PAINT_STREAMS (default 4) sub-batches on as many streams inside one graph: kernels of different layers share
-        the CUs and fill each other's stalls (the effect the training step gets from its weight-gradient
-        stream)."""
-        cy, H, W = self.dim_y
-        cx = self.dim_x[0]
-        dev = self.device
-        fields = len(modes[1]) if modes is not None and isinstance(modes[1], tuple) else 1
-        levels = 1
-        if scales is not None:
-            levels = scales["n_scale"] + int(scales["include_original"])
-            if not pipeline or cy != levels or cx != fields * levels:
-                raise ValueError(f"a {levels}-level split-scale transform needs dim_y[0] = dim_x[0] = {levels}, the "
-                                 f"model has {cy} and {cx}" if fields == 1 else
-                                 f"{fields} label fields of a {levels}-level split-scale transform need dim_y[0] = "
-                                 f"{levels} and dim_x[0] = {fields * levels}, the model has {cy} and {cx}")
-        if fields > 1 and (not pipeline or cx != fields * levels):
-            raise ValueError(f"{fields} label fields of {levels} channel(s) need dim_x[0] = {fields * levels}, the model "
-                             f"has {cx}")
-        st = {"y": None if pipeline else torch.zeros((n, cy, H, W), device=dev),
-              "aux": torch.zeros((n, self.n_aux), device=dev) if self.use_aux_label and not pipeline else None,
-              "out": None if pipeline else torch.zeros((n, cx, H, W), device=dev),
-              "z": torch.zeros((n, *self.dim_z), device=dev) if given_z else None}
-        if pipeline:
-            if scales is not None and self.has_p_y_in:
-                raise NotImplementedError("the captured paint pipeline has no split-scale load step for a p_y_in network "
-                                          "(bp_paint_load_scales2 writes two destinations); paint / paint_batch take it")
-            if self.L != 1:
-                raise NotImplementedError("the captured paint pipeline needs L = 1 (sample_P and paint take any L: they "
-                                          "paint with one latent draw per tile)")
-            per_tile = math.prod(self.dim_z)
-            st["eps"] = torch.zeros((1, n, per_tile), device=dev)
-            # parameter block of a slot: one contiguous device buffer = one host-to-device copy per batch
-            block = PG.ParamBlock(PG.paint_fields(n, 2 if modes is None else 4, max(self.n_aux, 1),
-                                                  xf_out_width=4 * fields if fields > 1 else None, noise=pixel_noise))
-            st["param_block"], st["block_layout"], st["block_bytes"] = block, block.layout, block.nbytes
-            st["slots"] = [PG.new_slot((n, 1 if scales is not None else cy, H, W),
-                                       (n, fields if fields > 1 else 1 if scales is not None else cx, H, W), block, dev)
-                           for _ in range(2)]
+    def _sub_batch_plans(self, n, samples=1):
+        """Eval-mode layers do not couple the tiles of a batch (batch-norm runs on its running statistics), so a captured
+        paint graph paints its ``n`` tiles as BP_PAINT_STREAMS (default 4) sub-batches on as many streams: kernels of
+        different layers share the CUs and fill each other's stalls (the effect the training step gets from its
+        weight-gradient stream).  The count drops until it divides ``n`` and a sub-batch has at least 8 generator samples
+        (``samples`` = K per tile).  Returns (h, plans): the tiles of a sub-batch and one paint plan per sub-batch."""
         parts = int(os.environ.get("BP_PAINT_STREAMS", "4"))
-        while parts > 1 and (n % parts != 0 or n // parts < 8):
+        while parts > 1 and (n % parts != 0 or n // parts * samples < 8):
             parts -= 1
         h = n // parts
-        plans = [self._paint_plan(h)] + [_Plan(self, h, False, False, samples=1) for _ in range(parts - 1)]
-        st["plans"] = plans
-        # (what paint_graph re-packs before a replay when weights changed.  The variance head runs in every replay, but
-        #  only a draw from the likelihood reads it: its units are listed for such a graph, and stay out of the others)
-        st["units"] = PlanBase.flat_units([u for plan in plans
-                                           for us in [plan.p_units] + plan.g_units + [plan.mu_units, plan.y_units]
-                                           + ([plan.var_units] if pixel_noise else [])
-                                           for u in us])
-        others = [torch.cuda.Stream(device=dev) for _ in range(parts - 1)]
-        if scales is not None:
-            sc = st["scales"] = self._scales_context(scales, h, parts)
-            for sl in st["slots"]:
-                sl["scratch"], sl["weights"] = sc["scratch"], sc["weights"]
+        return h, [self._paint_plan(h, samples)] + [_Plan(self, h, False, False, samples=samples)
+                                                    for _ in range(parts - 1)]
 
-        if pipeline:
-            # The load and store steps of this capture, chosen once: the legacy shift-log entry points (two-double rows)
-            # or, with ``modes``, their ``_mode`` forms, which hold the mode as a constant of the graph.
-            lib, y_net = self._lib, bool(plans[0].y_units)
-            if pixel_noise:
-                for plan in plans:
-                    plan.draw_slot()
+    @staticmethod
+    def _paint_units(plans, with_var=False):
+        """What ``paint_graph`` / ``sample_P_graphed`` re-pack before a replay when weights changed.  The variance head
+        runs in every replay, but only a draw from the likelihood reads it: its units are listed for such a graph
+        (``with_var``), and stay out of the others."""
+        return PlanBase.flat_units([u for plan in plans
+                                    for us in [plan.p_units] + plan.g_units + [plan.mu_units, plan.y_units]
+                                    + ([plan.var_units] if with_var else [])
+                                    for u in us])
 
-            def head(plan):
-                """What the store reads, (view, softplus): the mean head, or the draw (bp_likelihood_draw has applied
-                the softplus)."""
-                if pixel_noise:
-                    return C.byref(plan.draw.view), 0
-                return C.byref(plan.mu_head.view), 1 if plan.mu_softplus else 0
+    def _capture_sample_graph(self, n, given_z):
+        """``sample_P_graphed``'s graph for batches of ``n``: NCHW ``y`` and ``aux`` (and ``z``, if given) in, the mean
+        head out as NCHW ``out``; without a given z the latent's normals come from ``torch.randn`` inside the graph."""
+        cy, H, W = self.dim_y
+        dev = self.device
+        h, plans = self._sub_batch_plans(n)
+        st = {"y": torch.zeros((n, cy, H, W), device=dev),
+              "aux": torch.zeros((n, self.n_aux), device=dev) if self.use_aux_label else None,
+              "out": torch.zeros((n, self.dim_x[0], H, W), device=dev),
+              "z": torch.zeros((n, *self.dim_z), device=dev) if given_z else None,
+              "plans": plans, "units": self._paint_units(plans)}
 
-            def entry(name, mode):
-                return getattr(lib, name) if modes is None else functools.partial(getattr(lib, name + "_mode"), mode)
-            m_in, m_out = modes if modes is not None else (None, None)
-            if fields > 1:
-                # one store launch for the whole head: every field's mode is a constant of the graph
-                field_modes = (C.c_int32 * fields)(*m_out)
-                inc = int(scales["include_original"]) if scales is not None else 0
-
-                def store_fields(plan, xf, out, sm):
-                    src, sp = head(plan)
-                    return lib.bp_paint_store_fields(field_modes, fields, levels, inc, src, None, sp, xf, out, sm)
-            if scales is not None:
-                what = " (scales)"
-                load_fn, store_fn = entry("bp_paint_load_scales2", m_in), entry("bp_paint_store_scales", m_out)
-
-                def load(plan, lo, raw, xf, auxp, sm):
-                    return load_fn(raw, xf, auxp, plan.caux, sc["n_scale"], sc["include_original"], L.ptr(sc["weights"]),
-                                   sc["radii"], L.ptr(sc["scratch"][lo // h]), sc["ws"], C.byref(plan.y2.view),
-                                   C.byref(plan.hy_slot.view), sm)
-
-                def store(plan, xf, out, sm):
-                    src, sp = head(plan)
-                    return store_fn(src, None, sp, sc["include_original"], xf, out, sm)
-            else:
-                what = ""
-                # the transformed tile goes where the generator needs it: with a p_y_in network that is y2 alone
-                # (bp_paint_load, then the network), without one y2 and the generator's input (bp_paint_load2)
-                load_fn = entry("bp_paint_load" if y_net else "bp_paint_load2", m_in)
-                store_fn = entry("bp_paint_store", m_out)
-
-                def load(plan, lo, raw, xf, auxp, sm):
-                    dst = (C.byref(plan.y2.view),) if y_net else (C.byref(plan.y2.view), C.byref(plan.hy_slot.view))
-                    return load_fn(raw, cy, xf, auxp, plan.caux, *dst, sm)
-
-                def store(plan, xf, out, sm):
-                    src, sp = head(plan)
-                    return store_fn(src, None, sp, xf, out, sm)
-            if fields > 1:
-                store, what = store_fields, what + f" ({fields} fields)"
-
-        def paint_pipeline(plan, lo, sl):
-            sm = _stream()
-            plan.pack_all()
-            auxp = L.ptr(sl["aux"][lo:lo + h]) if self.use_aux_label else None
-            L.check(load(plan, lo, L.ptr(sl["raw"][lo:lo + h]), L.ptr(sl["xf_in"][lo:lo + h]), auxp, sm),
-                    "paint load" + what)
-            if y_net:
-                plan.run_y_net(False)
-            plan.run_prior(False)
-            eps = st["eps"][:, lo:lo + h]
-            L.check(self._lib.bp_philox_normal_dev(L.ptr(sl["seed"]), L.ptr(sl["tile_ids"][lo:lo + h]), h, 1,
-                                                   eps.shape[-1], L.ptr(eps), sm), "philox")
-            plan.run_latent(eps.reshape(1, h, *self.dim_z), use_q=False)
-            plan.run_generator(False)
-            if pixel_noise:
-                plan.run_draw(sl["seed"], sl["noise_ids"][lo:lo + h], sl["noise_org"][lo:lo + h])
-            L.check(store(plan, L.ptr(sl["xf_out"][lo:lo + h]), L.ptr(sl["out"][lo:lo + h]), sm), "paint store" + what)
-
-        def paint(plan, lo, sl):
-            if pipeline:
-                return paint_pipeline(plan, lo, sl)
-            plan.load_inputs(st["y"][lo:lo + h], None if st["aux"] is None else st["aux"][lo:lo + h])
+        def paint(k, _):
+            plan, part = plans[k], slice(k * h, (k + 1) * h)
+            plan.load_inputs(st["y"][part], None if st["aux"] is None else st["aux"][part])
             if given_z:
-                L.check(self._lib.bp_nchw_to_view(L.ptr(st["z"][lo:lo + h]), self.dim_z[0], None, 0,
-                                                  C.byref(plan.z.view), _stream()), "z layout")
+                L.check(self._lib.bp_nchw_to_view(L.ptr(st["z"][part]), self.dim_z[0], None, 0, C.byref(plan.z.view),
+                                                  _stream()), "z layout")
             else:
                 plan.run_prior(False)
                 plan.run_latent(torch.randn(size=(1, h, *self.dim_z), device=dev), use_q=False)
             plan.run_generator(False)
-            self._head_to_nchw(plan.mu_head, plan.mu_softplus, st["out"][lo:lo + h])
+            self._head_to_nchw(plan.mu_head, plan.mu_softplus, st["out"][part])
 
-        def run(sl=None):
-            main = torch.cuda.current_stream(dev)
-            for k, s2 in enumerate(others):
-                s2.wait_stream(main)
-                with torch.cuda.stream(s2):
-                    paint(plans[k + 1], (k + 1) * h, sl)
-            paint(plans[0], 0, sl)
-            for s2 in others:
-                main.wait_stream(s2)
-
-        st["graph"] = PG.capture(run, st.get("slots", [None]), dev)[0]
+        st["graph"] = PG.capture(PG.fork_join(paint, len(plans), dev), [None], dev)[0]
         return st
 
-    def _capture_ensemble_graph(self, n, draws, scales, modes, pixel_noise, return_draws):
-        """``paint_graph(n, draws=K)``: ``_capture_paint_graph``'s pipeline over plans with K latent draws per tile.  The
-        BP_PAINT_STREAMS sub-batches split the n TILES (a sub-batch of h tiles is h K generator samples); everything in
-        front of the latent runs once per tile, and the store reduces over the draws."""
+    def _capture_pipeline(self, n, draws, scales, modes, pixel_noise, return_draws):
+        """``paint_graph``'s capture: raw tiles and a parameter block in, painted tiles out, two slots.  ``draws`` = None
+        is a single painting, the K = 1 case of an ensemble with a store of its own.  The sub-batches split the n TILES
+        (a sub-batch of h tiles is h K generator samples); everything in front of the latent runs once per tile.  What
+        the variants differ in is chosen once, below: the load step and the store step."""
         cy, H, W = self.dim_y
-        cx, dev, lib, K = self.dim_x[0], self.device, self._lib, draws
-        m_in, m_out = int(modes[0]), modes[1] if isinstance(modes[1], tuple) else (int(modes[1]),)
-        fields = len(m_out)
-        levels = 1 if scales is None else scales["n_scale"] + int(scales["include_original"])
-        if (cy != levels and scales is not None) or cx != fields * levels:
-            raise ValueError(f"{fields} label field(s) of {levels} channel(s) need dim_x[0] = {fields * levels}"
-                             + (f" and dim_y[0] = {levels}" if scales is not None else "")
-                             + f", the model has dim_y[0] = {cy} and dim_x[0] = {cx}")
-        if scales is not None and self.has_p_y_in:
-            raise NotImplementedError("the captured paint pipeline has no split-scale load step for a p_y_in network "
-                                      "(bp_paint_load_scales2 writes two destinations); paint / paint_batch take it")
-        parts = int(os.environ.get("BP_PAINT_STREAMS", "4"))
-        while parts > 1 and (n % parts != 0 or n // parts * K < 8):
-            parts -= 1
-        h = n // parts
-        per_tile = math.prod(self.dim_z)
-        block = PG.ParamBlock(PG.paint_fields(n, 4, max(self.n_aux, 1), xf_out_width=4 * fields, noise=pixel_noise,
-                                              draws=K, parts=parts))
-        outs = {"mean": (n, fields, H, W), "var": (n, fields, H, W)}
-        if return_draws:
-            outs["draws"] = (n, K, fields, H, W)
-        st = {"draws": K, "parts": parts, "eps": torch.zeros((parts, K, h, per_tile), device=dev),
+        dev, lib = self.device, self._lib
+        K = 1 if draws is None else draws
+        m_in = None if modes is None else modes[0]
+        field_modes = (None,) if modes is None else modes[1] if isinstance(modes[1], tuple) else (modes[1],)
+        fields = len(field_modes)
+        levels = PG.paint_levels(cy, self.dim_x[0], self.has_p_y_in, self.L, scales, fields, draws is not None)
+        inc = 0 if scales is None else int(scales["include_original"])
+        h, plans = self._sub_batch_plans(n, K)
+        parts, per_tile = len(plans), math.prod(self.dim_z)
+        # parameter block of a slot: one contiguous device buffer = one host-to-device copy per batch
+        block = PG.ParamBlock(PG.paint_fields(n, 2 if modes is None else 4, max(self.n_aux, 1),
+                                              xf_out_width=None if modes is None else 4 * fields, noise=pixel_noise,
+                                              draws=draws, parts=parts))
+        outs = (n, fields, H, W)
+        if draws is not None:
+            outs = {"mean": outs, "var": outs, **({"draws": (n, K, fields, H, W)} if return_draws else {})}
+        st = {"draws": draws, "parts": parts, "plans": plans, "units": self._paint_units(plans, pixel_noise),
+              "eps": torch.zeros((1, n, per_tile) if draws is None else (parts, K, h, per_tile), device=dev),
               "param_block": block, "block_layout": block.layout, "block_bytes": block.nbytes,
-              "slots": [PG.new_slot((n, 1 if scales is not None else cy, H, W), outs, block, dev) for _ in range(2)]}
-        plans = st["plans"] = [self._paint_plan(h, K)] + [_Plan(self, h, False, False, samples=K)
-                                                           for _ in range(parts - 1)]
-        st["units"] = PlanBase.flat_units([u for plan in plans
-                                           for us in [plan.p_units] + plan.g_units + [plan.mu_units, plan.y_units]
-                                           + ([plan.var_units] if pixel_noise else [])
-                                           for u in us])
-        others = [torch.cuda.Stream(device=dev) for _ in range(parts - 1)]
+              "slots": [PG.new_slot((n, 1, H, W), outs, block, dev) for _ in range(2)]}
         y_net = bool(plans[0].y_units)
         if pixel_noise:
             for plan in plans:
                 plan.draw_slot()
-        field_modes = (C.c_int32 * fields)(*m_out)
-        inc = int(scales["include_original"]) if scales is not None else 0
         if scales is not None:
             sc = st["scales"] = self._scales_context(scales, h, parts)
             for sl in st["slots"]:
                 sl["scratch"], sl["weights"] = sc["scratch"], sc["weights"]
 
-        def block0(plan):
-            """Sample block 0 of the generator's h_y slice (draw 0 of the h tiles), and the K - 1 blocks behind it."""
+        def entry(name, mode):
+            """The legacy shift-log entry point (two-double rows) or, with ``modes``, its ``_mode`` form, which holds
+            the mode as a constant of the graph."""
+            return getattr(lib, name) if modes is None else functools.partial(getattr(lib, name + "_mode"), mode)
+
+        def generator_y(plan):
+            """Where the load puts the generator's copy of the transformed tile, and the K - 1 sample blocks behind it
+            that it is repeated into: the plan's h_y slice, or (an ensemble) draw 0 of it and the rest."""
             s = plan.hy_slot
+            if draws is None:
+                return s.view, None
             rest = L.View(plan.p_in.buf[h:].data_ptr(), h * (K - 1), s.h, s.w, s.c, s.cstride, s.coff) if K > 1 else None
             return L.View(plan.p_in.buf.data_ptr(), h, s.h, s.w, s.c, s.cstride, s.coff), rest
 
-        def paint(plan, k, sl):
-            sm, lo = _stream(), k * h
+        # The load step.  The transformed tile goes where the generator needs it: with a p_y_in network that is y2 alone
+        # (bp_paint_load, then the network), without one y2 and the generator's input (bp_paint_load2); a split-scale
+        # painter builds the pyramid behind the transform (bp_paint_load_scales2, two destinations).
+        if scales is not None:
+            load_fn = entry("bp_paint_load_scales2", m_in)
+
+            def load(plan, k, first, raw, xf, auxp, sm):
+                return load_fn(raw, xf, auxp, plan.caux, sc["n_scale"], sc["include_original"], L.ptr(sc["weights"]),
+                               sc["radii"], L.ptr(sc["scratch"][k]), sc["ws"], C.byref(plan.y2.view), C.byref(first), sm)
+        elif y_net:
+            load_fn = entry("bp_paint_load", m_in)
+
+            def load(plan, k, first, raw, xf, auxp, sm):
+                return load_fn(raw, cy, xf, auxp, plan.caux, C.byref(plan.y2.view), sm)
+        else:
+            load_fn = entry("bp_paint_load2", m_in)
+
+            def load(plan, k, first, raw, xf, auxp, sm):
+                return load_fn(raw, cy, xf, auxp, plan.caux, C.byref(plan.y2.view), C.byref(first), sm)
+
+        # The store step reads (src, softplus) -- the mean head, or under ``pixel_noise`` the draw (bp_likelihood_draw
+        # has applied the softplus) -- and writes tiles [lo, lo + h) of the slot.  An ensemble reduces over the draws;
+        # several fields go out in one launch for the whole head, every field's mode a constant of the graph.
+        fm = (C.c_int32 * fields)(*field_modes) if modes is not None else None
+        if draws is not None:
+            def store(src, sp, xf, sl, lo, sm):
+                return lib.bp_paint_store_moments(fm, fields, levels, inc, src, None, sp, xf, K, L.ptr(sl["mean"][lo:lo + h]),
+                                                  L.ptr(sl["var"][lo:lo + h]),
+                                                  L.ptr(sl["draws"][lo:lo + h]) if return_draws else None, sm)
+        elif fields > 1:
+            def store(src, sp, xf, sl, lo, sm):
+                return lib.bp_paint_store_fields(fm, fields, levels, inc, src, None, sp, xf, L.ptr(sl["out"][lo:lo + h]), sm)
+        elif scales is not None:
+            store_fn = entry("bp_paint_store_scales", field_modes[0])
+
+            def store(src, sp, xf, sl, lo, sm):
+                return store_fn(src, None, sp, inc, xf, L.ptr(sl["out"][lo:lo + h]), sm)
+        else:
+            store_fn = entry("bp_paint_store", field_modes[0])
+
+            def store(src, sp, xf, sl, lo, sm):
+                return store_fn(src, None, sp, xf, L.ptr(sl["out"][lo:lo + h]), sm)
+
+        def paint(k, sl):
+            plan, sm, lo = plans[k], _stream(), k * h
             plan.pack_all()
-            raw, xf = L.ptr(sl["raw"][lo:lo + h]), L.ptr(sl["xf_in"][lo:lo + h])
             auxp = L.ptr(sl["aux"][lo:lo + h]) if self.use_aux_label else None
-            first, rest = block0(plan)
-            if scales is not None:
-                rc = lib.bp_paint_load_scales2_mode(m_in, raw, xf, auxp, plan.caux, sc["n_scale"], sc["include_original"],
-                                                    L.ptr(sc["weights"]), sc["radii"], L.ptr(sc["scratch"][k]), sc["ws"],
-                                                    C.byref(plan.y2.view), C.byref(first), sm)
-            elif y_net:
-                rc = lib.bp_paint_load_mode(m_in, raw, cy, xf, auxp, plan.caux, C.byref(plan.y2.view), sm)
-            else:
-                rc = lib.bp_paint_load2_mode(m_in, raw, cy, xf, auxp, plan.caux, C.byref(plan.y2.view), C.byref(first), sm)
-            L.check(rc, "ensemble load")
+            first, rest = generator_y(plan)
+            L.check(load(plan, k, first, L.ptr(sl["raw"][lo:lo + h]), L.ptr(sl["xf_in"][lo:lo + h]), auxp, sm), "paint load")
             if y_net:
                 plan.run_y_net(False)                    # (repeats h_y over K itself)
             elif K > 1:
                 L.check(lib.bp_repeat_samples(C.byref(first), K - 1, C.byref(rest), sm), "repeat y over the draws")
             plan.run_prior(False)
-            eps = st["eps"][k]
+            eps = st["eps"].view(parts, K, h, per_tile)[k]
             L.check(lib.bp_philox_normal_dev(L.ptr(sl["seed"]), L.ptr(sl["tile_ids"][lo:lo + h]), h, K, per_tile,
                                              L.ptr(eps), sm), "philox")
             plan.run_latent(eps.view(K, h, *self.dim_z), use_q=False)
             plan.run_generator(False)
+            src, sp = C.byref(plan.mu_head.view), 1 if plan.mu_softplus else 0
             if pixel_noise:
-                plan.run_draw(sl["seed"], sl["noise_ids"][k], None)
+                if draws is None:
+                    plan.run_draw(sl["seed"], sl["noise_ids"][lo:lo + h], sl["noise_org"][lo:lo + h])
+                else:                                    # (per sub-batch the ids of its samples, draw-major; no origins)
+                    plan.run_draw(sl["seed"], sl["noise_ids"][k], None)
                 src, sp = C.byref(plan.draw.view), 0
-            else:
-                src, sp = C.byref(plan.mu_head.view), 1 if plan.mu_softplus else 0
-            L.check(lib.bp_paint_store_moments(field_modes, fields, levels, inc, src, None, sp,
-                                               L.ptr(sl["xf_out"][lo:lo + h]), K, L.ptr(sl["mean"][lo:lo + h]),
-                                               L.ptr(sl["var"][lo:lo + h]),
-                                               L.ptr(sl["draws"][lo:lo + h]) if return_draws else None, sm),
-                    "ensemble store")
+            L.check(store(src, sp, L.ptr(sl["xf_out"][lo:lo + h]), sl, lo, sm), "paint store")
 
-        def run(sl):
-            main = torch.cuda.current_stream(dev)
-            for k, s2 in enumerate(others):
-                s2.wait_stream(main)
-                with torch.cuda.stream(s2):
-                    paint(plans[k + 1], k + 1, sl)
-            paint(plans[0], 0, sl)
-            for s2 in others:
-                main.wait_stream(s2)
-
-        st["graph"] = PG.capture(run, st["slots"], dev)[0]
+        st["graph"] = PG.capture(PG.fork_join(paint, parts, dev), st["slots"], dev)[0]
         return st
 
     # ---- the whole training step as one hipGraph (small minibatches are launch-bound: ~450 launches per step)

@@ -115,6 +115,28 @@ def noise_lattice(ids, origins, n, h, w):
     return np.ascontiguousarray(ids), org
 
 
+def paint_levels(cy, cx, has_p_y_in, L, scales, fields, ensemble, mismatch=ValueError):
+    """Which CVAEs the captured paint pipeline takes, in ONE place (``CVAE.paint_graph`` and
+    ``CVAEPainter._device_paint_parameters`` both ask here).  ``cy`` = dim_y[0] and ``cx`` = dim_x[0] of the model,
+    ``scales`` its split-scale description or None, ``fields`` the number of label fields, ``ensemble`` whether the
+    number of draws is the caller's (``paint_graph(draws=K)``) and not the model's ``L``.  Returns the channels of one
+    field, ``levels`` = n_scale + include_original (1 without ``scales``), or raises: ``mismatch`` where the model's
+    channels are not cy = levels and cx = fields * levels, NotImplementedError for what the pipeline has no step for.
+    Needs no GPU."""
+    levels = 1 if scales is None else int(scales["n_scale"]) + int(bool(scales["include_original"]))
+    if cy != levels or cx != fields * levels:
+        raise mismatch(f"the captured paint pipeline paints {fields} label field(s) of {levels} channel(s) from tiles of "
+                       f"{levels} channel(s) (a split-scale transform's levels, or 1): it needs dim_y[0] = {levels} and "
+                       f"dim_x[0] = {fields * levels}, the model has {cy} and {cx}")
+    if scales is not None and has_p_y_in:
+        raise NotImplementedError("the captured paint pipeline has no split-scale load step for a p_y_in network "
+                                  "(bp_paint_load_scales2 writes two destinations); paint / paint_batch take it")
+    if L != 1 and not ensemble:
+        raise NotImplementedError("the captured paint pipeline needs L = 1 (sample_P, paint and paint_batch take any L: "
+                                  "they paint with one latent draw per tile)")
+    return levels
+
+
 def new_slot(raw_shape, out_shape, block, device):
     """One slot: ``raw``, ``out``, the uint8 ``block`` and its named views, ``xf_in`` / ``xf_out`` filled with 1.0 (a
     valid transform for the warm-up).  ``out_shape`` may be a dict name -> shape of several outputs in place of ``out``
@@ -126,6 +148,24 @@ def new_slot(raw_shape, out_shape, block, device):
     sl["xf_in"].fill_(1.0)
     sl["xf_out"].fill_(1.0)
     return sl
+
+
+def fork_join(part, parts, device):
+    """``run(sl)`` for ``capture``: ``part(k, sl)`` for k < ``parts``, part 0 on the current stream and part k > 0 on a
+    side stream of its own -- the side streams wait on the main stream, run their parts, and the main stream waits on all
+    of them, so that inside one graph the parts are parallel branches."""
+    others = [torch.cuda.Stream(device=device) for _ in range(parts - 1)]
+
+    def run(sl=None):
+        main = torch.cuda.current_stream(device)
+        for k, s2 in enumerate(others, 1):
+            s2.wait_stream(main)
+            with torch.cuda.stream(s2):
+                part(k, sl)
+        part(0, sl)
+        for s2 in others:
+            main.wait_stream(s2)
+    return run
 
 
 def capture(run, slots, device):

@@ -19,6 +19,8 @@ import torch
 import torch.utils.data
 
 from .models import cvae as _cvae
+from .models import paint_graph as PG
+from .models.paint_graph import seed_word as _seed_word      # noqa: F401  (the name this module had for it)
 from .utils import datasets
 
 try:                                    # the reference pickles its metadata with dill
@@ -57,6 +59,21 @@ class Painter:
         variance head.  No side effects: nothing is captured, no random number is drawn."""
         raise ValueError(f"pixel_noise=True: {type(self).__name__} has no likelihood with a variance head to draw from")
 
+    def _stream_prologue(self, inputs, z, tile_ids, rank, world_size):
+        """What ``paint_stream`` and ``paint_ensemble`` begin with: the model in eval mode, the tiles' shape checked
+        (ValueError), ``z`` broadcast over the N tiles, ``tile_ids`` defaulting to 0 ... N - 1, and this rank's share
+        [lo, hi) of the tiles.  Returns (model, (H, W), N, zs, ids, lo, hi); nothing is captured."""
+        model = self.model
+        model.train(False)
+        H, W = self._tile_shape()
+        N = len(inputs)
+        if tuple(inputs.shape[1:]) != (H, W):
+            raise ValueError(self._shape_mismatch(tuple(inputs.shape)))
+        zs = np.broadcast_to(np.asarray(z, dtype=np.float64), (N,))
+        ids = np.arange(N, dtype=np.int64) if tile_ids is None else np.asarray(tile_ids, dtype=np.int64)
+        per = (N + world_size - 1) // world_size
+        return model, (H, W), N, zs, ids, min(rank * per, N), min((rank + 1) * per, N)
+
     def paint_stream(self, inputs, z, batch_size=64, tile_ids=None, seed=0, rank=0, world_size=1, out=None,
                      pixel_noise=False, noise_ids=None, noise_origins=None):
         """Paint MANY raw tiles: ``inputs`` (N, H, W) float32 host array (NumPy, memory map, or a pinned torch tensor),
@@ -82,18 +99,9 @@ class Painter:
             ``seed``: lattice ``noise_ids[i]`` [default: ``tile_ids[i]``], window origin ``noise_origins[i]`` =
             (row, col) >= 0 [default: (0, 0)].  Like the latent noise it does not depend on batches or ranks; tiles that
             share an id see the same e where their windows overlap."""
-        model = self.model
-        model.train(False)
+        model, (H, W), N, zs, ids, lo, hi = self._stream_prologue(inputs, z, tile_ids, rank, world_size)
         if pixel_noise:
             self._need_pixel_noise()
-        H, W = self._tile_shape()
-        N = len(inputs)
-        if tuple(inputs.shape[1:]) != (H, W):
-            raise ValueError(self._shape_mismatch(tuple(inputs.shape)))
-        zs = np.broadcast_to(np.asarray(z, dtype=np.float64), (N,))
-        ids = np.arange(N, dtype=np.int64) if tile_ids is None else np.asarray(tile_ids, dtype=np.int64)
-        per = (N + world_size - 1) // world_size
-        lo, hi = min(rank * per, N), min((rank + 1) * per, N)
         params, scales, modes = self._device_paint_parameters(zs[lo:hi])     # (NotImplementedError before any capture)
         if pixel_noise:
             params = _with_noise(params, ids if noise_ids is None else noise_ids, noise_origins, N, H, W, lo, hi)
@@ -430,7 +438,6 @@ class CVAEPainter(Painter):
         inputs = np.asarray(inputs)
         zs = np.broadcast_to(np.asarray(z, dtype=np.float64), (inputs.shape[0],))
         if pixel_noise:
-            from .models import paint_graph as PG
             self._need_pixel_noise()
             N = inputs.shape[0]
             n_ids, n_org = PG.noise_lattice(np.arange(N, dtype=np.int64) if noise_ids is None else noise_ids,
@@ -539,37 +546,15 @@ class CVAEPainter(Painter):
 
     def _device_paint_parameters(self, zs, ensemble=False):
         """``_transform_parameters(zs)`` where this painter has a device form -- one of the six range compressions on
-        either side (one per label field) and L = 1, with or without a prior network or a p_y_in network; single-channel
-        tiles, or a split-scale transform in the orders ``_transform_parameters`` names whose levels are the model's
-        dim_y[0] = dim_x[0], without a p_y_in network; with F > 1 label fields dim_x[0] = F * dim_y[0] -- and
-        NotImplementedError where it has none.  No side effects.  ``ensemble`` (``paint_ensemble``: the number of draws
-        is its argument, not the model's): any L, and ``_transform_parameters(zs, records=True)``."""
+        either side (one per label field), with or without a prior network or a p_y_in network, a split-scale transform
+        in the orders ``_transform_parameters`` names, and a model the captured pipeline takes
+        (``paint_graph.paint_levels``: channels, L = 1, no split-scale with a p_y_in network) -- and NotImplementedError
+        where it has none.  No side effects.  ``ensemble`` (``paint_ensemble``: the number of draws is its argument, not
+        the model's): any L, and ``_transform_parameters(zs, records=True)``."""
         model = self.model
-        if getattr(model, "L", 1) != 1 and not ensemble:
-            raise NotImplementedError("the captured paint pipeline needs L = 1 (paint / paint_batch take any L)")
         params, scales, modes = self._transform_parameters(zs, records=ensemble)
-        cy, cx = model.dim_y[0], model.dim_x[0]
-        F = len(self.label_fields)
-        if F > 1:
-            levels = 1 if scales is None else scales["n_scale"] + int(scales["include_original"])
-            if scales is not None and getattr(model, "has_p_y_in", False):
-                raise NotImplementedError("the device paint path takes split-scale tiles only for models without a "
-                                          "p_y_in network")
-            if cy != levels or cx != F * levels:
-                raise NotImplementedError(f"the device paint path needs dim_y[0] = {levels} and dim_x[0] = {F * levels} "
-                                          f"for {F} label fields of {levels} channel(s), the model has {cy} and {cx}")
-        elif scales is None:
-            if cy != 1:
-                raise NotImplementedError("the device paint path takes single-channel input tiles (or a split-scale "
-                                          "transform's levels)")
-        else:
-            if getattr(model, "has_p_y_in", False):     # (no split-scale load step with one destination: CVAE.paint_graph)
-                raise NotImplementedError("the device paint path takes split-scale tiles only for models without a "
-                                          "p_y_in network")
-            levels = scales["n_scale"] + int(scales["include_original"])
-            if cy != levels or cx != levels:
-                raise NotImplementedError(f"the device paint path needs dim_y[0] = dim_x[0] = {levels} for this "
-                                          f"split-scale transform, the model has {cy} and {cx}")
+        PG.paint_levels(model.dim_y[0], model.dim_x[0], getattr(model, "has_p_y_in", False), getattr(model, "L", 1),
+                        scales, len(self.label_fields), ensemble, mismatch=NotImplementedError)
         return params, scales, modes
 
     def paint_ensemble(self, inputs, z, draws, batch_size=64, tile_ids=None, seed=0, rank=0, world_size=1,
@@ -592,28 +577,19 @@ class CVAEPainter(Painter):
 
         Planes and light cones have no ensemble form: the moments of a feathered blend of overlapping tiles are not
         the blend of the tiles' moments."""
-        from .models import paint_graph as PG
         K = PG.check_draws(draws)
         B = int(batch_size)
         if B < K or B % K:
             raise ValueError(f"batch_size counts generator samples: {K} draws per tile must divide it, got {batch_size}")
-        N = len(inputs)
-        ids = np.arange(N, dtype=np.int64) if tile_ids is None else np.asarray(tile_ids, dtype=np.int64)
-        lattice = None
-        if pixel_noise:
+        if pixel_noise:                                   # (checked before the model is touched)
             self._need_pixel_noise()
-            lattice = np.asarray(ids if noise_ids is None else noise_ids)
+            N = len(inputs)
+            lattice = np.asarray(noise_ids) if noise_ids is not None else \
+                np.arange(N, dtype=np.int64) if tile_ids is None else np.asarray(tile_ids, dtype=np.int64)
             if lattice.shape != (N,):
                 raise ValueError(f"noise ids must be {N} integers, got shape {lattice.shape}")
             PG.ensemble_noise_ids(lattice, 1)             # (the range check, before any capture)
-        model = self.model
-        model.train(False)
-        H, W = self._tile_shape()
-        if tuple(inputs.shape[1:]) != (H, W):
-            raise ValueError(self._shape_mismatch(tuple(inputs.shape)))
-        zs = np.broadcast_to(np.asarray(z, dtype=np.float64), (N,))
-        per = (N + world_size - 1) // world_size
-        lo, hi = min(rank * per, N), min((rank + 1) * per, N)
+        model, (H, W), N, zs, ids, lo, hi = self._stream_prologue(inputs, z, tile_ids, rank, world_size)
         params, scales, modes = self._device_paint_parameters(zs[lo:hi], ensemble=True)
         if pixel_noise:
             params = dict(params, noise_ids=lattice[lo:hi].astype(np.int64))
@@ -687,7 +663,6 @@ def _fill_block(hv, params, ids, a, b, B):
     keys = ("xf_in", "xf_out", "aux", "tile_ids")
     if "noise_ids" in params and hv["noise_ids"].ndim == 3:
         # an ensemble pipeline: (parts, K, B / parts), per sub-batch of tiles the ids of its draws, draw-major
-        from .models import paint_graph as PG
         parts, K, h = hv["noise_ids"].shape
         tile = np.empty(B, np.int64)
         tile[:m] = params["noise_ids"][a:b]
@@ -705,7 +680,6 @@ def _fill_block(hv, params, ids, a, b, B):
 def _with_noise(params, noise_ids, noise_origins, N, H, W, lo, hi):
     """``params`` of tiles [lo, hi) of ``N`` with the two fields of a pipeline that paints with pixel noise:
     ``noise_ids`` / ``noise_org`` of all N tiles, checked (``paint_graph.noise_lattice``: ValueError), cut to [lo, hi)."""
-    from .models import paint_graph as PG
     ids, org = PG.noise_lattice(noise_ids, noise_origins, N, H, W)
     if org is None:
         org = np.zeros((N, 2), np.int32)
@@ -721,10 +695,6 @@ def _paint_graph(model, B, scales, modes, pixel_noise=False, ensemble=None):
 def _n_fields(modes):
     """The number of label fields ``modes`` speaks of: (input mode, (mode of field 0, ...)) for several, 1 otherwise."""
     return len(modes[1]) if modes is not None and isinstance(modes[1], (tuple, list)) else 1
-
-
-def _seed_word(seed):
-    return np.array(int(seed) & 0xFFFFFFFFFFFFFFFF, dtype=np.uint64).astype(np.int64)
 
 
 def _paint_stream_pipeline(painter, model, inputs, tile_shape, lo, hi, B, params, ids, seed, out, scales=None,
@@ -778,7 +748,7 @@ def _paint_stream_pipeline(painter, model, inputs, tile_shape, lo, hi, B, params
     for gs, hb in zip(g["slots"], cache[key]):
         h_blk = hb["h_blk"]
         hv = block.views(h_blk)
-        hv["seed"][0] = _seed_word(seed)
+        hv["seed"][0] = PG.seed_word(seed)
         if not torch_in and hb["h_in"] is None:
             hb["h_in"] = torch.empty((B, 1, H, W), dtype=torch.float32).pin_memory()
         if not torch_out and hb["h_out"] is None:
@@ -884,7 +854,7 @@ def _paint_plane_pipeline(painter, model, tile, delta, geo, B, params, tile_ids,
     blocks = torch.zeros((n_batches, g["block_bytes"]), dtype=torch.uint8)
     for bi in range(n_batches):
         hv = block.views(blocks[bi])
-        hv["seed"][0] = _seed_word(seed)
+        hv["seed"][0] = PG.seed_word(seed)
         _fill_block(hv, params, tile_ids, bi * B, min(bi * B + B, n), B)
     lib = L.load()
     # accumulators and the resampling scratch are kept between calls (release_paint_buffers() frees them)

@@ -3,7 +3,10 @@ split-scale transform (with and without modes), with a p_y_in network, without a
 with and without a given z, and the CGAN pipeline in fp32 and bf16.  tests/golden/paint_sequence.json pins the
 single-scale shift-log CVAE alone; tests/golden/paint_sequences.json holds, per variant, the unit names and the entry
 points in call order (warm-up, slot 0, slot 1) as ``record_all`` found them on the commit before the captured paint
-paths were given one owner (models/paint_graph.py).  Fresh 64^2 models at batch 8."""
+paths were given one owner (models/paint_graph.py).  The entries of the pipelines added since -- several label fields,
+pixel noise, ensembles of K draws, and the one single painting with four sub-batches (batch 32) -- and ``plans``, the
+number of sub-batch plans of every CVAE pipeline, were recorded the same way on the commit before the single and the
+ensemble capture became one.  Fresh 64^2 models at batch 8 unless an entry says otherwise."""
 import json
 import os
 
@@ -21,6 +24,7 @@ pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "paint_sequences.json")
 BATCH = 8
 MODES = (T.MODE_IDS["log-tanh"], T.MODE_IDS["x/(1+x)"])
+FIELD_MODES = (T.MODE_IDS["log"], (T.MODE_IDS["shift-log-2p"], T.MODE_IDS["1/x"]))      # (input, (field 0, field 1))
 SCALES = {"n_scale": N_SCALE, "step_size": STEP, "include_original": True}
 
 
@@ -34,11 +38,11 @@ def _cvae(arch):
     return model, log
 
 
-def _pipeline(arch, **kw):
+def _pipeline(arch, batch=BATCH, **kw):
     model, log = _cvae(arch)
-    g = model.paint_graph(BATCH, **kw)
+    g = model.paint_graph(batch, **kw)
     torch.cuda.synchronize()
-    return {"units": [u.name for u in g["units"]], "entry_points": log}
+    return {"units": [u.name for u in g["units"]], "entry_points": log, "plans": len(g["plans"])}
 
 
 def _sample_p(given_z):
@@ -70,6 +74,21 @@ VARIANTS = {
     "cvae scales modes": lambda: _pipeline(A.fiducial_architecture(SIZE, n_scale=N_SCALE + 1), scales=SCALES, modes=MODES),
     "cvae p_y_in": lambda: _pipeline(CN.architectures()["a"]),
     "cvae no prior": lambda: _pipeline(CN.architectures()["c"]),
+    "cvae shift-log b32": lambda: _pipeline(A.fiducial_architecture(SIZE), batch=32),
+    "cvae fields": lambda: _pipeline(A.fiducial_architecture(SIZE, n_fields=2), modes=FIELD_MODES),
+    "cvae fields scales": lambda: _pipeline(A.fiducial_architecture(SIZE, n_fields=2, n_scale=N_SCALE + 1), scales=SCALES,
+                                            modes=FIELD_MODES),
+    "cvae noise": lambda: _pipeline(A.fiducial_architecture(SIZE, predict_var=True), pixel_noise=True),
+    "cvae noise scales modes": lambda: _pipeline(A.fiducial_architecture(SIZE, predict_var=True, n_scale=N_SCALE + 1),
+                                                 scales=SCALES, modes=MODES, pixel_noise=True),
+    "ensemble k4": lambda: _pipeline(A.fiducial_architecture(SIZE), draws=4),
+    "ensemble k1": lambda: _pipeline(A.fiducial_architecture(SIZE), draws=1),
+    "ensemble k4 noise draws": lambda: _pipeline(A.fiducial_architecture(SIZE, predict_var=True), draws=4,
+                                                 pixel_noise=True, return_draws=True),
+    "ensemble k4 scales": lambda: _pipeline(A.fiducial_architecture(SIZE, n_scale=N_SCALE + 1), draws=4, scales=SCALES),
+    "ensemble k4 fields": lambda: _pipeline(A.fiducial_architecture(SIZE, n_fields=2), draws=4, modes=FIELD_MODES),
+    "ensemble k4 p_y_in": lambda: _pipeline(CN.architectures()["a"], draws=4),
+    "ensemble k4 no prior": lambda: _pipeline(CN.architectures()["c"], draws=4),
     "sample_P_graphed": lambda: _sample_p(False),
     "sample_P_graphed z": lambda: _sample_p(True),
     "cgan fp32": lambda: _cgan("fp32"),
@@ -96,6 +115,8 @@ def test_variant_launches_what_it_launched_before(before, name):
     now = VARIANTS[name]()
     assert now["units"] == before[name]["units"]
     assert now["entry_points"] == before[name]["entry_points"]
+    if "plans" in before[name]:
+        assert now["plans"] == before[name]["plans"]
     assert len(now["entry_points"]) > 0
 
 

@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 import torch
 
-from baryon_painter_amd.models.paint_graph import ParamBlock, paint_fields
+from baryon_painter_amd.models.paint_graph import ParamBlock, paint_fields, paint_levels
 from baryon_painter_amd.painter import _fill_block, _seed_word
 
 # n = 3: the float32 ``aux`` field is 12 bytes and rounds up to 16; ``tile_ids`` is 24 bytes, ``seed`` 8.
@@ -67,3 +67,47 @@ def test_host_views_alias_the_buffer_and_a_short_batch_repeats_its_last_tile(cas
     assert np.array_equal(raw[offsets["tile_ids"] + 8:offsets["tile_ids"] + 24].view(np.int64), [2 ** 40 + 7] * 2)
     assert np.array_equal(raw[offsets["aux"]:offsets["aux"] + 12].view(np.float32), np.float32([0.125, 2.5, 2.5]))
     assert not raw[offsets["aux"] + 12:].any()            # the padding of the last field stays untouched
+
+
+# ------------------------------------------------------------------------------------------- the geometry rule
+def _scales(levels):
+    return None if levels == 1 else {"n_scale": levels - 1, "step_size": 2.0, "include_original": True}
+
+
+@pytest.mark.parametrize("ensemble", [False, True])
+@pytest.mark.parametrize("p_y_in", [False, True])
+@pytest.mark.parametrize("levels", [1, 3])
+@pytest.mark.parametrize("F", [1, 2])
+def test_geometry_rule_of_the_captured_pipeline(F, levels, p_y_in, ensemble):
+    """dim_y[0] = levels, dim_x[0] = F levels; no split-scale with a p_y_in network; L = 1 unless an ensemble.  Per
+    point of the table the good case, and each axis gone wrong on its own."""
+    sc = _scales(levels)
+    split_with_net = sc is not None and p_y_in
+
+    def rule(cy=levels, cx=F * levels, L=1, **kw):
+        return paint_levels(cy, cx, p_y_in, L, sc, F, ensemble, **kw)
+    if split_with_net:
+        for L in (1, 2):
+            with pytest.raises(NotImplementedError, match="p_y_in"):
+                rule(L=L)
+    else:
+        assert rule() == levels
+        if ensemble:
+            assert rule(L=2) == levels
+        else:
+            with pytest.raises(NotImplementedError, match="captured.*L = 1"):
+                rule(L=2)
+    # the channels are looked at first, and the caller names the exception (the painter: NotImplementedError)
+    for bad in ({"cy": levels + 1}, {"cx": F * levels + 1}, {"cx": levels} if F > 1 else {"cx": 2 * levels}):
+        with pytest.raises(ValueError, match="dim_y") as e:
+            rule(**bad)
+        assert not isinstance(e.value, NotImplementedError)
+        with pytest.raises(NotImplementedError, match="captured"):
+            rule(mismatch=NotImplementedError, **bad)
+
+
+def test_geometry_rule_counts_the_original_as_a_level():
+    assert paint_levels(2, 2, False, 1, {"n_scale": 2, "step_size": 2.0, "include_original": False}, 1, False) == 2
+    assert paint_levels(3, 6, False, 1, {"n_scale": 2, "step_size": 2.0, "include_original": True}, 2, False) == 3
+    with pytest.raises(ValueError):
+        paint_levels(3, 3, False, 1, {"n_scale": 2, "step_size": 2.0, "include_original": False}, 1, False)
