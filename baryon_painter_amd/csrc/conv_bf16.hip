@@ -165,7 +165,11 @@ int bp_bf16_igemm_run(const ConvGeom& g, const bp_view* in, const PW& pw, const 
         if (bp_bf16_flat_ok(g, in, out, bias, mode)) return bp_bf16_flat_run(g, in, pw, image + l.flat, out, st, sr);
         break;
       case B_WS:
-        if (bp_bf16_ws_ok(g, in, out, bias, mode)) return bp_bf16_ws_run(g, in, pw, image + l.ws, out, st, sr);
+        if (bp_bf16_ws_ok(g, in, out, bias, mode)) {
+          // (the query answers for the generic kernel too, which bp_set_option may bring back: the caller is held to it)
+          if (sr && sr->ws_bytes < bp_bf16_stats_workspace(g, in, out, mode)) return BP_EWORKSPACE;
+          return bp_bf16_ws_run(g, in, pw, image + l.ws, out, st, sr);
+        }
         break;
       case B_GENERIC: break;      // (below)
     }

@@ -40,7 +40,8 @@ struct FlatArgs {
   double* stat;
 };
 
-template <bool OUT_VEC, bool STATS2>
+// RAW_VEC: every pixel's slice of `raw` starts on a 16-byte boundary (one float4 load); otherwise four scalar loads
+template <bool OUT_VEC, bool STATS2, bool RAW_VEC = true>
 __global__ __launch_bounds__(256, 2) void flat_k7_kernel(FlatArgs a) {
   __shared__ __attribute__((aligned(16))) float tile[NQ * PLANE];
   __shared__ double lsum[STATS2 ? 8 * 256 : 1];      // per-lane running sums (registers hold the weights)
@@ -128,7 +129,9 @@ __global__ __launch_bounds__(256, 2) void flat_k7_kernel(FlatArgs a) {
         float4 rq = make_float4(0.f, 0.f, 0.f, 0.f);
         if constexpr (STATS2) {                        // (issued before the MFMA chain, used after it)
           const int Yc = min(y0 + row, a.h - 1), Xc = min(x0 + ct * 16 + lm, a.w - 1);
-          rq = *reinterpret_cast<const float4*>(a.raw + (((int64_t)n * a.h + Yc) * a.w + Xc) * a.raw_cs + a.raw_co + 4 * kq);
+          const float* rp = a.raw + (((int64_t)n * a.h + Yc) * a.w + Xc) * a.raw_cs + a.raw_co + 4 * kq;
+          if constexpr (RAW_VEC) rq = *reinterpret_cast<const float4*>(rp);
+          else rq = make_float4(rp[0], rp[1], rp[2], rp[3]);
           __builtin_amdgcn_sched_barrier(0);           // (keep the load in front of the MFMA chain)
         }
 #pragma unroll
@@ -220,7 +223,8 @@ static int bp_flat_pack(const ConvGeom& g, const WeightMap& wm, const float* w_t
 
 static int flat_k7_tiles(const bp_view* out) { return bp_ceil_div(out->w, TW) * bp_ceil_div(out->h, TH) * out->n; }
 
-// mode-2 statistics are offered where the raw tensor (same grid as `out`) can be read 16 bytes at a time
+// mode-2 statistics are offered where the produced view can be written 16 bytes at a time (the raw tensor, on the same
+// grid, is not known to the query: the kernel reads it either way)
 static size_t bp_flat_stats_workspace(const bp_view* out, int mode) {
   if (mode != 2 || !bp_view_vec4(out)) return 0;
   return (size_t)flat_grid(flat_k7_tiles(out)) * 2 * CO * sizeof(double);
@@ -230,7 +234,7 @@ static int bp_flat_run(const ConvGeom& g, const bp_view* in, const PW& pw, const
                 const bp_view* out, hipStream_t st, const IgemmStatsReq* sr) {
   FlatArgs a{};
   if (sr) {
-    if (sr->mode != 2 || bias || !sr->raw || !bp_view_vec4(sr->raw) || !bp_view_vec4(out) || sr->raw->n != out->n ||
+    if (sr->mode != 2 || bias || !sr->raw || !bp_view_vec4(out) || sr->raw->n != out->n ||
         sr->raw->h != out->h || sr->raw->w != out->w || sr->raw->c != CO)
       return BP_EUNSUPPORTED;
     if (!sr->ws || sr->ws_bytes < bp_flat_stats_workspace(out, 2) || !sr->sums) return BP_EWORKSPACE;
@@ -246,7 +250,8 @@ static int bp_flat_run(const ConvGeom& g, const bp_view* in, const PW& pw, const
   const int64_t ntiles = (int64_t)a.tiles_x * a.tiles_y * a.n;
   if (ntiles > 0x7fffffff) return BP_EUNSUPPORTED;
   const int grid = flat_grid((int)ntiles);
-  if (sr) hipLaunchKernelGGL((flat_k7_kernel<true, true>), dim3(grid), dim3(256), 0, st, a);
+  if (sr && bp_view_vec4(sr->raw)) hipLaunchKernelGGL((flat_k7_kernel<true, true>), dim3(grid), dim3(256), 0, st, a);
+  else if (sr) hipLaunchKernelGGL((flat_k7_kernel<true, true, false>), dim3(grid), dim3(256), 0, st, a);
   else if (bp_view_vec4(out)) hipLaunchKernelGGL((flat_k7_kernel<true, false>), dim3(grid), dim3(256), 0, st, a);
   else hipLaunchKernelGGL((flat_k7_kernel<false, false>), dim3(grid), dim3(256), 0, st, a);
   BP_CHECK_LAUNCH();
@@ -455,7 +460,9 @@ static int flat_t4_tiles(const bp_view* out) {
   return bp_ceil_div(bp_ceil_div(out->w, 2), TTW) * bp_ceil_div(bp_ceil_div(out->h, 2), TTH) * out->n;
 }
 
+// (0 on a produced view the kernel refuses: the query asks what bp_flat_t4_run asks)
 static size_t bp_flat_t4_stats_workspace(const bp_view* out) {
+  if (!bp_view_vec4(out)) return 0;
   return (size_t)flat_grid(flat_t4_tiles(out)) * 2 * TCO * sizeof(double);
 }
 
@@ -717,6 +724,7 @@ static int flat_g4_tiles(const bp_view* out) {
 }
 
 static size_t bp_flat_g4_stats_workspace(const bp_view* out) {
+  if (!bp_view_vec4(out)) return 0;      // (as bp_flat_g4_run)
   return (size_t)flat_g4_grid(flat_g4_tiles(out)) * 2 * out->c * sizeof(double);
 }
 
@@ -981,6 +989,7 @@ static int flat_t64_tiles(const bp_view* out) {
 }
 
 static size_t bp_flat_t64_stats_workspace(const bp_view* out) {
+  if (!bp_view_vec4(out)) return 0;      // (as bp_flat_t64_run)
   return (size_t)flat_g4_grid(flat_t64_tiles(out)) * 2 * out->c * sizeof(double);
 }
 

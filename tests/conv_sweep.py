@@ -478,3 +478,155 @@ def terms(case):
     ho, wo = out_shape(case)
     ty, tdx, tdw, tdb = _conv4(one, np.ones((n, 1, h, w)), np.ones((1, 1, k, k)), None, np.ones((n, 1, ho, wo)))
     return ty * ci, tdx * co, tdw, tdb
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The statistics sweep (test_gpu_stats_sweep.py): the same pinned cases through the convolution + per-channel sums entry
+# points, and STATS_EXTRA for what the sweep's small tensors cannot reach.  The epilogues write one row of partial sums
+# per workgroup; bp_conv_stats_workspace is host arithmetic and tells how many: bytes / (16 C) = rows + folded rows.
+STATS_DIRECT_ROWS = 2048                # csrc/conv_igemm.hip stats_fold_plan: up to here the last stage adds the rows itself
+
+
+def fold_plan(rows):
+    """(folded rows, rows per folded row) of stats_fold_plan: none up to STATS_DIRECT_ROWS, then one per 32 rows up to
+    256 of them."""
+    nfold = 0 if rows <= STATS_DIRECT_ROWS else ((rows + 31) // 32 if rows // 32 < 256 else 256)
+    per = (rows + nfold - 1) // nfold if nfold else 0
+    if nfold:
+        nfold = (rows + per - 1) // per
+    return nfold, per
+
+
+def stats_rows(nbytes, channels, width=None):
+    """Rows of partial sums behind a workspace of `nbytes` for `channels` produced channels (rows of `width` doubles,
+    2 * channels unless given); None if no row count, or more than one (a few sizes next to 8192 rows), gives that size."""
+    width = 2 * channels if width is None else width
+    if nbytes <= 0 or nbytes % (8 * width):
+        return None
+    total = nbytes // (8 * width)
+    found = [rows for rows in range(total, max(total - 257, 0), -1) if rows + fold_plan(rows)[0] == total]
+    return found[0] if len(found) == 1 else None
+
+
+def fold_regime(rows):
+    """Which branch of stats_fold_plan a row count takes."""
+    if rows <= STATS_DIRECT_ROWS:
+        return "direct"
+    return "fold32" if rows // 32 < 256 else "fold256"
+
+
+# (tag, case).  The first field of a tag names what the case is for, the second the direction it is meant in (f: forward,
+# d: data gradient) and the regime / row count test_conv_sweep_ref.py checks against bp_conv_stats_workspace:
+#   rows:<dir>:<regime>   tiled kernel (tile of 8 x 32 phase-grid pixels), rows = phases x images x tiles: many images and
+#                         phases, few pixels -- "direct" 2048 rows exactly, "fold32" rows % 32 != 0, "fold256" rows % 256 != 0
+#   wres:f:walk           the weights-resident persistent kernel with more tiles than workgroups (two tiles each)
+#   wide:<dir>:<C>        256 / 512 produced channels on at most two tiles; 1024: refused (stats_plan admits up to 512; its
+#                         LDS condition refuses no power of two below that in any configuration the dispatcher picks)
+#   walk:f:<family>       the register-resident kernels with more tiles than workgroups (grid-stride walk), the one-channel
+#                         kernel and the activation-backward epilogue (act) past 2048 rows: the fold runs
+#                                 (transposed, cin, cout, k, stride, pad, out_pad, n, h, w)
+STATS_EXTRA = [
+    ("rows:f:direct", (1, 4, 16, 4, 4, 0, 0, 32, 9, 33)),           # 16 phases x 32 images x 4 tiles = 2048
+    ("rows:f:fold32", (1, 4, 16, 4, 4, 0, 0, 43, 3, 70)),           # 16 x 43 x 3 = 2064 = 64.5 x 32
+    ("rows:f:fold256", (1, 4, 16, 4, 4, 0, 0, 171, 2, 65)),         # 16 x 171 x 3 = 8208 = 32 x 256 + 16
+    ("rows:d:direct", (0, 16, 4, 4, 4, 0, 0, 32, 36, 132)),
+    ("rows:d:fold32", (0, 16, 4, 4, 2, 1, 0, 57, 34, 130)),         # 4 phases x 57 x 9 = 2052 = 64 x 32 + 4
+    ("rows:d:fold256", (0, 16, 4, 4, 4, 0, 0, 171, 8, 260)),
+    ("wres:f:walk", (0, 16, 32, 4, 2, 1, 0, 257, 2, 34)),           # 257 x 2 tiles of 8 x 16 = 514 > 512 workgroups
+    ("wide:f:256", (0, 8, 256, 3, 1, 1, 0, 1, 5, 20)),
+    ("wide:f:512", (0, 4, 512, 1, 1, 0, 0, 1, 5, 20)),
+    ("wide:d:256", (0, 256, 16, 3, 1, 1, 0, 1, 5, 20)),
+    ("wide:d:512", (0, 512, 4, 3, 1, 1, 0, 2, 5, 20)),
+    ("wide:f:1024", (0, 4, 1024, 1, 1, 0, 0, 1, 5, 20)),
+    ("walk:f:stem", (0, 3, 16, 5, 1, 2, 0, 1025, 9, 5)),            # 1025 x 2 tiles of 8 x 64 > 2048 workgroups
+    ("walk:f:flat_t4", (1, 32, 16, 4, 2, 1, 0, 257, 1, 17)),        # 257 x 2 phase-grid tiles of 8 x 16 > 512
+    ("walk:f:flat_g4", (0, 32, 64, 4, 2, 1, 0, 129, 2, 34)),        # 129 x 2 tiles of 4 x 16 > 256
+    ("walk:f:flat_t64", (1, 64, 32, 4, 2, 1, 0, 129, 1, 17)),       # 129 x 2 phase-grid tiles of 8 x 16 > 256
+    ("walk:f:enc", (0, 8, 16, 8, 4, 2, 0, 257, 4, 68)),             # 257 x 2 tiles of 4 x 16 > 512
+    ("walk:f:enc0", (0, 2, 8, 4, 2, 1, 0, 1025, 4, 66)),            # 1025 x 2 tiles of 8 x 32 > 2048
+    ("walk:f:tiny", (1, 1, 1, 4, 2, 1, 0, 683, 9, 15)),             # 683 x 3 blocks of 256 pixels = 2049 rows
+    ("walk:d:act", (0, 8, 1, 5, 1, 2, 0, 1025, 17, 5)),             # 1025 x 2 tiles of 16 x 64 = 2050 rows
+]
+
+# Cases at which the statistics sweep once found the library wrong: (tag, case, what was wrong).  Each stays in
+# test_gpu_stats_sweep.py for good (kept apart from REGRESSIONS: the pinned convolution sweep does not change).
+STATS_REGRESSIONS = [
+    # conv_flat.hip's forward kernels 720000 / 730000 / 740000 refuse a produced view that is not 16-byte addressable, but
+    # their workspace queries looked at the tile count alone: a caller that trusted the answer got BP_EUNSUPPORTED
+    ("flat_t4_query_on_odd_view", (1, 32, 16, 4, 2, 1, 0, 2, 5, 7), "workspace > 0 on a view the kernel refuses"),
+    ("flat_g4_query_on_odd_view", (0, 32, 64, 4, 2, 1, 0, 2, 6, 9), "the same for the stride-2 gather 32 -> 64"),
+    ("flat_t64_query_on_odd_view", (1, 64, 32, 4, 2, 1, 0, 2, 5, 7), "the same for the transposed form 64 -> 32"),
+    # conv_flat.hip flat_k7_kernel (710000, data gradient with sums) read raw 16 bytes at a time and refused any other raw
+    # view -- which bp_conv_stats_workspace, not being told about raw, cannot know: it reads such a view with scalar loads now
+    ("flat_k7_raw_view_not_16_byte", (0, 16, 8, 7, 1, 3, 0, 2, 5, 7), "BP_EUNSUPPORTED after a non-zero query"),
+    # bp_conv_stats_workspace answers for the generic bf16 kernel as well where the weights-stationary one runs; the call
+    # checked the latter's smaller need only and ran with a workspace 8 bytes short of the query
+    ("bf16_ws_workspace_short_of_the_query", (1, 128, 64, 4, 2, 1, 0, 2, 7, 16), "BP_OK with workspace_bytes = query - 8"),
+]
+
+
+def stats_cases():
+    """[(tag, case)] of test_gpu_stats_sweep.py: the pinned sweep as it stands, then STATS_EXTRA and STATS_REGRESSIONS."""
+    return tagged_cases() + list(STATS_EXTRA) + [("regression:" + t, c) for t, c, _ in STATS_REGRESSIONS]
+
+
+def counting_inputs(case, index, direction):
+    """Operands that make every value a small integer or half-integer, exactly representable in bf16, so that any
+    order of additions -- fp32 or double -- is exact.
+    direction 0: (x, w): x = 1, no pending activation, w = 1 on the gathered channel index % cin and 0 elsewhere: y is
+       the number of taps inside the image, the same in every produced channel.
+    direction 1: (dy, w, raw, (scale, shift, slope)): dy = 1, w = 1 on the gathered channel index % cout; raw in {1, 2}
+       chequered differently per channel, scale 1, shift -1.5, slope 0.5 (0 on every third channel): t = +-0.5,
+       g in {dx, dx / 2, 0} and every term of the three sums is a multiple of 1/4."""
+    tr, ci, co, k, s, p, op, n, h, w = case
+    wt = np.zeros(weight_shape(case), np.float32)
+    if direction == 0:
+        g = index % ci
+        if tr:
+            wt[g, :] = 1.0
+        else:
+            wt[:, g] = 1.0
+        return np.ones((n, ci, h, w), np.float32), wt
+    g = index % co
+    if tr:
+        wt[:, g] = 1.0
+    else:
+        wt[g, :] = 1.0
+    ho, wo = out_shape(case)
+    c_, y_, x_ = np.arange(ci)[:, None, None], np.arange(h)[None, :, None], np.arange(w)[None, None, :]
+    raw = 1.0 + ((y_ + x_ + c_ + (c_ // 2) * y_ + (c_ // 4) * x_) & 1)
+    raw = np.ascontiguousarray(np.broadcast_to(raw[None], (n, ci, h, w)), dtype=np.float32)
+    slope = np.full(ci, 0.5, np.float32)
+    slope[2::3] = 0.0
+    return np.ones((n, co, ho, wo), np.float32), wt, raw, (np.ones(ci, np.float32), np.full(ci, -1.5, np.float32), slope)
+
+
+def counting_reference(case, direction, T=None):
+    """float64 result of the convolution on counting_inputs: the number of taps behind each element (terms() of one
+    gathered channel), in every produced channel."""
+    tr, ci, co, k, s, p, op, n, h, w = case
+    ty, tdx = (terms(case) if T is None else T)[:2]
+    if direction == 0:
+        return np.ascontiguousarray(np.broadcast_to(ty / ci, (n, co) + ty.shape[2:]))
+    return np.ascontiguousarray(np.broadcast_to(tdx / co, (n, ci) + tdx.shape[2:]))
+
+
+def stats_reference(mode, stored, raw=None, pw=None):
+    """float64 per-channel sums the epilogues promise, from a tensor as stored (float64 values of what the device holds,
+    NCHW), and the magnitudes behind them.  Returns (sums, mags, g): lists of per-channel arrays.
+    mode 1: stored = y: [sum y, sum y^2].
+    mode 2 / 3: stored = dx, raw and pw = (scale, shift, slope) float32: t = fma(raw, scale, shift) rounded once to
+       float32 decides the mask, g = dx where t > 0, else the float32 product dx * slope (include/bp_hip.h):
+       [sum g, sum g raw] and, mode 3, [sum_{t <= 0} dx t]; g is returned for the stored-tensor check of mode 3."""
+    ax = (0, 2, 3)
+    if mode == 1:
+        return [stored.sum(axis=ax), (stored * stored).sum(axis=ax)], [np.abs(stored).sum(axis=ax), (stored * stored).sum(axis=ax)], None
+    scale, shift, slope = (np.asarray(v, np.float32)[None, :, None, None] for v in pw)
+    r64 = np.asarray(raw, np.float64)
+    t = (r64 * scale.astype(np.float64) + shift.astype(np.float64)).astype(np.float32)
+    prod = (stored.astype(np.float32) * slope).astype(np.float64)        # (fp32 multiply: exact inputs, one rounding)
+    g = np.where(t > 0, stored, prod)
+    q = [g, g * r64]
+    if mode == 3:
+        q.append(np.where(t > 0, 0.0, stored * t.astype(np.float64)))
+    return [v.sum(axis=ax) for v in q], [np.abs(v).sum(axis=ax) for v in q], g
