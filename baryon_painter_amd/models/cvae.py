@@ -324,6 +324,9 @@ class _Plan(PlanBase):
             for u in reversed(us):
                 u.prepare_backward()
         if self.hy_one is not None:
+            if self.hy_slot.grad2 is not None:
+                raise NotImplementedError("p_y_z_in.0: a residual block directly behind the concatenation [h_z, h_y] is "
+                                          "not supported with a p_y_in network and L > 1")
             self.hy_slot.ensure_grad()           # (the slice of d/d p_in that bp_repeat_samples_adjoint sums over l)
         for u in reversed(self.y_units):
             u.prepare_backward()

@@ -240,6 +240,7 @@ class Slot:
         four-channel buffer costs every streaming pass over its gradient four times the bytes)."""
         s = Slot(self.buf, self.n, self.h, self.w, c1 - c0, self.coff + c0, pw, parent=self)
         s.dense_grad = dense_grad
+        self.subs = self.subs + [s]
         return s
 
     def pw_struct(self):
@@ -250,6 +251,7 @@ class Slot:
 
     # ---- gradients
     dense_grad = False       # a channel slice that keeps d(loss)/d(slot) in a dense buffer of its own (see sub())
+    subs = []                # the channel slices of this slot (see sub()): their producers run its backward
 
     def ensure_grad(self):
         if self.grad is None:
@@ -282,6 +284,12 @@ class Slot:
         if self.grad2 is not None or self.n_consumers > 2:
             raise NotImplementedError("more than two consumers of one activation")
         self.grad2 = view
+        # a concatenation: the backward of each channel slice is run by the slice's own producer, which reads the
+        # slice's grad2 -- the same channels of the second contribution (a residual block directly behind the
+        # concatenation: without this its skip gradient never reached p_z_in / the recognition branches)
+        for s in self.subs:
+            s.set_grad2_alias(L.View(view.ptr, view.n, view.h, view.w, s.c, view.cstride,
+                                     view.coff + s.coff - self.coff, view.dtype))
 
 
 class PlanBase:
@@ -422,6 +430,7 @@ class ConvUnit:
         self._g_ready = False                # ... and stored g itself (layers without batch-norm)
         self._act_producer = None            # None: undecided; False: separate pass; a ConvUnit: fused
         self._stats_impl = L.IMPL_BF16 if self.bf16 else L.IMPL_MFMA
+        self._took = {}                      # what the last training forward / backward did (``route``)
         if EPILOGUE_FWD and bn is not None and holder.bias is None \
                 and (self.bf16 or (self.out.dt == L.F32 and self._impl("fwd") in (L.IMPL_AUTO, L.IMPL_MFMA))):
             nb = lib.bp_conv_stats_workspace(C.byref(cv), L.PACK_FWD, C.byref(inp.view), C.byref(self.out.view),
@@ -461,6 +470,33 @@ class ConvUnit:
                      "packed": torch.zeros(n_bwd, device=dev, dtype=torch.bfloat16 if self.bf16 else torch.float32),
                      "target": target if target is not None and target.dense_grad else None}
         self.packed_bwd = None
+
+    def route(self):
+        """The decisions the plan compiler took for this layer, for tests and tools (read-only; nothing here steers a
+        launch).  Those that fall at the first training forward / backward are None until then.
+          fwd_stats           batch-norm statistics from the forward convolution's epilogue
+          fwd_finalize_fused  ... and the finalize on that launch (bp_conv_forward_bn)
+          bwd_finalize_fused  the batch-norm backward finalize on the activation-backward launch (bp_act_backward_bn)
+          fused_producer      name of the producer whose backward sums this layer's data gradient took, or False
+          fused_act_producer  name of the producer whose whole activation backward it did, or False
+          sums_by_consumer / act_by_consumer   the same two, seen from the producer
+          restricted          None, or where the data gradient of a channel slice goes: "dense" / "slice"
+          grad2               a second gradient contribution to this layer's output (two heads, a residual skip)
+          g_stored            g = d(loss)/d(batch-norm output) written out (False: recomputed in the apply pass)
+          bf16, in_dtype, out_dtype   bf16 kernels; element types of the slots"""
+        def name(u):
+            return u if u is None or u is False else u.name
+        dt = {L.F32: "f32", L.BF16: "bf16"}
+        sub = self._sub
+        return {"fwd_stats": bool(self.fwd_stats), "fwd_finalize_fused": self._took.get("fwd_bn"),
+                "bwd_finalize_fused": self._took.get("bwd_bn"),
+                "fused_producer": name(self._fused_producer) if self.dx is not None else False,
+                "fused_act_producer": name(self._act_producer) if self.dx is not None else False,
+                "sums_by_consumer": self._took.get("sums_by_consumer"),
+                "act_by_consumer": self._took.get("act_by_consumer"),
+                "restricted": None if sub is None else "dense" if sub["target"] is not None else "slice",
+                "grad2": self.out.grad2 is not None, "g_stored": self._took.get("g_stored"),
+                "bf16": bool(self.bf16), "in_dtype": dt[self.inp.dt], "out_dtype": dt[self.out.dt]}
 
     ws_own = None       # this layer's own split-K workspace when the plan defers the reductions (cvae._Plan)
     ws_name = "ws"      # which of the plan's workspaces this unit's reductions use (branches that run on
@@ -545,6 +581,8 @@ class ConvUnit:
         sync_bn = plan.sync is not None and plan.sync.sync_bn
         peer_fused = sync_bn and fused and self.bn is not None and FUSED_FINALIZE and plan.sync.fused(plan.device)
         fused_bn = fused and self.bn is not None and FUSED_FINALIZE and (not sync_bn or peer_fused)
+        if training and self.bn is not None:
+            self._took["fwd_bn"] = fused_bn
         t0 = plan.prof_begin()
         if fused_bn:
             bn = self.bn
@@ -684,6 +722,7 @@ class ConvUnit:
         d2 = None if dout2 is None else C.byref(dout2)
         nstreams = 2 + (dout2 is not None) + (act_out is not None)       # tensors this pass and the apply pass read
         finalized = False
+        self._took.update(g_stored=g_out is not None, sums_by_consumer=self._sums_ready, act_by_consumer=self._g_ready)
         if self._sums_ready and g_out is None and dout2 is None and act_out is None:
             self._sums_ready = False         # the consumer's data gradient left {sum g, sum g*raw} in self.sums
         elif self._g_ready and bn is None and dout2 is None and act_out is None and g_out is dout:
@@ -724,6 +763,7 @@ class ConvUnit:
             L.check(lib.bp_prelu_slope_grad(L.ptr(self.sums), c, L.ptr(grads[id(self.act_holder.weight)]), st),
                     f"{self.name} prelu grad")
         if bn is not None:
+            self._took["bwd_bn"] = finalized
             pscale = 1.0
             if plan.sync is not None and plan.sync.sync_bn and not finalized:
                 yield self.sums[:2 * c]

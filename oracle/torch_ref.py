@@ -42,17 +42,24 @@ class _StageGradBf16(torch.autograd.Function):
 
 
 def _bf16_layer(bf16, p):
-    """The bf16 policy of baryon_painter_amd.models.cvae._Plan.bf16_unit / bf16_out for the layer with state_dict
-    prefix ``p``: (runs on bf16 matrix cores, output stored as bf16)."""
+    """(runs on bf16 matrix cores, output stored as bf16, input slot stored as bf16) of the layer with state_dict
+    prefix ``p``.  ``bf16`` True: the policy of baryon_painter_amd.models.cvae._Plan.bf16_unit / bf16_out for the fiducial
+    network, by layer name.  A mapping {layer name: (runs on bf16 kernels, output stored as bf16[, input slot is
+    bf16])}: what a compiled plan reports (``ConvUnit.route()``; a residual block under its own name, for its sum) -- any
+    architecture; layers it does not name are fp32."""
     if not bf16:
-        return False, False
+        return False, False, False
     name = p[:-1]
+    if isinstance(bf16, dict):
+        e = tuple(bf16.get(name, (False, False)))
+        return e if len(e) == 3 else (*e, not name.startswith("p_y_z_in.0"))
     head0 = name in ("p_mu_out.0", "p_var_out.0")
+    # the stem's input is an fp32 slot whose gradient stays fp32 (dense one-channel buffer)
     return (name.startswith("p_y_z_in.") or head0 or name in ("p_mu_out.2", "p_var_out.2"),
-            name.startswith("p_y_z_in.") or head0)
+            name.startswith("p_y_z_in.") or head0, not p.startswith("p_y_z_in.0."))
 
 
-def _seq(architecture, x, P, prefix, training, tap=None, bf16=False):
+def _seq(architecture, x, P, prefix, training, tap=None, bf16=False, act_tap=None):
     """``tap`` (debug aid, tools/chain_bisect.py): dict that receives every convolution's raw output under the
     layer's state_dict prefix, with ``retain_grad()`` so that d(loss)/d(raw) can be read after backward.
     ``bf16``: a ROUNDING TWIN of the throughput mode (BASELINE.json configs[3]) -- the graph stays in its own dtype, but
@@ -60,17 +67,20 @@ def _seq(architecture, x, P, prefix, training, tap=None, bf16=False):
     matrix-core layers (staged activation, packed weight), their stored raw outputs and residual sums, and the gradients
     stored in those slots.  Not bit-equal to the kernels (accumulation order, fp32 vs this graph's dtype), but the same
     rounding noise at the same places: what a correct bf16 execution's distance from the float64 truth looks like, per
-    tensor, conditioning included."""
+    tensor, conditioning included.
+    ``act_tap``: dict that receives the INPUT of every relu / leaky relu / prelu (residual tails under the block's prefix
+    + "tail"): how far a case's activations stay from their kinks."""
     for i, layer in enumerate(architecture or []):
         name = layer[0].lower()
         cfg = layer[1] if len(layer) == 2 else None
         p = f"{prefix}{i}."
+        if act_tap is not None and name in ("relu", "leaky relu", "prelu"):
+            act_tap[p] = x
         if name in ("conv", "transp conv"):
             w = P[p + "weight"]
-            mm, stored = _bf16_layer(bf16, p)
+            mm, stored, in_bf16 = _bf16_layer(bf16, p)
             if mm:
-                # the stem's input is an fp32 slot whose gradient stays fp32 (dense one-channel buffer)
-                x = _StoreBf16.apply(x, not p.startswith("p_y_z_in.0."))
+                x = _StoreBf16.apply(x, in_bf16)
                 w = _StoreBf16.apply(w, False)
             if name == "conv":
                 x = F.conv2d(x, w, P.get(p + "bias"), stride=cfg.get("stride", 1), padding=cfg.get("padding", 0))
@@ -107,8 +117,10 @@ def _seq(architecture, x, P, prefix, training, tap=None, bf16=False):
         elif name == "flatten":
             x = x.view(x.size(0), -1)
         elif name == "residual block":
-            h = _seq(cfg[0], x, P, p + "res_block.", training, tap, bf16) + x
+            h = _seq(cfg[0], x, P, p + "res_block.", training, tap, bf16, act_tap) + x
             tail = cfg[1][0]
+            if act_tap is not None and tail is not None:
+                act_tap[p + "tail"] = h
             if tail is None:
                 x = h
             elif tail.lower() == "relu":
@@ -128,9 +140,10 @@ class TorchRefCVAE:
     def __init__(self, architecture, params, buffers=None, dtype=torch.float32, tap=None, bf16=False):
         """params: name -> array/tensor (learnables).  Buffers default to torch's initial values.
         ``dtype`` float64 gives the "true value" of every tensor; ``tap``, ``bf16`` (rounding twin of the throughput
-        mode): see ``_seq``."""
+        mode; True or a mapping from a compiled plan, ``_bf16_layer``): see ``_seq``."""
         self.a = architecture
         self.dtype, self.tap, self.bf16 = dtype, tap, bf16
+        self.act_tap = None                  # (set to a dict before ``forward``: see ``_seq``)
         self.P = {}
         for k, v in params.items():
             t = torch.as_tensor(v, dtype=dtype).clone()
@@ -183,13 +196,15 @@ class TorchRefCVAE:
         x, y = torch.as_tensor(x, dtype=dt), torch.as_tensor(y, dtype=dt)
         aux, eps = torch.as_tensor(aux, dtype=dt), torch.as_tensor(eps, dtype=dt)
         y2 = self._merge(y, aux) if a["aux_label"] else y
-        h = torch.cat([_seq(a["q_x_in"], x, P, "q_x_in.", tr, tap), _seq(a["q_y_in"], y2, P, "q_y_in.", tr, tap)], 1)
-        h = _seq(a["q_x_y_out"], h, P, "q_out.", tr, tap)
+        at = self.act_tap
+        h = torch.cat([_seq(a["q_x_in"], x, P, "q_x_in.", tr, tap, act_tap=at),
+                       _seq(a["q_y_in"], y2, P, "q_y_in.", tr, tap, act_tap=at)], 1)
+        h = _seq(a["q_x_y_out"], h, P, "q_out.", tr, tap, act_tap=at)
         self.z_mu, self.z_log_var = h[:, 0], h[:, 1]
         z = (self.z_mu + eps * (torch.exp(self.z_log_var / 2) + self.min_z_var)).view(-1, *self.dim_z)
         M = x.size(0)
         if "prior_z_y" in a:
-            hp = _seq(a["prior_z_y"], y2, P, "prior_network.", tr, tap)
+            hp = _seq(a["prior_z_y"], y2, P, "prior_network.", tr, tap, act_tap=at)
             p_mu, p_lv = hp[:, 0], hp[:, 1]
         else:
             p_mu = torch.zeros_like(self.z_mu)
@@ -213,13 +228,13 @@ class TorchRefCVAE:
         return self.ELBO
 
     def _P(self, z, y2):
-        a, P, tr, tap = self.a, self.P, self.training, self.tap
-        h_y = _seq(a["p_y_in"], y2, P, "p_y_in.", tr, tap)
-        h_z = _seq(a["p_z_in"], z, P, "p_z_in.", tr, tap)
+        a, P, tr, tap, at = self.a, self.P, self.training, self.tap, self.act_tap
+        h_y = _seq(a["p_y_in"], y2, P, "p_y_in.", tr, tap, act_tap=at)
+        h_z = _seq(a["p_z_in"], z, P, "p_z_in.", tr, tap, act_tap=at)
         b = self.bf16
-        h = _seq(a["p_y_z_in"], torch.cat([h_z, h_y.repeat(self.L, 1, 1, 1)], 1), P, "p_y_z_in.", tr, tap, b)
-        x_mu = _seq(a["p_y_z_out"][0], h, P, "p_mu_out.", tr, tap, b)
-        x_lv = _seq(a["p_y_z_out"][1], h, P, "p_var_out.", tr, tap, b) if self.predict_var else None
+        h = _seq(a["p_y_z_in"], torch.cat([h_z, h_y.repeat(self.L, 1, 1, 1)], 1), P, "p_y_z_in.", tr, tap, b, at)
+        x_mu = _seq(a["p_y_z_out"][0], h, P, "p_mu_out.", tr, tap, b, at)
+        x_lv = _seq(a["p_y_z_out"][1], h, P, "p_var_out.", tr, tap, b, at) if self.predict_var else None
         return x_mu, x_lv
 
     def sample_P(self, y, aux, eps=None, z=None):

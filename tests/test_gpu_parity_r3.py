@@ -21,6 +21,7 @@ from baryon_painter_amd.utils import synthetic as syn
 from golden_util import check, crop_rel_l2, distance, summary_distance
 
 import gpu_util as G
+from plan_units import conv_units as _conv_units
 
 pytestmark = pytest.mark.gpu
 SLOPE = 0.9
@@ -173,25 +174,6 @@ def test_training_script_network_at_512_bf16(gold):
 
 
 # ---------------------------------------------------------------------------------------------- the chain, layer by layer
-def _conv_units(plan):
-    out = []
-
-    def walk(us):
-        for u in us:
-            if hasattr(u, "body"):
-                walk(u.body)
-            else:
-                out.append(u)
-    for us in plan.q_units:
-        walk(us)
-    walk(plan.p_units)
-    for us in plan.g_units:
-        walk(us)
-    walk(plan.mu_units)
-    walk(plan.var_units)
-    return out
-
-
 @pytest.mark.parametrize("size,n", [(128, 2), (512, 2)])
 def test_backward_chain_layer_by_layer(size, n):
     """tools/chain_bisect.py as a test, on the WELL-CONDITIONED (softened) network: every convolution's raw output and

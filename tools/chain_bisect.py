@@ -74,6 +74,8 @@ for u in units(plan):
     gh, g32 = rel(g, t64.grad), rel(t32.grad, t64.grad)
     print(f"{u.name:32s} {r_h:9.2e} {r_32:9.2e} | {gh[0]:9.2e} {gh[1]:9.2e}   {g32[0]:9.2e} {g32[1]:9.2e}   "
           f"{gh[1] / max(g32[1], 1e-30):7.2f}", flush=True)
+    if os.environ.get("BP_BISECT_ROUTES") == "1":        # the decisions the plan compiler took for this layer
+        print("    " + ", ".join(f"{k}={v}" for k, v in u.route().items() if v not in (None, False)))
 
 print("\nparameter gradients: distance from float64 (max/scale), ours vs f32 CPU")
 rows = []
