@@ -171,6 +171,9 @@ SIGNATURES = {
     "bp_loglik_workspace": (C.c_size_t, [C.POINTER(Loglik)]),
     "bp_loglik_forward": (C.c_int, [C.POINTER(Loglik), _P, _VP, _VP, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "bp_loglik_backward": (C.c_int, [C.POINTER(Loglik), _P, _VP, _VP, _P, _VP, _VP, _P]),
+    "bp_loglik_samples_workspace": (C.c_size_t, [C.POINTER(Loglik)]),
+    "bp_loglik_samples": (C.c_int, [C.POINTER(Loglik), _P, _VP, _VP, _P, _P, C.c_size_t, _P]),
+    "bp_posterior_score": (C.c_int, [C.POINTER(Latent), _P, _P, _P, C.c_int32, _P, _P, _P]),
     "bp_unary_forward": (C.c_int, [_VP, _PWP, C.c_int32, _VP, _P]),
     "bp_unary_backward": (C.c_int, [_VP, _VP, _VP, C.c_int32, _VP, _P]),
     "bp_bce_logits": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_float, _P, _P, C.c_size_t, _P]),

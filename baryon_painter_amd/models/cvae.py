@@ -1103,6 +1103,120 @@ class CVAE(torch.nn.Module):
         g["graph"].replay()
         return g["out"].clone()
 
+    # ---- scoring on tiles whose truth is known
+    def _score_plan(self, n, K, what):
+        """The plan of ``score`` / ``reconstruct``: recognition and prior networks over n tiles, the generator over n K
+        samples (l-major), no gradients; cached per (n, K) beside the paint plans.  Its ``score_ws`` / ``score_ll``
+        are the workspace and the (K n, cx) float64 result of ``bp_loglik_samples``."""
+        if self.training:
+            raise RuntimeError(f"{what} is an eval-mode path (batch statistics would couple the tiles): call "
+                               "model.train(False) first")
+        key = ("score", n, int(K))
+        plan = self._paint_plans.get(key)
+        if plan is None:
+            plan = _Plan(self, n, False, True, samples=int(K))
+            for name, slot in (("p_mu_out", plan.mu_head), ("p_var_out", plan.var_head)):
+                if slot is not None and slot.view.dtype != L.F32:
+                    raise NotImplementedError(f"{what}: the head {name} ends in a bf16 slot; the score kernels read "
+                                              "fp32 heads")
+            nbytes = self._lib.bp_loglik_samples_workspace(C.byref(plan.ll))
+            plan.score_ws = torch.zeros(max(nbytes, 8) // 8, device=self.device, dtype=torch.float64)
+            plan.score_ll = torch.zeros((int(K) * n, self.dim_x[0]), device=self.device, dtype=torch.float64)
+            self._paint_plans[key] = plan
+        return plan
+
+    def _encode_decode(self, plan, eps):
+        """The plan's loaded x, y -> Q and the prior -> z = z_mu + eps s(z_log_var) -> both heads, all with running
+        statistics."""
+        for us in plan.q_units:
+            for u in us:
+                u.forward(False)
+        plan.run_prior(False)
+        plan.run_latent(eps, use_q=True)
+        plan.run_generator(False)
+
+    def score(self, x, y, aux_label=None, draws=1, eps=None, return_log_w=False):
+        """Score the painter on tiles whose truth ``x`` is known: the per-tile evidence lower bound in EVAL mode
+        (running statistics, as every paint path), tightened by K = ``draws`` (1 ... 64) importance-weighted draws from
+        the recognition network.  Returns an (n, 5) float64 device tensor with the columns
+          0 ``bound``           logsumexp_k(log w_k) - log K       (the K-draw bound; K = 1: the ELBO)
+          1 ``elbo``            mean_k log w_k
+          2 ``log_likelihood``  mean_k sum_c log p(x | z_k, y)[c]  (a density: -log(2 pi)/2 per pixel)
+          3 ``kl``              -mean_k (log p(z_k | y) - log q(z_k | x, y)), a Monte-Carlo estimate of KL(q || p)
+          4 ``ess``             effective sample size of the weights, in [1, K]
+        with log w_k = log p(x | z_k, y) + log p(z_k | y) - log q(z_k | x, y) and z_k = z_mu + eps_k (exp(z_log_var / 2)
+        + min_z_var), the sampler's own standard deviation; a model without prior network has the prior ``sample_P``
+        draws from, N(0, (1 + min_z_var)^2).  ``alpha_var``, ``beta_KL`` and ``likelihood_scaling`` do not enter: this
+        scores the generative model, not the training objective.  Values are nats in NETWORK units: they compare painters
+        that share a transform and carry no Jacobian to physical units.
+
+        ``eps``: (K, n, *dim_z) standard normals, or None for ``_draw_eps(n, K)``.  ``return_log_w``: also the (K, n)
+        float64 log-weights.  Runs eagerly (``bp_loglik_samples`` + ``bp_posterior_score`` behind the plan's launches)."""
+        K = PG.check_draws(draws)
+        with torch.no_grad():
+            x = torch.as_tensor(x, device=self.device, dtype=torch.float32)
+            y = torch.as_tensor(y, device=self.device, dtype=torch.float32)
+            self._check_inputs(x, y)
+            n = y.shape[0]
+            aux = self._aux(aux_label, n)
+            if eps is None:
+                eps = self._draw_eps(n, K)
+            else:
+                eps = torch.as_tensor(eps, device=self.device, dtype=torch.float32)
+                if tuple(eps.shape) != (K, n, *self.dim_z):
+                    raise ValueError(f"eps has shape {tuple(eps.shape)}, expected {(K, n, *self.dim_z)}")
+            plan = self._score_plan(n, K, "score")
+            plan.load_inputs(y, aux, x, False)
+            return self._score_loaded(plan, eps, return_log_w)
+
+    def _score_loaded(self, plan, eps, return_log_w=False):
+        """``score`` behind ``load_inputs``: y (with the aux planes) and x are in the plan (``CVAEPainter.score`` puts
+        them there with the device transforms); ``eps`` is a (K, n, *dim_z) float32 device tensor."""
+        n, K = plan.n, plan.L
+        with torch.no_grad():
+            self._encode_decode(plan, eps)
+            lib, st = self._lib, _stream()
+            L.check(lib.bp_loglik_samples(C.byref(plan.ll), L.ptr(plan.x_nchw), C.byref(plan.mu_head.view),
+                                          None if plan.var_head is None else C.byref(plan.var_head.view),
+                                          L.ptr(plan.score_ll), L.ptr(plan.score_ws), plan.score_ws.numel() * 8, st),
+                    "per-sample log-likelihood")
+            out = torch.empty((n, 5), device=self.device, dtype=torch.float64)
+            log_w = torch.empty((K, n), device=self.device, dtype=torch.float64) if return_log_w else None
+            L.check(lib.bp_posterior_score(C.byref(plan.lat), L.ptr(plan.stats4), L.ptr(plan.eps), L.ptr(plan.score_ll),
+                                           self.dim_x[0], L.ptr(out), L.ptr(log_w), st), "posterior score")
+            return (out, log_w) if return_log_w else out
+
+    def reconstruct(self, x, y, aux_label=None, eps=None):
+        """Encode the truth, decode it: x_mu (n, cx, H, W) float32 in network units for z = z_mu + eps s(z_log_var) from
+        the recognition network -- what the generator can express of ``x``.  ``eps`` (1, n, *dim_z) or (n, *dim_z); None
+        is the posterior mean (normals of zero: z = z_mu exactly).  Eval mode only."""
+        with torch.no_grad():
+            x = torch.as_tensor(x, device=self.device, dtype=torch.float32)
+            y = torch.as_tensor(y, device=self.device, dtype=torch.float32)
+            self._check_inputs(x, y)
+            n = y.shape[0]
+            aux = self._aux(aux_label, n)
+            if eps is None:
+                eps = torch.zeros((1, n, *self.dim_z), device=self.device)
+            else:
+                eps = torch.as_tensor(eps, device=self.device, dtype=torch.float32)
+                if tuple(eps.shape) not in ((1, n, *self.dim_z), (n, *self.dim_z)):
+                    raise ValueError(f"eps has shape {tuple(eps.shape)}, expected {(1, n, *self.dim_z)}")
+                eps = eps.reshape(1, n, *self.dim_z)
+            plan = self._score_plan(n, 1, "reconstruct")
+            plan.load_inputs(y, aux, x, False)
+            return self._reconstruct_loaded(plan, eps)
+
+    def _reconstruct_loaded(self, plan, eps):
+        """``reconstruct`` behind ``load_inputs`` (see ``_score_loaded``); ``eps`` (1, n, *dim_z)."""
+        n = plan.n
+        with torch.no_grad():
+            self._encode_decode(plan, eps)
+            cx, H, W = self.dim_x
+            mu = torch.empty((n, cx, H, W), device=self.device)
+            self._head_to_nchw(plan.mu_head, plan.mu_softplus, mu)
+            return mu
+
     def paint_graph(self, n, scales=None, modes=None, pixel_noise=False, draws=None, return_draws=False):
         """The captured paint pipeline for batches of ``n`` RAW tiles (configs[4]).  Returns a dict with ``slots``: TWO
         input / parameter / output buffer sets, each with its own captured graph over the SAME launch plans, so that a

@@ -29,6 +29,9 @@ except ImportError:                     # pragma: no cover
     _pickler = pickle
 
 
+SCORE_KEYS = ("bound", "elbo", "log_likelihood", "kl", "ess")      # the columns of ``CVAE.score``, in order
+
+
 class Painter:
     """Abstract base class for a baryon painter (painter.py:16-31)."""
 
@@ -608,9 +611,182 @@ class CVAEPainter(Painter):
             return False
         return True
 
+    # ---- scoring on held-out tiles -----------------------------------------------------------------
+    def _score_parameters(self, zs):
+        """(input mode, label modes, input records (n, 4), label records (F, n, 4)) of the FORWARD transforms of the
+        input field and of every label field, for tiles at redshifts ``zs`` -- what ``score`` / ``reconstruct`` load
+        raw tiles with on the device.  NotImplementedError, without side effects, for a painter that has no such form: a
+        split-scale (multi-scale) painter, a chain ``data_transforms.device_shift_log`` does not read, or a model whose
+        channels are not one per field."""
+        from .utils import data_transforms as T
+        tr = self.transform
+        func = None if tr is None else getattr(tr, "func", None)
+        if tr is None:
+            raise NotImplementedError("score needs the painter's transforms (transform=None has no device form)")
+        if T.has_split_scale(func) or T.has_split_scale(getattr(self.inverse_transform, "func", None)):
+            raise NotImplementedError("score has no device form for a split-scale painter: transform on the host and "
+                                      "call model.score")
+        F = len(self.label_fields)
+        if F < 1 or self.model.dim_y[0] != 1 or self.model.dim_x[0] != F:
+            raise NotImplementedError(f"score needs one channel per field, the model has dim_y {self.model.dim_y} and "
+                                      f"dim_x {self.model.dim_x} for {F} label fields")
+        rc_in = T.device_shift_log(func, 0, self.input_field)
+        rcs = [T.device_shift_log(func, 0, f) for f in self.label_fields]
+        rec_x = np.stack([rc.records(tr.stats[f], zs) for rc, f in zip(rcs, self.label_fields)])
+        return rc_in.mode, [rc.mode for rc in rcs], rc_in.records(tr.stats[self.input_field], zs), rec_x
+
+    def can_score(self, z=0.0):
+        """Whether ``score`` / ``reconstruct`` have a device form for this painter, WITHOUT side effects (as
+        ``can_paint_stream``): nothing is built, no random number is drawn."""
+        try:
+            self._score_parameters(np.atleast_1d(np.asarray(z, dtype=np.float64))[:1])
+        except NotImplementedError:
+            return False
+        return True
+
+    def _score_batches(self, inputs, truths, z, tile_ids, seed, per_batch, K, lo, hi, run):
+        """Batches of ``per_batch`` tiles of [lo, hi) through ``run(plan, eps or None, a, b)``: per batch ONE pinned
+        upload (raw tiles, raw truths, records, redshifts, tile ids and the seed in one block), the forward transforms on
+        the device (``bp_paint_load_mode`` with each field's own record, the truths into their channel slices of the
+        plan's ``x_in`` slot), and -- where ``K`` is not None -- the normals of counter (g, k, tile id) under ``seed``."""
+        import ctypes as C
+        from . import _lib as L
+        from .models.graph import _stream
+        model = self.model
+        dev, lib = model.device, model._lib
+        H, W = self._tile_shape()
+        F = len(self.label_fields)
+        zs = np.broadcast_to(np.asarray(z, dtype=np.float64), (len(inputs),))
+        ids = np.arange(len(inputs), dtype=np.int64) if tile_ids is None else np.asarray(tile_ids, dtype=np.int64)
+        mode_in, modes_x, _, _ = self._score_parameters(zs[:1])
+        per_tile = int(np.prod(model.dim_z))
+        caux = model.n_aux if model.use_aux_label else 0
+        blocks = self.__dict__.setdefault("_score_buffers", {})     # (page-locking costs tens of milliseconds: kept)
+        with torch.no_grad():
+            for a in range(lo, hi, per_batch):
+                b = min(a + per_batch, hi)
+                n = b - a
+                _, _, rec_in, rec_x = self._score_parameters(zs[a:b])
+                parts = [("raw", np.float32, (n, 1, H, W)), ("truth", np.float32, (F, n, H, W)),
+                         ("rec_in", np.float64, (n, 4)), ("rec_x", np.float64, (F, n, 4)), ("ids", np.int64, (n,)),
+                         ("seed", np.int64, (1,)), ("aux", np.float32, (n, 1))]
+                if (n, F, H, W) not in blocks:
+                    off, layout = 0, {}
+                    for name, dt, shape in parts:
+                        layout[name] = (off, dt, shape)
+                        off += -(-int(np.prod(shape)) * np.dtype(dt).itemsize // 16) * 16
+                    host = torch.zeros(off, dtype=torch.uint8).pin_memory()
+                    blocks[(n, F, H, W)] = (layout, host, torch.zeros(off, dtype=torch.uint8, device=dev),
+                                            torch.zeros((n, 1, H, W), device=dev))
+                layout, host, block, y_t = blocks[(n, F, H, W)]
+                hv = host.numpy()
+
+                def field(buf, name, layout=layout):
+                    """The typed view of one part of the block: of the host mirror (NumPy) or of the device copy."""
+                    off, dt, shape = layout[name]
+                    size = int(np.prod(shape)) * np.dtype(dt).itemsize
+                    if isinstance(buf, torch.Tensor):
+                        return buf[off:off + size].view(getattr(torch, np.dtype(dt).name)).view(shape)
+                    return buf[off:off + size].view(dt).reshape(shape)
+                field(hv, "raw")[:, 0] = np.asarray(inputs[a:b], dtype=np.float32)
+                tr_ab = np.asarray(truths[a:b], dtype=np.float32).reshape(n, F, H, W)
+                field(hv, "truth")[:] = tr_ab.transpose(1, 0, 2, 3)
+                field(hv, "rec_in")[:] = rec_in
+                field(hv, "rec_x")[:] = rec_x
+                field(hv, "ids")[:] = ids[a:b]
+                field(hv, "seed")[0] = PG.seed_word(seed)
+                field(hv, "aux")[:, 0] = zs[a:b]
+                block.copy_(host, non_blocking=True)
+                plan = model._score_plan(n, 1 if K is None else K, "score")
+                st = _stream()
+                L.check(lib.bp_paint_load_mode(mode_in, L.ptr(field(block, "raw")), 1, L.ptr(field(block, "rec_in")), None,
+                                               0, C.byref(L.view(y_t, n, H, W, 1)), st), "load y")
+                plan.load_inputs(y_t, field(block, "aux") if caux else None, None, False)
+                truth_d, rec_d = field(block, "truth"), field(block, "rec_x")
+                for j in range(F):
+                    v = L.view(plan.x_in.buf, n, H, W, 1, plan.x_in.cstride, plan.x_in.coff + j)
+                    L.check(lib.bp_paint_load_mode(modes_x[j], L.ptr(truth_d[j]), 1, L.ptr(rec_d[j]), None, 0, C.byref(v),
+                                                   st), "load x")
+                if plan.x_nchw.data_ptr() != plan.x_in.buf.data_ptr():
+                    L.check(lib.bp_view_to_nchw(C.byref(plan.x_in.view), None, 0, L.ptr(plan.x_nchw), st), "x layout")
+                eps = None
+                if K is not None:
+                    eps = torch.empty((K, n, *model.dim_z), device=dev)
+                    L.check(lib.bp_philox_normal_dev(L.ptr(field(block, "seed")), L.ptr(field(block, "ids")), n, K,
+                                                     per_tile, L.ptr(eps), st), "philox")
+                run(plan, eps, a, b)
+                torch.cuda.current_stream(dev).synchronize()      # (the pinned block is rewritten by the next batch)
+
+    def _score_prologue(self, inputs, truths, z, rank, world_size):
+        """Shapes checked (ValueError), the device form checked (NotImplementedError), the model in eval mode; returns
+        this rank's share [lo, hi) of the N tiles.  Nothing is built, no random number is drawn."""
+        H, W = self._tile_shape()
+        F = len(self.label_fields)
+        N = len(inputs)
+        self._score_parameters(np.atleast_1d(np.asarray(z, dtype=np.float64))[:1])
+        if tuple(np.shape(inputs)[1:]) != (H, W):
+            raise ValueError(self._shape_mismatch(tuple(np.shape(inputs))))
+        if tuple(np.shape(truths)) not in ([(N, F, H, W)] + ([(N, H, W)] if F == 1 else [])):
+            raise ValueError(f"truths have shape {tuple(np.shape(truths))}, expected {(N, F, H, W)}")
+        self.model.train(False)
+        per = (N + world_size - 1) // world_size
+        return N, min(rank * per, N), min((rank + 1) * per, N)
+
+    def score(self, inputs, truths, z, draws=16, batch_size=64, tile_ids=None, seed=0, rank=0, world_size=1):
+        """Score this painter on held-out tiles: raw dark-matter tiles ``inputs`` (N, H, W) and the raw truth of every
+        label field, ``truths`` (N, H, W) or (N, F, H, W), at redshifts ``z`` -> a dict of float64 arrays (N,) with the
+        keys ``bound``, ``elbo``, ``log_likelihood``, ``kl`` and ``ess`` (``CVAE.score``'s columns: the per-tile evidence
+        lower bound in eval mode, tightened by ``draws`` = K importance-weighted draws from the recognition network).
+        Values are nats in NETWORK units -- they compare painters that share a transform and carry no Jacobian to
+        physical units.
+
+        ``batch_size`` counts generator samples, as in ``paint_ensemble``: a batch carries ``batch_size // K`` tiles and K
+        must divide it (ValueError).  Draw k of tile id t (``tile_ids``, default 0 ... N - 1) uses the Philox counter
+        (g, k, t) under ``seed``, so nothing depends on batches or ranks; ``rank`` / ``world_size`` shard the tiles as in
+        ``paint_stream`` (the result is then (dict, (lo, hi))).  The forward transforms run on the device, each field
+        with its own record (any of the six range compressions); a split-scale painter or a chain without a device form
+        raises NotImplementedError before any device work (``can_score``): transform on the host and call
+        ``model.score``."""
+        K = PG.check_draws(draws)
+        B = int(batch_size)
+        if B < K or B % K:
+            raise ValueError(f"batch_size counts generator samples: {K} draws per tile must divide it, got {batch_size}")
+        N, lo, hi = self._score_prologue(inputs, truths, z, rank, world_size)
+        out = np.zeros((hi - lo, 5), np.float64)
+
+        def run(plan, eps, a, b):
+            out[a - lo:b - lo] = self.model._score_loaded(plan, eps).cpu().numpy()
+        self._score_batches(inputs, truths, z, tile_ids, seed, B // K, K, lo, hi, run)
+        result = {k: np.ascontiguousarray(out[:, j]) for j, k in enumerate(SCORE_KEYS)}
+        return (result, (lo, hi)) if world_size > 1 else result
+
+    def reconstruct(self, inputs, truths, z, batch_size=64, sample=False, seed=0, tile_ids=None):
+        """Encode the truth, decode it, in physical units: what the generator can express of ``truths`` -- tiles shaped as
+        ``paint_batch`` returns them.  Inputs and the device loads are ``score``'s; the head (``model.reconstruct``) goes
+        through the inverse transform exactly as ``paint_batch`` applies it.  ``sample=False``: the posterior mean,
+        z = z_mu; ``sample=True``: one draw, draw 0 of the Philox counter (g, 0, tile id) under ``seed``."""
+        N, lo, hi = self._score_prologue(inputs, truths, z, 0, 1)
+        zs = np.broadcast_to(np.asarray(z, dtype=np.float64), (N,))
+        out = []
+
+        def run(plan, eps, a, b):
+            if eps is None:
+                eps = torch.zeros((1, plan.n, *self.model.dim_z), device=self.model.device)
+            pred = self.model._reconstruct_loaded(plan, eps).cpu().numpy()
+            if self.inverse_transform is not None and len(self.label_fields) > 1:
+                pred = np.stack([self._inverse_fields(p, float(zz)) for p, zz in zip(pred, zs[a:b])])
+            elif self.inverse_transform is not None:
+                pred = np.stack([self.inverse_transform(p[None] if p.shape[0] == 1 else p, field=self.label_fields[0],
+                                                        z=float(zz)) for p, zz in zip(pred, zs[a:b])])
+            out.append(pred)
+        self._score_batches(inputs, truths, z, tile_ids, seed, int(batch_size), 1 if sample else None, lo, hi, run)
+        return np.concatenate(out, axis=0)
+
     def release_paint_buffers(self):
-        """``Painter.release_paint_buffers``, and a multi-scale pipeline's pyramid scratch."""
+        """``Painter.release_paint_buffers``, a multi-scale pipeline's pyramid scratch, and the pinned and device blocks
+        ``score`` / ``reconstruct`` keep per batch shape."""
         super().release_paint_buffers()
+        self.__dict__.pop("_score_buffers", None)
         if hasattr(self.model, "release_scale_buffers"):
             self.model.release_scale_buffers()
 

@@ -629,6 +629,42 @@ int bp_loglik_backward(const bp_loglik* ll, const float* x_nchw, const bp_view* 
                        const bp_view* var_raw, const float* seed, const bp_view* d_mu_raw,
                        const bp_view* d_var_raw, void* stream);
 
+/* ---- scoring a painter on held-out tiles (CVAE.score, CVAEPainter.score) ------ */
+/* Per-SAMPLE Gaussian log-density of the truth under the two heads, in float64:
+ *   out[(l n + m) c + ch] = sum_{y,x} [ -log(2 pi)/2 - lv/2 - (x - x_mu)^2 exp(-lv) / 2 ]
+ * for sample l n + m of mu_raw / var_raw against x[m].  x_mu is the float32 value the paint paths read from the mean
+ * head (softplus_f(raw) with ll->mu_softplus, bp_view_to_nchw's device function), lv the variance head's output, 0 for
+ * var_raw == NULL; every other operation is float64 without contraction: d = (double) x - (double) x_mu,
+ * term = (c0 - 0.5 lv) - (0.5 (d d)) exp(-lv).  Only n, L, c, h, w and mu_softplus of `ll` are read.
+ *   x_nchw : (n, c, H, W) float32;   mu_raw, var_raw : (L n, H, W, c) fp32 views, any cstride / coff
+ *   out    : (L n, c) float64;       workspace : bp_loglik_samples_workspace(ll) bytes
+ * One streaming launch over samples x chunks of 2048 pixels plus one small launch that adds a sample's chunk sums in
+ * a fixed order; x, mu and var are each read once, 16 bytes per lane where c == cstride == 1, H W % 4 == 0 and the
+ * pointers are 16-byte aligned, one float per access otherwise.  How a sample's pixels are split into partial sums
+ * depends on (h, w, c) alone: no atomics, the same inputs give the same bits, and a sample's sum has the same bits
+ * whatever else is in the launch.  Non-finite values get no special handling: a NaN in one sample is that sample's.
+ * Before anything is written: BP_EINVAL for a null pointer other than var_raw, a malformed view, n, L, c, h or w < 1,
+ * mu_raw->n != n L or view shapes that disagree with `ll`; then BP_EUNSUPPORTED for a bf16 view, L > 64 or
+ * n L H W c >= 2^31; then BP_EWORKSPACE.  bp_loglik_samples_workspace returns 0 for a descriptor that would be refused. */
+size_t bp_loglik_samples_workspace(const bp_loglik* ll);
+int bp_loglik_samples(const bp_loglik* ll, const float* x_nchw, const bp_view* mu_raw, const bp_view* var_raw,
+                      double* out, void* workspace, size_t workspace_bytes, void* stream);
+/* The score of each tile from its K = lt->L draws: with s(lv) = exp(lv / 2) + min_z_var in float64 from the float32
+ * stats4 planes of bp_latent_forward and eps (L, n, zc, zh, zw), for tile m and draw k, over the latent elements j
+ * (64 at a time by a fixed shuffle tree, the groups in ascending order),
+ *   r_k     = sum_j [ (log s_q - log s_p) + (eps^2/2 - ((z_mu + eps s_q - p_mu) / s_p)^2 / 2) ]
+ *   log w_k = ((loglik[(k n + m) c + 0] + ...) + loglik[.. + c - 1]) + r_k
+ *   score[m] = { logsumexp_k(log w_k) - log K,  mean_k log w_k,  mean_k sum_c loglik,  -mean_k r_k,
+ *                exp(2 lse(log w) - lse(2 log w)) }          (bound, elbo, log_likelihood, kl, ess)
+ * logsumexp subtracts the maximum; a tile whose log w_k are all -inf gets bound = -inf and ess = NaN; K = 1 gives
+ * bound == elbo bit for bit and ess == 1.  A model without prior network passes zero prior planes in stats4 (what
+ * bp_latent_forward writes), so s_p = 1 + min_z_var.  log_w: NULL or (L, n), receives every log w_k.
+ * One launch, one wave per tile, lane k takes draws k (no atomics, no workspace, no host synchronisation).  Before
+ * anything is written: BP_EINVAL for a null pointer other than log_w or n, L, c or a latent extent < 1; then
+ * BP_EUNSUPPORTED for L > 64. */
+int bp_posterior_score(const bp_latent* lt, const float* stats4, const float* eps, const double* loglik, int32_t c,
+                       double* score, double* log_w, void* stream);
+
 /* ---- GAN heads (the CGAN of trained_models/README.md:95-144; no code in the reference) ------ */
 /* out = f(act(in)), kind 0 identity, 1 tanh (generator output, README.md:128), 2 sigmoid, 3 softplus.  Also the
  * saturating layers of the CVAE's layer language (models/utils.py:68-73, 140-145; graph.UnaryUnit).  With
