@@ -14,6 +14,9 @@ BP_EINVAL, BP_EUNSUPPORTED, BP_ELAUNCH, BP_EWORKSPACE = -1, -2, -3, -4
 IMPL_AUTO, IMPL_DIRECT, IMPL_MFMA, IMPL_BF16 = 0, 1, 2, 3
 IMPL_SHARED = 0x100
 IMPL_DEFER = 0x200
+# `family` of bp_conv_backward_weight_plan, in the order of the enum in include/bp_hip.h
+WGRAD_FAMILIES = ("ws_f32", "enc", "thin_c1", "thin_cy1", "small", "small_chunked", "tiles", "tiles_dma", "general", "stem",
+                  "flat", "flat_s2", "direct", "bf16_tiled", "bf16_wf", "bf16_sf", "bf16_wh", "ws_bf16")
 PACK_FWD, PACK_BWD = 0, 1
 F32, BF16 = 0, 1
 F64 = 2            # bp_plane_cut's float64 planes
@@ -94,6 +97,7 @@ SIGNATURES = {
     "bp_conv_backward_data_act": (C.c_int, [_CP, _VP, _P, _VP, _VP, _PWP, _P, _P, C.c_size_t, _P]),
     "bp_conv_backward_weight_workspace": (C.c_size_t, [_CP, _VP, _VP]),
     "bp_conv_backward_weight": (C.c_int, [_CP, _VP, _PWP, _VP, _P, _P, _P, C.c_size_t, C.c_int, _P]),
+    "bp_conv_backward_weight_plan": (C.c_int, [_CP, _VP, _VP, C.c_int, C.POINTER(C.c_int32)]),
     "bp_wgrad_defer_begin": (C.c_int, []),
     "bp_wgrad_defer_flush": (C.c_int, [C.c_int, _P]),
     "bp_peer_handle_bytes": (C.c_int, []),

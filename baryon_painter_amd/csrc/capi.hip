@@ -240,13 +240,15 @@ size_t bp_conv_backward_weight_workspace(const bp_conv* cv, const bp_view* x, co
   return align256(main) + align256(bp_channel_sums_workspace(dy)) + align256((size_t)2 * dy->c * sizeof(double));
 }
 
-int bp_conv_backward_weight(const bp_conv* cv, const bp_view* x, const bp_pointwise* x_pw, const bp_view* dy,
-                            float* dw_torch, float* dbias, void* workspace, size_t workspace_bytes, int impl,
-                            void* stream) {
+// One walk for the call and for bp_conv_backward_weight_plan (`plan`: nothing is launched, no workspace is asked for;
+// plan = {family, nsplit, cxp, cyp} of the kernel the call would run).
+static int backward_weight(const bp_conv* cv, const bp_view* x, const bp_pointwise* x_pw, const bp_view* dy,
+                           float* dw_torch, float* dbias, void* workspace, size_t workspace_bytes, int impl,
+                           void* stream, int32_t* plan) {
   const bool shared = (impl & BP_IMPL_SHARED) != 0;
-  const WgradPrivateWs priv((impl & BP_IMPL_DEFER) != 0);      // (this call's reduction may wait for the flush)
+  const WgradPrivateWs priv(!plan && (impl & BP_IMPL_DEFER) != 0);      // (this call's reduction may wait for the flush)
   impl &= ~(BP_IMPL_SHARED | BP_IMPL_DEFER);
-  if (!conv_ok(cv) || !shapes_ok(cv, x, dy, impl == BP_IMPL_BF16) || !dw_torch) return BP_EINVAL;
+  if (!conv_ok(cv) || !shapes_ok(cv, x, dy, impl == BP_IMPL_BF16) || (!plan && !dw_torch)) return BP_EINVAL;
   const bp_view* X = cv->transposed ? dy : x;
   const bp_view* Y = cv->transposed ? x : dy;
   const PW none{nullptr, nullptr, nullptr};
@@ -257,22 +259,25 @@ int bp_conv_backward_weight(const bp_conv* cv, const bp_view* x, const bp_pointw
     if (dbias) return BP_EUNSUPPORTED;       // (bias gradients: the fp32 path; the CVAE's convolutions have none)
     const size_t need = bp_wgrad_bf16_workspace(cv, X, Y);
     if (!need) return BP_EUNSUPPORTED;
-    if (!workspace || workspace_bytes < need) return BP_EWORKSPACE;
-    return bp_wgrad_bf16_run(cv, X, pwx, Y, pwy, dw_torch, workspace, workspace_bytes, st);
+    if (!plan && (!workspace || workspace_bytes < need)) return BP_EWORKSPACE;
+    return bp_wgrad_bf16_run(cv, X, pwx, Y, pwy, dw_torch, workspace, workspace_bytes, st, plan);
   }
   const size_t ws_main = align256(bp_wgrad_mfma_workspace(cv, X, Y));
   if (impl == BP_IMPL_AUTO) impl = ws_main ? BP_IMPL_MFMA : BP_IMPL_DIRECT;
-  if (impl == BP_IMPL_MFMA || dbias) {
+  if (!plan && (impl == BP_IMPL_MFMA || dbias)) {
     if (!workspace || workspace_bytes < bp_conv_backward_weight_workspace(cv, x, dy)) return BP_EWORKSPACE;
   }
   int rc;
   if (impl == BP_IMPL_MFMA) {
     if (!ws_main) return BP_EUNSUPPORTED;
-    rc = bp_wgrad_mfma(cv, X, pwx, Y, pwy, dw_torch, workspace, ws_main, st, shared);
+    rc = bp_wgrad_mfma(cv, X, pwx, Y, pwy, dw_torch, workspace, ws_main, st, shared, plan);
+  } else if (plan) {
+    plan[0] = BP_WG_DIRECT; plan[1] = plan[2] = plan[3] = 0;
+    rc = BP_OK;
   } else {
     rc = bp_direct_wgrad(cv, X, pwx, Y, pwy, dw_torch, st);
   }
-  if (rc != BP_OK) return rc;
+  if (rc != BP_OK || plan) return rc;
   if (dbias) {
     char* base = reinterpret_cast<char*>(workspace) + ws_main;
     const size_t ws_sums = align256(bp_channel_sums_workspace(dy));
@@ -281,6 +286,20 @@ int bp_conv_backward_weight(const bp_conv* cv, const bp_view* x, const bp_pointw
     if (rc != BP_OK) return rc;
     rc = bp_sums_to_float(sums, dy->c, dbias, stream);
   }
+  return rc;
+}
+
+int bp_conv_backward_weight(const bp_conv* cv, const bp_view* x, const bp_pointwise* x_pw, const bp_view* dy,
+                            float* dw_torch, float* dbias, void* workspace, size_t workspace_bytes, int impl,
+                            void* stream) {
+  return backward_weight(cv, x, x_pw, dy, dw_torch, dbias, workspace, workspace_bytes, impl, stream, nullptr);
+}
+
+int bp_conv_backward_weight_plan(const bp_conv* cv, const bp_view* x, const bp_view* dy, int impl, int32_t out[4]) {
+  if (!out) return BP_EINVAL;
+  out[0] = -1; out[1] = out[2] = out[3] = 0;
+  const int rc = backward_weight(cv, x, nullptr, dy, nullptr, nullptr, nullptr, 0, impl, nullptr, out);
+  if (rc != BP_OK) { out[0] = -1; out[1] = out[2] = out[3] = 0; }
   return rc;
 }
 

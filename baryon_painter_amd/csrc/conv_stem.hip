@@ -387,6 +387,8 @@ bool bp_stem_wgrad_ok(const bp_conv* cv, const bp_view* X, const bp_view* Y, con
 
 static int stem_wgrad_tiles(const bp_view* X) { return bp_ceil_div(X->w, TW) * bp_ceil_div(X->h, TH) * X->n; }
 
+int bp_stem_wgrad_grid(const bp_view* X) { return stem_wgrad_grid(stem_wgrad_tiles(X)); }
+
 size_t bp_stem_wgrad_workspace(const bp_view* X) {
   const int grid = stem_wgrad_grid(stem_wgrad_tiles(X));
   const int chunks = bp_ceil_div(grid, FOLD_ROWS);

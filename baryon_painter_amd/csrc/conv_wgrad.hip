@@ -243,10 +243,13 @@ WgradPlan wgrad_plan(const bp_conv* cv, const bp_view* X, const bp_view* Y) {
 // the k8 stride-4 encoder layer (conv_enc.hip), one-channel tails (conv_wgrad_thin.hip), the tap-packed few-channel
 // kernel, then the tap-blocked one;
 // BP_EUNSUPPORTED -> generic kernel
+// *family (bp_conv_backward_weight_plan): the BP_WG_* value of the kernel that answered
 static int wgrad_fast(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* ws,
-                      size_t ws_bytes, size_t* need, int* nsplit, int* cxp, int* cyp, hipStream_t st, bool dry) {
+                      size_t ws_bytes, size_t* need, int* nsplit, int* cxp, int* cyp, hipStream_t st, bool dry,
+                      int* family) {
   // the output-stationary kernel of the 128 <-> 128 k3 trunk layers (conv_wgrad_ws_f32.hip)
   int rc = bp_wgrad_ws_f32(cv, X, pwx, Y, pwy, ws, ws_bytes, need, nsplit, cxp, cyp, st, dry);
+  *family = BP_WG_WS_F32;
   if (rc == BP_OK && dry) {        // (size the workspace for either kernel: bp_set_option may switch later)
     size_t need2 = 0;
     int ns2, cx2, cy2;
@@ -254,9 +257,19 @@ static int wgrad_fast(const bp_conv* cv, const bp_view* X, const PW& pwx, const 
   }
   if (rc != BP_EUNSUPPORTED) return rc;
   rc = bp_wgrad_enc(cv, X, pwx, Y, pwy, ws, ws_bytes, need, nsplit, cxp, cyp, st, dry);
-  if (rc == BP_EUNSUPPORTED) rc = bp_wgrad_thin(cv, X, pwx, Y, pwy, ws, ws_bytes, need, nsplit, cxp, cyp, st, dry);
-  if (rc == BP_EUNSUPPORTED) rc = bp_wgrad_small(cv, X, pwx, Y, pwy, ws, ws_bytes, need, nsplit, cxp, cyp, st, dry);
-  if (rc == BP_EUNSUPPORTED) rc = bp_wgrad_tiles(cv, X, pwx, Y, pwy, ws, ws_bytes, need, nsplit, cxp, cyp, st, dry);
+  *family = BP_WG_ENC;
+  if (rc == BP_EUNSUPPORTED) {
+    rc = bp_wgrad_thin(cv, X, pwx, Y, pwy, ws, ws_bytes, need, nsplit, cxp, cyp, st, dry);
+    *family = X->c == 1 ? BP_WG_THIN_C1 : BP_WG_THIN_CY1;
+  }
+  if (rc == BP_EUNSUPPORTED) {
+    rc = bp_wgrad_small(cv, X, pwx, Y, pwy, ws, ws_bytes, need, nsplit, cxp, cyp, st, dry);
+    *family = BP_WG_SMALL;
+  }
+  if (rc == BP_EUNSUPPORTED) {
+    rc = bp_wgrad_tiles(cv, X, pwx, Y, pwy, ws, ws_bytes, need, nsplit, cxp, cyp, st, dry);
+    *family = bp_wgrad_tiles_last_dma() ? BP_WG_TILES_DMA : BP_WG_TILES;
+  }
   return rc;
 }
 
@@ -353,7 +366,8 @@ static PW pw_offset(const PW& p, int c0) {
 }
 
 static int wgrad_chunked(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* dst,
-                         float* ws, size_t ws_bytes, size_t* need_out, hipStream_t st, bool dry, bool on_x) {
+                         float* ws, size_t ws_bytes, size_t* need_out, hipStream_t st, bool dry, bool on_x,
+                         int32_t* plan = nullptr) {
   const int wide = on_x ? X->c : Y->c;
   size_t need_max = 0;
   for (int c0 = 0; c0 < wide; c0 += 16) {
@@ -368,6 +382,7 @@ static int wgrad_chunked(const bp_conv* cv, const bp_view* X, const PW& pwx, con
     const int rc = bp_wgrad_small(cv, Xc, px, Yc, py, ws, ws_bytes, &need, &ns, &cxp, &cyp, st, dry);
     if (rc != BP_OK) return rc;
     if (need > need_max) need_max = need;
+    if (plan && c0 == 0) { plan[0] = BP_WG_SMALL_CHUNKED; plan[1] = ns; plan[2] = cxp; plan[3] = cyp; }
     if (!dry) {
       const int rr = wgrad_reduce(ws, dst, cv->k, Xc->c, Yc->c, cxp, cyp, ns, st, X->c, on_x ? c0 : 0, on_x ? 0 : c0,
                                   /*may_defer=*/false);      // (the chunks share one workspace)
@@ -387,12 +402,13 @@ size_t bp_wgrad_bf16_workspace(const bp_conv* cv, const bp_view* X, const bp_vie
 }
 
 int bp_wgrad_bf16_run(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* dst,
-                      void* workspace, size_t workspace_bytes, hipStream_t st) {
+                      void* workspace, size_t workspace_bytes, hipStream_t st, int32_t* plan) {
   size_t need = 0;
   int ns, cxp, cyp;
   const int rc = bp_wgrad_bf16(cv, X, pwx, Y, pwy, reinterpret_cast<float*>(workspace), workspace_bytes, &need, &ns,
-                               &cxp, &cyp, st, false);
+                               &cxp, &cyp, st, plan != nullptr);
   if (rc != BP_OK) return rc;
+  if (plan) { plan[0] = bp_wgrad_bf16_last_family(); plan[1] = ns; plan[2] = cxp; plan[3] = cyp; return BP_OK; }
   return wgrad_reduce(reinterpret_cast<const float*>(workspace), dst, cv->k, X->c, Y->c, cxp, cyp, ns, st);
 }
 
@@ -423,7 +439,8 @@ static size_t wgrad_general_workspace(const bp_conv* cv, const bp_view* X, const
   if (wide_side_chunks(cv, X, Y, &on_x) &&
       wgrad_chunked(cv, X, none, Y, none, nullptr, nullptr, 0, &need, nullptr, true, on_x) == BP_OK)
     return need;
-  if (wgrad_fast(cv, X, none, Y, none, nullptr, 0, &need, &ns, &cxp, &cyp, nullptr, true) == BP_OK) return need;
+  int family;
+  if (wgrad_fast(cv, X, none, Y, none, nullptr, 0, &need, &ns, &cxp, &cyp, nullptr, true, &family) == BP_OK) return need;
   const WgradPlan p = wgrad_plan(cv, X, Y);
   return p.ok ? p.ws_bytes : 0;
 }
@@ -439,31 +456,44 @@ struct SharedTarget {                        // for the duration of one bp_wgrad
 }  // namespace
 
 int bp_wgrad_mfma(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy,
-                  float* dst, void* workspace, size_t workspace_bytes, hipStream_t st, bool shared) {
+                  float* dst, void* workspace, size_t workspace_bytes, hipStream_t st, bool shared, int32_t* plan) {
+  // `plan` (bp_conv_backward_weight_plan): the same walk, dry -- {family, nsplit, cxp, cyp} of the kernel it ends at
+  // instead of its launch
   const SharedTarget guard(shared);
-  if (bp_stem_wgrad_ok(cv, X, Y, pwy, nullptr)) return bp_stem_wgrad(X, pwx, Y, dst, workspace, workspace_bytes, st);
-  if (bp_wgrad_flat_ok(cv, X, Y, pwy)) return bp_wgrad_flat(X, pwx, Y, dst, workspace, workspace_bytes, st, shared);
+  const bool dry = plan != nullptr;
+  auto planned = [&](int family, int ns, int cxp, int cyp) {
+    plan[0] = family; plan[1] = ns; plan[2] = cxp; plan[3] = cyp;
+    return BP_OK;
+  };
+  if (bp_stem_wgrad_ok(cv, X, Y, pwy, nullptr))
+    return dry ? planned(BP_WG_STEM, bp_stem_wgrad_grid(X), 0, 0) : bp_stem_wgrad(X, pwx, Y, dst, workspace, workspace_bytes, st);
+  if (bp_wgrad_flat_ok(cv, X, Y, pwy))
+    return dry ? planned(BP_WG_FLAT, bp_wgrad_flat_grid(X, shared), 0, 0)
+               : bp_wgrad_flat(X, pwx, Y, dst, workspace, workspace_bytes, st, shared);
   if (bp_wgrad_flat_s2_ok(cv, X, Y, pwx, pwy))
-    return bp_wgrad_flat_s2(X, pwx, Y, pwy, dst, workspace, workspace_bytes, st, shared);
+    return dry ? planned(BP_WG_FLAT_S2, bp_wgrad_flat_s2_grid(Y, shared), 0, 0)
+               : bp_wgrad_flat_s2(X, pwx, Y, pwy, dst, workspace, workspace_bytes, st, shared);
   {
     bool on_x = false;
     if (wide_side_chunks(cv, X, Y, &on_x)) {
       size_t need = 0;
       return wgrad_chunked(cv, X, pwx, Y, pwy, dst, reinterpret_cast<float*>(workspace), workspace_bytes, &need, st,
-                           false, on_x);
+                           dry, on_x, plan);
     }
   }
   {
     size_t need = 0;
-    int ns, cxp, cyp;
+    int ns, cxp, cyp, family;
     const int rc = wgrad_fast(cv, X, pwx, Y, pwy, reinterpret_cast<float*>(workspace), workspace_bytes, &need,
-                              &ns, &cxp, &cyp, st, false);
+                              &ns, &cxp, &cyp, st, dry, &family);
     if (rc == BP_OK)
-      return wgrad_reduce(reinterpret_cast<const float*>(workspace), dst, cv->k, X->c, Y->c, cxp, cyp, ns, st);
+      return dry ? planned(family, ns, cxp, cyp)
+                 : wgrad_reduce(reinterpret_cast<const float*>(workspace), dst, cv->k, X->c, Y->c, cxp, cyp, ns, st);
     if (rc != BP_EUNSUPPORTED) return rc;
   }
   const WgradPlan p = wgrad_plan(cv, X, Y);
   if (!p.ok) return BP_EUNSUPPORTED;
+  if (dry) return planned(BP_WG_GENERAL, p.nsplit, p.CXP, p.CYP);
   if (!workspace || workspace_bytes < p.ws_bytes) return BP_EWORKSPACE;
   WgradArgs a{};
   a.X = X->ptr; a.xh = X->h; a.xw = X->w; a.xcs = X->cstride; a.xco = X->coff; a.cx = X->c;

@@ -1051,13 +1051,20 @@ bool wb_view_ok(const bp_view* v) {
 
 }  // namespace
 
+static thread_local int t_wb_family = BP_WG_BF16_TILED;
+int bp_wgrad_bf16_last_family() { return t_wb_family; }
+
 // Same contract as bp_wgrad_tiles (conv_wgrad_tiles.hip): partial sums to ws, BP_EUNSUPPORTED if no variant fits.
 int bp_wgrad_bf16(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* ws,
                   size_t ws_bytes, size_t* need, int* nsplit, int* cxp, int* cyp, hipStream_t st, bool dry) {
   if (!wb_view_ok(X) || !wb_view_ok(Y)) return BP_EUNSUPPORTED;
+  t_wb_family = BP_WG_BF16_WF;
   if (wf_ok(cv, X, Y, pwy)) return wf_launch(X, pwx, Y, ws, ws_bytes, need, nsplit, cxp, cyp, st, dry);
+  t_wb_family = BP_WG_BF16_SF;
   if (sf_ok(cv, X, Y, pwy)) return sf_launch(X, pwx, Y, ws, ws_bytes, need, nsplit, cxp, cyp, st, dry);
+  t_wb_family = BP_WG_BF16_WH;
   if (wh_ok(cv, X, Y, pwy)) return wh_launch(X, pwx, Y, ws, ws_bytes, need, nsplit, cxp, cyp, st, dry);
+  t_wb_family = BP_WG_WS_BF16;
   {      // the output-stationary kernel of the 128 <-> 128 k3 trunk layers (conv_wgrad_ws_bf16.hip)
     const int rc = bp_wgrad_ws_bf16(cv, X, pwx, Y, pwy, ws, ws_bytes, need, nsplit, cxp, cyp, st, dry);
     if (rc == BP_OK && dry) {      // (size the workspace for either kernel: bp_set_option may switch later)
@@ -1069,6 +1076,7 @@ int bp_wgrad_bf16(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_v
     }
     if (rc != BP_EUNSUPPORTED) return rc;
   }
+  t_wb_family = BP_WG_BF16_TILED;
   const int k = cv->k, s = cv->stride, cx = X->c, cy = Y->c;
 #define BP_WB_(...) return wb_launch<__VA_ARGS__>(cv, X, pwx, Y, pwy, ws, ws_bytes, need, nsplit, cxp, cyp, st, dry)
   if (k == 3 && s == 1) {

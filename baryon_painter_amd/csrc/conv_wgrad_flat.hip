@@ -213,6 +213,8 @@ bool bp_wgrad_flat_ok(const bp_conv* cv, const bp_view* X, const bp_view* Y, con
          Y->dtype == BP_F32 && bp_view_vec4(X) && bp_view_vec4(Y);
 }
 
+int bp_wgrad_flat_grid(const bp_view* X, bool shared) { return shared_grid(flat_grid(flat_tiles(X)), shared); }
+
 size_t bp_wgrad_flat_workspace(const bp_view* X) {
   const int grid = flat_grid(flat_tiles(X));
   const int chunks = bp_ceil_div(grid, FOLD_ROWS);
@@ -471,6 +473,8 @@ bool bp_wgrad_flat_s2_ok(const bp_conv* cv, const bp_view* X, const bp_view* Y, 
          X->h == 2 * Y->h && X->w == 2 * Y->w && X->n == Y->n && !(pwx.scale && pwy.scale) && X->dtype == BP_F32 &&
          Y->dtype == BP_F32 && bp_view_vec4(X) && bp_view_vec4(Y);
 }
+
+int bp_wgrad_flat_s2_grid(const bp_view* Y, bool shared) { return shared_grid(s2::grid_of(s2::tiles_of(Y)), shared); }
 
 size_t bp_wgrad_flat_s2_workspace(const bp_view* Y) {
   const int grid = s2::grid_of(s2::tiles_of(Y));

@@ -26,6 +26,8 @@
 // shortest (43.4 -> 42.9 ms): a grid that does not fill every CU twice leaves room for the main chain's workgroups.
 static thread_local int t_wt_target = 0;
 void bp_wgrad_tiles_target(int target) { t_wt_target = target; }
+static thread_local bool t_wt_last_dma = false;
+bool bp_wgrad_tiles_last_dma() { return t_wt_last_dma; }
 
 namespace {
 
@@ -566,6 +568,7 @@ int launch(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y,
            size_t ws_bytes, size_t* need, int* nsplit_out, int* cxp, int* cyp, hipStream_t st, bool dry) {
   using Cfg = WtCfg<KHB, KW, S, NTX, NTY, WX, WY, WK, BH>;
   using Dm = WtDma<KHB, KW, S, NTX, NTY, WX, WY, WK, BH>;
+  t_wt_last_dma = DMA;
   static_assert(WK == 1 || (WX == 1 && WY == 1), "k-split variants own the whole channel block");
   static_assert(DMA || Cfg::LDS <= 64 * 1024, "LDS budget");
   static_assert(!DMA || Dm::LDS <= 80 * 1024, "LDS budget: two workgroups per CU");
@@ -587,7 +590,8 @@ int launch(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y,
   // (only launches of about a millisecond: a long one -- the CGAN's 256 -> 512 layers run 5 - 18 ms -- loses more to the
   //  uneven grid than the main chain gains: CGAN iteration 345.8 ms at 512, 348.7 at 448)
   const double flop = 2.0 * (double)Y->n * Y->h * Y->w * cv->k * cv->k * X->c * Y->c;
-  const int target = (!dry && t_wt_target > 0 && t_wt_target < wt_target && flop < 1.5e11) ? t_wt_target : wt_target;
+  // (the target is set for the length of one bp_wgrad_mfma walk only, run or plan: the workspace queries never see it)
+  const int target = (t_wt_target > 0 && t_wt_target < wt_target && flop < 1.5e11) ? t_wt_target : wt_target;
   int64_t ns = (target + base - 1) / base;
   if (ns > ntiles) ns = ntiles;
   if (ns < 1) ns = 1;

@@ -89,10 +89,10 @@ int bp_direct_wgrad(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp
 // conv_wgrad.hip: the fp32 / bf16 weight gradient behind capi.hip, and its deferred reductions
 size_t bp_wgrad_mfma_workspace(const bp_conv* cv, const bp_view* X, const bp_view* Y);
 int bp_wgrad_mfma(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* dst,
-                  void* workspace, size_t workspace_bytes, hipStream_t st, bool shared);
+                  void* workspace, size_t workspace_bytes, hipStream_t st, bool shared, int32_t* plan = nullptr);
 size_t bp_wgrad_bf16_workspace(const bp_conv* cv, const bp_view* X, const bp_view* Y);
 int bp_wgrad_bf16_run(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* dst,
-                      void* workspace, size_t workspace_bytes, hipStream_t st);
+                      void* workspace, size_t workspace_bytes, hipStream_t st, int32_t* plan = nullptr);
 void bp_wgrad_private_ws(bool on);
 int bp_wgrad_defer_begin_impl();
 int bp_wgrad_defer_flush_impl(hipStream_t st, int end);
@@ -107,21 +107,27 @@ WgradPartialFn bp_wgrad_ws_f32, bp_wgrad_enc, bp_wgrad_thin, bp_wgrad_small, bp_
 void bp_f32_wgrad_ws_set(int v);        // conv_wgrad_ws_f32.hip
 void bp_bf16_wgrad_ws_set(int v);       // conv_wgrad_ws_bf16.hip
 void bp_wgrad_tiles_target(int target); // conv_wgrad_tiles.hip
+// which kernel the last bp_wgrad_tiles / bp_wgrad_bf16 call on this thread chose (for bp_conv_backward_weight_plan)
+bool bp_wgrad_tiles_last_dma();         // conv_wgrad_tiles.hip: the LDS-DMA variant
+int bp_wgrad_bf16_last_family();        // conv_wgrad_bf16.hip: BP_WG_BF16_* / BP_WG_WS_BF16
 
 // Weight-gradient kernels that reduce their own partial sums.
 // conv_stem.hip: weight gradient of the 3 -> 16 k5 stem
 bool bp_stem_wgrad_ok(const bp_conv* cv, const bp_view* X, const bp_view* Y, const PW& pwy, const float* dbias);
 size_t bp_stem_wgrad_workspace(const bp_view* X);
+int bp_stem_wgrad_grid(const bp_view* X);
 int bp_stem_wgrad(const bp_view* X, const PW& pwx, const bp_view* Y, float* dst, void* workspace, size_t workspace_bytes,
                   hipStream_t st);
 // conv_wgrad_flat.hip: weight gradient of the 16 -> 8 k7 head layer
 bool bp_wgrad_flat_ok(const bp_conv* cv, const bp_view* X, const bp_view* Y, const PW& pwy);
 size_t bp_wgrad_flat_workspace(const bp_view* X);
+int bp_wgrad_flat_grid(const bp_view* X, bool shared);
 int bp_wgrad_flat(const bp_view* X, const PW& pwx, const bp_view* Y, float* dst, void* workspace, size_t workspace_bytes,
                   hipStream_t st, bool shared);
 // ... and of the thin stride-2 k4 layers (16 channels at full resolution, 32 at half)
 bool bp_wgrad_flat_s2_ok(const bp_conv* cv, const bp_view* X, const bp_view* Y, const PW& pwx, const PW& pwy);
 size_t bp_wgrad_flat_s2_workspace(const bp_view* Y);
+int bp_wgrad_flat_s2_grid(const bp_view* Y, bool shared);
 int bp_wgrad_flat_s2(const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* dst, void* workspace,
                      size_t workspace_bytes, hipStream_t st, bool shared);
 

@@ -206,6 +206,21 @@ int bp_conv_backward_weight(const bp_conv* cv, const bp_view* x, const bp_pointw
                             const bp_view* dy, float* dw_torch, float* dbias, void* workspace,
                             size_t workspace_bytes, int impl, void* stream);
 
+/* Which kernel bp_conv_backward_weight would run for these views and this `impl` (BP_IMPL_SHARED included; options set
+ * with bp_set_option are honoured), and with how many partial images: out = {family, nsplit, cxp, cyp}.  Host arithmetic
+ * only: nothing is launched and no view pointer is dereferenced (its alignment is looked at).  `family` is one of the
+ * values below, one per file-level kernel; `nsplit` is the number of partial images the kernel writes (for the kernels
+ * that reduce themselves -- stem, flat, flat_s2 -- their grid; 0 for the direct kernel); cxp x cyp are the padded
+ * channel counts of one partial image (0 where the kernel has no such image; for the chunked kernel: of one chunk).
+ * A pending activation does not enter the choice.  Returns what the call would return before its first launch
+ * (BP_EUNSUPPORTED: no kernel; then out is {-1, 0, 0, 0}). */
+enum {
+  BP_WG_WS_F32 = 0, BP_WG_ENC, BP_WG_THIN_C1, BP_WG_THIN_CY1, BP_WG_SMALL, BP_WG_SMALL_CHUNKED, BP_WG_TILES,
+  BP_WG_TILES_DMA, BP_WG_GENERAL, BP_WG_STEM, BP_WG_FLAT, BP_WG_FLAT_S2, BP_WG_DIRECT, BP_WG_BF16_TILED, BP_WG_BF16_WF,
+  BP_WG_BF16_SF, BP_WG_BF16_WH, BP_WG_WS_BF16
+};
+int bp_conv_backward_weight_plan(const bp_conv* cv, const bp_view* x, const bp_view* dy, int impl, int32_t out[4]);
+
 /* Deferred split-K reductions.  Between bp_wgrad_defer_begin() and bp_wgrad_defer_flush(end = 1, ...) on one host
  * thread, a bp_conv_backward_weight call flagged BP_IMPL_DEFER launches the layer's partial-sum kernel but only
  * RECORDS its reduction into dw_torch;
