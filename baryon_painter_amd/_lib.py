@@ -19,7 +19,7 @@ WGRAD_FAMILIES = ("ws_f32", "enc", "thin_c1", "thin_cy1", "small", "small_chunke
                   "flat", "flat_s2", "direct", "bf16_tiled", "bf16_wf", "bf16_sf", "bf16_wh", "ws_bf16")
 PACK_FWD, PACK_BWD = 0, 1
 F32, BF16 = 0, 1
-F64 = 2            # bp_plane_cut's float64 planes
+F64 = 2            # bp_plane_cut's and bp_window_*'s float64 planes
 # range-compression modes of the `_mode` entry points (utils.data_transforms.MODE_IDS maps the mode names to these)
 RC_SHIFT_LOG, RC_LOG, RC_SHIFT_LOG_2P, RC_LOG_TANH, RC_X_1PX, RC_INV_X = range(6)
 
@@ -165,6 +165,13 @@ SIGNATURES = {
                                          _P]),
     "bp_plane_project_workspace": (C.c_size_t, [C.c_int32, C.c_int32]),
     "bp_plane_project": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_double, _P, C.c_size_t, _P, C.c_int32, _P]),
+    "bp_window_min_workspace": (C.c_size_t, []),
+    "bp_window_min": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_size_t,
+                                _P, _P]),
+    "bp_window_zoom_workspace": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "bp_window_zoom": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32,
+                                 _P, C.c_size_t, _P, _P]),
+    "bp_tile_crop": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "bp_linear_workspace": (C.c_size_t, [C.c_int32, C.POINTER(Linear)]),
     "bp_linear_forward": (C.c_int, [C.POINTER(Linear), _VP, _PWP, _P, _P, _VP, _P, C.c_size_t, _P]),
     "bp_linear_backward_data": (C.c_int, [C.POINTER(Linear), _VP, _P, _VP, _P]),

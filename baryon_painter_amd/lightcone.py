@@ -373,8 +373,24 @@ def _field_index(painter, field):
     return None
 
 
+def small_plane_geometry(n_mass, shift, delta_size, tile_size, mass_size, n_pixel_tile):
+    """The integers of ``paint_small_plane`` for a mass plane of ``n_mass`` rows, with ``get_tile``'s exact expressions:
+    the window cut from the mass plane -- origin (``x0``, ``y0``), not wrapped yet, and ``cut`` pixels a side -- and the
+    footprint cropped from the painted tile of ``n_pixel_tile`` pixels -- origin (``r0``, ``c0``) and ``crop`` pixels a
+    side.  ValueError for ``tile_size < delta_size``, as ``get_tile``'s."""
+    rel, exp = delta_size / mass_size, tile_size / delta_size
+    if exp < 1:
+        raise ValueError("Expension factors < 1 not supported.")
+    cut = int(n_mass * rel * exp)
+    off = int(n_mass * rel * (exp - 1) / 2)
+    centre = (1 - delta_size / tile_size) / 2
+    return {"x0": int(n_mass * shift[0]) - off, "y0": int(n_mass * shift[1]) - off, "cut": cut,
+            "r0": int(n_pixel_tile * centre), "c0": int(n_pixel_tile * centre),
+            "crop": int(n_pixel_tile * (delta_size / tile_size) * 1)}
+
+
 def paint_small_plane(painter, massplane, shift, delta_size, tile_size, mass_size, n_pixel_tile, z, seed=None,
-                      tile_id=0, subtract_minimum=False, field=None, pixel_noise=False):
+                      tile_id=0, subtract_minimum=False, field=None, pixel_noise=False, on_device=False, out=None):
     """Paint a plane whose footprint ``delta_size`` is smaller than the network's tile ``tile_size`` (the low-redshift
     branch of ``process_SLICS``, process_SLICS.py:149-176): ONE tile, expanded to the network's size around the
     footprint, is cut with wrap-around at ``shift`` from the periodic mass plane of ``mass_size`` (all three sizes in
@@ -382,18 +398,33 @@ def paint_small_plane(painter, massplane, shift, delta_size, tile_size, mass_siz
     the central footprint of the painted tile is returned.  ``subtract_minimum``: the reference's ``SLICS_density``
     switch (the tile's minimum is subtracted before resampling).
 
-    One tile per plane: cut and zoom stay on the host.  A painter with a device pipeline for this redshift
+    By default cut and zoom stay on the host.  A painter with a device pipeline for this redshift
     (``can_paint_stream``) paints through ``paint_stream`` with the Philox key (``seed``, ``tile_id``); ``seed=None``
     draws a fresh key from torch's global generator.  Any other painter goes through ``paint``.  The plane is returned
     as float64, like ``paint_plane``'s.  ``field``: the label field to return, needed for a painter with several
     (ValueError without it, before any random number is drawn).  ``pixel_noise``: the tile is a draw from the likelihood
-    (``paint_plane``) on the lattice ``tile_id`` at origin (0, 0), on either path (``paint`` under the same ``seed``)."""
-    import scipy.ndimage
+    (``paint_plane``) on the lattice ``tile_id`` at origin (0, 0), on either path (``paint`` under the same ``seed``).
+
+    ``on_device=True`` (opt-in; needs ``painter.can_paint_stream(z)``, NotImplementedError otherwise, raised before any
+    random number is drawn or any graph is captured): minimum, cut, zoom, paint and crop run on the device on one stream
+    (csrc/window.hip around ``model.paint_graph(1)``), with the integers of ``small_plane_geometry`` and the seed word,
+    tile id and noise lattice of the host path.  A NumPy or memory-mapped ``massplane`` (float32 or float64): only the
+    wrapped window is gathered on the host and uploaded.  A CUDA ``massplane`` on the painter's device is used in
+    place, the wrap in the kernel; both give the same bits.  Returns the (m, m) float64 plane as NumPy, or fills and
+    returns ``out`` (a CUDA float64 (m, m) tensor; nothing is downloaded).  The resampled tile is SciPy's float64
+    zoom rounded once to float32, within one float32 rounding of the host path's tile and not bit-equal to it
+    everywhere, so the painted planes of the two paths differ by what the network makes of that."""
     j = _field_index(painter, field)
     noise = {}
     if pixel_noise:
         _need_pixel_noise(painter)
         noise = {"pixel_noise": True}
+    if on_device:
+        return _paint_small_plane_device(painter, massplane, shift, delta_size, tile_size, mass_size, n_pixel_tile, z,
+                                         seed, tile_id, subtract_minimum, j, out, pixel_noise)
+    if out is not None:
+        raise ValueError("out= needs on_device=True")
+    import scipy.ndimage
     tile = get_tile(massplane, shift, tile_relative_size=delta_size / mass_size,
                     expansion_factor=tile_size / delta_size)
     if subtract_minimum:
@@ -419,9 +450,45 @@ def paint_small_plane(painter, massplane, shift, delta_size, tile_size, mass_siz
                     tile_relative_size=delta_size / tile_size)
 
 
+def _paint_small_plane_device(painter, massplane, shift, delta_size, tile_size, mass_size, n_pixel_tile, z, seed,
+                              tile_id, subtract_minimum, j, out, pixel_noise):
+    if not (hasattr(painter, "_paint_small_plane_device") and _streams(painter, z)):
+        raise NotImplementedError("paint_small_plane(on_device=True) needs a painter with a device paint pipeline "
+                                  "(CVAEPainter / CGANPainter .can_paint_stream)")
+    import torch
+    geo = small_plane_geometry(massplane.shape[0], shift, delta_size, tile_size, mass_size, n_pixel_tile)
+    cut = geo["cut"]
+    if cut < 2 or int(round(cut * (n_pixel_tile / cut))) != n_pixel_tile:
+        raise ValueError(f"the expanded tile of {cut} pixels does not zoom to {n_pixel_tile} pixels")
+    if tuple(painter._tile_shape()) != (n_pixel_tile, n_pixel_tile):
+        raise ValueError(painter._shape_mismatch((1, n_pixel_tile, n_pixel_tile)))
+    dev = torch.device(painter.model.device)
+    if isinstance(massplane, torch.Tensor):
+        if massplane.device != dev:
+            raise ValueError(f"the mass plane lives on {massplane.device}, the painter on {dev}")
+        plane = massplane if massplane.is_contiguous() else massplane.contiguous()
+        origin = (geo["x0"], geo["y0"])
+    else:
+        # (get_tile's own gather: the window alone crosses the host link, not the plane)
+        window = get_tile(massplane, shift, tile_relative_size=delta_size / mass_size,
+                          expansion_factor=tile_size / delta_size)
+        if window.dtype not in (np.float32, np.float64):
+            raise TypeError("the mass plane must be float32 or float64")
+        plane = torch.from_numpy(np.ascontiguousarray(window)).to(dev)
+        origin = (0, 0)
+    if plane.dim() != 2 or plane.dtype not in (torch.float32, torch.float64):
+        raise TypeError("the mass plane must be a 2-d float32 or float64 plane")
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    kw = {"pixel_noise": True} if pixel_noise else {}
+    return painter._paint_small_plane_device(plane, origin, cut, (geo["r0"], geo["c0"], geo["crop"]), z, tile_id, seed,
+                                             subtract_minimum=subtract_minimum, field_index=j, out=out, **kw)
+
+
 def paint_light_cone(painter, planes, z, delta_size, tile_size, n_pixel_tile, resolution, scales, min_tile_overlap=0.5,
                      falloff=0.05, sigma=0.5, regularise_std=None, batch_size=64, order=3, subtract_minimum=False,
-                     on_device=False, seed=None, out=None, return_planes=False, field=None, pixel_noise=False):
+                     on_device=False, seed=None, out=None, return_planes=False, field=None, pixel_noise=False,
+                     small_planes_on_device=False):
     """Mass planes in, one y map out (``process_SLICS`` followed by ``create_y_map``'s loop, process_SLICS.py:147-220 and
     55-64): plane i of the light cone is painted at redshift ``z[i]`` and projected into the (resolution, resolution)
     map with the factor ``scales[i]`` (``y_map_scales``) at once; no list of painted planes is kept.
@@ -442,7 +509,14 @@ def paint_light_cone(painter, planes, z, delta_size, tile_size, n_pixel_tile, re
     otherwise, before any random number is drawn): ``paint_plane(on_device=True, out=...)`` leaves each plane in a
     device buffer that ``bp_plane_project_order`` reads on the same stream and the next plane reuses; only the finished map is downloaded,
     or nothing with ``out`` (a CUDA float64 (resolution, resolution) tensor that is accumulated into and returned).
-    Small planes are painted as on the host path and uploaded.
+    Small planes are painted as on the host path and uploaded, for which the stream is synchronised.
+
+    ``small_planes_on_device=True`` (with ``on_device=True`` only; ValueError without it): small planes take
+    ``paint_small_plane(on_device=True, out=...)`` into a device buffer that the projection reads on the same stream --
+    no synchronisation, no upload of a painted plane; a mass plane given as a CUDA tensor is cut in place, of a host
+    one only the window is uploaded.  Off by default: the device's resampled tile is within one float32 rounding of
+    SciPy's and not bit-equal to it, so a small plane painted this way is not the host path's bit for bit, which it is
+    with the flag off.
 
     ``field``: a painter with several label fields paints all of them from one latent draw, and the map is made of
     ONE: ``field`` names it (ValueError without it or for a name the painter does not paint, before any random number is
@@ -464,6 +538,8 @@ def paint_light_cone(painter, planes, z, delta_size, tile_size, n_pixel_tile, re
     n_f = len(painter.label_fields) if j is not None else 1
     if out is not None and not on_device:
         raise ValueError("out= needs on_device=True")
+    if small_planes_on_device and not on_device:
+        raise ValueError("small_planes_on_device=True needs on_device=True")
     # eligibility is decided UP FRONT, as in paint_plane: no random number is drawn for a light cone that cannot run
     if on_device:
         if order not in _DEVICE_ORDERS:
@@ -510,19 +586,27 @@ def paint_light_cone(painter, planes, z, delta_size, tile_size, n_pixel_tile, re
                 plane = plane[j]                                 # (a contiguous slice of the fields' planes)
         else:
             massplane, shift, mass_size = entry
-            if on_device:                                        # paint_stream copies on streams of its own
-                torch.cuda.current_stream(dev).synchronize()
-            plane = paint_small_plane(painter, massplane, shift, delta_size[i], tile_size, mass_size, n_pixel_tile,
-                                      z[i], seed=seed, tile_id=tile_id, subtract_minimum=subtract_minimum, field=field,
-                                      **noise)
+            kw = dict(seed=seed, tile_id=tile_id, subtract_minimum=subtract_minimum, field=field, **noise)
             tile_id += 1
-            if on_device:
-                host = plane
-                plane = torch.from_numpy(np.ascontiguousarray(plane)).to(dev)
+            host = None
+            if small_planes_on_device:                           # one stream from the cut to the projection
+                m = small_plane_geometry(massplane.shape[0], shift, delta_size[i], tile_size, mass_size,
+                                         n_pixel_tile)["crop"]
+                plane = paint_small_plane(painter, massplane, shift, delta_size[i], tile_size, mass_size, n_pixel_tile,
+                                          z[i], on_device=True,
+                                          out=torch.empty((m, m), dtype=torch.float64, device=dev), **kw)
+            else:
+                if on_device:                                    # paint_stream copies on streams of its own
+                    torch.cuda.current_stream(dev).synchronize()
+                plane = paint_small_plane(painter, massplane, shift, delta_size[i], tile_size, mass_size, n_pixel_tile,
+                                          z[i], **kw)
+                if on_device:
+                    host = plane
+                    plane = torch.from_numpy(np.ascontiguousarray(plane)).to(dev)
         if on_device:
             _project_device(plane, scales[i], y_map, order)
             if return_planes:
-                kept.append(plane.cpu().numpy() if delta_size[i] >= tile_size else host)
+                kept.append(host if delta_size[i] < tile_size and host is not None else plane.cpu().numpy())
         else:
             _project_host(y_map, plane, scales[i], order)
             if return_planes:

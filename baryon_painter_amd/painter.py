@@ -142,6 +142,32 @@ class Painter:
         return _paint_plane_pipeline(self, model, tile, delta, geo, int(batch_size), params, tile_ids, seed, weight_map,
                                      regularise_std, out, scales, modes)
 
+    def _paint_small_plane_device(self, plane, origin, size, crop, z, tile_id, seed, subtract_minimum=False,
+                                  field_index=None, out=None, pixel_noise=False):
+        """The device form of ``lightcone.paint_small_plane`` (on_device=True), on ONE stream and without a host
+        synchronisation: ``plane`` is a contiguous 2-d CUDA float32 / float64 tensor on the model's device -- the
+        periodic mass plane, or a window of it that the caller gathered -- and ``origin`` = (x0, y0), ``size`` the
+        ``size`` x ``size`` window of it that is the tile, wrapped in the kernel; ``crop`` = (r0, c0, m) the footprint
+        in the painted tile (``lightcone.small_plane_geometry``'s integers).  The window's minimum where
+        ``subtract_minimum`` (bp_window_min), the spline zoom straight into slot 0's ``raw`` of
+        ``model.paint_graph(1)`` (bp_window_zoom), the parameter block of one tile with ``paint_stream``'s seed word and
+        ``tile_id`` -- with ``pixel_noise`` the lattice ``tile_id`` at origin (0, 0), as on the host path -- the replay,
+        and the crop of label field ``field_index`` (None: the only one) of the slot's ``out`` (bp_tile_crop).  Returns
+        the (m, m) float64 plane as NumPy, or ``out`` (a CUDA float64 (m, m) tensor) filled in place."""
+        model = self.model
+        model.train(False)
+        tile, W = self._tile_shape()
+        if tile != W:
+            raise NotImplementedError("device planes need square tiles")
+        if pixel_noise:
+            self._need_pixel_noise()
+        params, scales, modes = self._device_paint_parameters(np.full(1, float(z)))
+        ids = np.array([tile_id], dtype=np.int64)
+        if pixel_noise:
+            params = _with_noise(params, ids, None, 1, tile, tile, 0, 1)
+        return _paint_small_plane_pipeline(self, model, tile, plane, origin, int(size), crop, params, ids, seed,
+                                           subtract_minimum, field_index, out, scales, modes)
+
 
 class CVAEPainter(Painter):
     def __init__(self, filename=None, training_data_set=None, test_data_set=None, architecture="test",
@@ -1073,6 +1099,66 @@ def _paint_plane_pipeline(painter, model, tile, delta, geo, B, params, tile_ids,
                              float(regularise_std) if reg else 0.0, L.ptr(buf["stats"]), L.ptr(acc),
                              L.ptr(wsum), n_plane, n_plane, sm), "plane blend")
         L.check(lib.bp_plane_finish(L.ptr(acc), L.ptr(wsum), F * n_plane * n_plane, L.ptr(result), sm), "plane finish")
+        if out is not None:
+            return out
+        return result.cpu().numpy()
+
+
+def _paint_small_plane_pipeline(painter, model, tile, plane, origin, size, crop, params, ids, seed, subtract_minimum,
+                                field_index, out, scales=None, modes=None):
+    """One tile through ``model.paint_graph(1)`` on the device (``Painter._paint_small_plane_device``): minimum, zoom
+    into slot 0's ``raw``, parameter block, replay, crop, on ONE stream.  ``modes`` of F > 1 label fields: the slot's
+    ``out`` is (1, F, tile, tile) and ``field_index`` says which field is cropped."""
+    import ctypes as C
+    from . import _lib as L
+    dev = torch.device(model.device)
+    F = _n_fields(modes)
+    if F > 1 and (field_index is None or not 0 <= field_index < F):
+        raise ValueError(f"a painter with {F} label fields needs the index of the field to crop")
+    j = field_index if F > 1 else 0
+    if (not isinstance(plane, torch.Tensor) or plane.device != dev or plane.dim() != 2 or not plane.is_contiguous() or
+            plane.dtype not in (torch.float32, torch.float64)):
+        raise TypeError(f"the plane must be a contiguous 2-d float32 or float64 tensor on {dev}")
+    r0, c0, m = (int(v) for v in crop)
+    if out is not None and (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.float64 or
+                            tuple(out.shape) != (m, m) or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous float64 ({m}, {m}) tensor on {dev}")
+    g = _paint_graph(model, 1, scales, modes, "noise_ids" in params)
+    block = g["param_block"]
+    blk = torch.zeros(g["block_bytes"], dtype=torch.uint8)
+    hv = block.views(blk)
+    hv["seed"][0] = PG.seed_word(seed)
+    _fill_block(hv, params, ids, 0, 1, 1)
+    lib = L.load()
+    # the resampling scratch is kept between calls, beside _paint_plane_pipeline's (release_paint_buffers() frees it)
+    cache = painter.__dict__.setdefault("_plane_device_buffers", {})
+    ws, ws_min = int(lib.bp_window_zoom_workspace(size, tile)), int(lib.bp_window_min_workspace())
+    key = ("small", ws, str(dev))
+    if key not in cache:
+        for k in [k for k in cache if k[0] == "small"]:
+            del cache[k]
+        cache[key] = {"scratch": torch.empty(max(ws // 8, 1), dtype=torch.float64, device=dev),
+                      "min_scratch": torch.empty(ws_min // 8, dtype=torch.float64, device=dev),
+                      "min": torch.empty(1, dtype=torch.float64, device=dev)}
+    buf = cache[key]
+    result = out if out is not None else torch.empty((m, m), dtype=torch.float64, device=dev)
+    with torch.no_grad(), torch.cuda.device(dev):
+        sm = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        dtype = L.F32 if plane.dtype == torch.float32 else L.F64
+        rows, cols = plane.shape
+        x0, y0 = int(origin[0]), int(origin[1])
+        gs = g["slots"][0]
+        minimum = None
+        if subtract_minimum:
+            minimum = L.ptr(buf["min"])               # (one value of the plane's dtype at the front of a double)
+            L.check(lib.bp_window_min(L.ptr(plane), dtype, rows, cols, x0, y0, size, L.ptr(buf["min_scratch"]), ws_min,
+                                      minimum, sm), "window min")
+        L.check(lib.bp_window_zoom(L.ptr(plane), dtype, rows, cols, x0, y0, size, minimum, tile, L.ptr(buf["scratch"]),
+                                   buf["scratch"].numel() * 8, L.ptr(gs["raw"]), sm), "window zoom")
+        gs["block"].copy_(blk.to(dev))
+        gs["graph"].replay()
+        img = C.c_void_p(gs["out"].data_ptr() + 4 * j * tile * tile)
+        L.check(lib.bp_tile_crop(img, tile, r0, c0, m, L.ptr(result), sm), "tile crop")
         if out is not None:
             return out
         return result.cpu().numpy()

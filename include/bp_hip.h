@@ -556,6 +556,36 @@ size_t bp_plane_project_workspace(int32_t n, int32_t res);
 int bp_plane_project(const double* plane, int32_t rows, int32_t cols, double scale, double* scratch,
                      size_t scratch_bytes, double* y, int32_t res, void* stream);
 
+/* ---- the low-redshift plane of a light cone (lightcone.paint_small_plane(on_device=True), process_SLICS.py:149-176)
+ * ONE tile around a footprint smaller than the network's tile: cut with wrap-around from the periodic mass plane,
+ * resampled to the tile, painted, and the footprint cropped from the painted tile, all on one stream.  The window is
+ * size x size; its pixel (i, j) is plane[(x0 + i) mod rows, (y0 + j) mod cols] of the rows x cols plane (BP_F32 or
+ * BP_F64), the modulo not negative (np.take(mode="wrap")): x0, y0 may be negative or past the edge.  The integers are
+ * the host's (lightcone.get_tile's expressions).
+ *   bp_window_min  : min_out[0] (device, of the plane's dtype) = the minimum of the window, NaN if the window holds a
+ *                    NaN (np.min).  Two stages in a fixed order through `scratch` (bp_window_min_workspace() bytes); the
+ *                    value stays on the device.
+ *   bp_window_zoom : out (tile, tile) float32 = scipy.ndimage.zoom(w, tile / size, order=3, mode="mirror") of the
+ *                    window w -- of w - minimum[0], subtracted in the plane's dtype, where `minimum` (device, of the
+ *                    plane's dtype) is not NULL -- in float64 with bp_plane_project's prefilter and sampler, rounded
+ *                    once to float32.  size == tile goes through the spline as well.  The first pass gathers from the
+ *                    plane; `scratch` is bp_window_zoom_workspace(size, tile) bytes (two float64 images of the window;
+ *                    0 for arguments that would be refused).  The plane is not modified.  A window with non-finite
+ *                    values is resampled without a fault, but not as SciPy's full-line recursion would spread them.
+ *   bp_tile_crop   : out (m, m) float64 = (double) img[(r0 + i) mod tile, (c0 + j) mod tile] of the (tile, tile)
+ *                    float32 image: get_tile of a painted tile.
+ * In this order, and with nothing launched or written: BP_EINVAL for a null pointer other than `minimum`, rows, cols,
+ * size, tile or m < 1, size or tile < 2 in bp_window_zoom, or a dtype that is neither BP_F32 nor BP_F64;
+ * BP_EUNSUPPORTED for size^2, tile^2 or m^2 >= 2^31 or an origin of 2^30 or more in absolute value; BP_EWORKSPACE for
+ * a scratch that is too short.  No atomics: the same inputs give the same bits.  No host synchronisation. */
+size_t bp_window_min_workspace(void);
+int bp_window_min(const void* plane, int32_t dtype, int32_t rows, int32_t cols, int32_t x0, int32_t y0, int32_t size,
+                  void* scratch, size_t scratch_bytes, void* min_out, void* stream);
+size_t bp_window_zoom_workspace(int32_t size, int32_t tile);
+int bp_window_zoom(const void* plane, int32_t dtype, int32_t rows, int32_t cols, int32_t x0, int32_t y0, int32_t size,
+                   const void* minimum, int32_t tile, double* scratch, size_t scratch_bytes, float* out, void* stream);
+int bp_tile_crop(const float* img, int32_t tile, int32_t r0, int32_t c0, int32_t m, double* out, void* stream);
+
 /* ---- fully connected layers of the latent bottleneck (replaces nn.Linear behind nn.Flatten / in front of
  *      nn.Unflatten, utils.py:132-133, 148-157, and their autograd backward) ------------------------------------- */
 
