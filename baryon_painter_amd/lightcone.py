@@ -194,6 +194,127 @@ def _paint_plane_device(painter, delta, tile_relative_size, n_pixel_tile, z, min
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Ensembles of planes: K latent draws of every tile, each draw blended into a plane of its own, the moments across the
+# K planes.  (The moments of a feathered blend are not the blend of the tiles' moments: the blend runs in physical
+# units behind a non-linear inverse.)
+
+def ensemble_moments(planes):
+    """(mean, var) across axis 0 of ``planes`` (K, ...) in float64, with the arithmetic of ``bp_plane_moments``
+    (include/bp_hip.h), every operation rounded once, in ascending k: S = ((P_0 + P_1) + ...) + P_{K-1}, M = S / K,
+    Q = ((P_0 - M)^2 + (P_1 - M)^2) + ..., mean = M, var = Q / K -- the population variance (``np.var``, ddof = 0) in two
+    passes.  NaN (a pixel no tile reaches) and infinite elements give what IEEE arithmetic gives; K = 1 gives var = +0
+    where the plane is finite."""
+    p = np.asarray(planes, dtype=np.float64)
+    if p.ndim < 1 or p.shape[0] < 1:
+        raise ValueError("ensemble_moments needs at least one plane")
+    K = np.float64(p.shape[0])
+    with np.errstate(invalid="ignore", over="ignore"):
+        S = p[0].copy()
+        for k in range(1, p.shape[0]):
+            S = S + p[k]
+        M = S / K
+        Q = None
+        for k in range(p.shape[0]):
+            d = p[k] - M
+            Q = d * d if Q is None else Q + d * d
+        return M, Q / K
+
+
+def _need_ensemble(painter, zs, draws, batch_size, pixel_noise, on_device, what, method="_paint_plane_device"):
+    """The refusals the ensemble surfaces share, before any random number is drawn or any graph is captured: ``draws``
+    = K outside 1 ... 64 or not dividing ``batch_size`` (ValueError), ``pixel_noise`` (NotImplementedError), a painter
+    without ``paint_ensemble`` -- the CGAN has no latent -- or without an ensemble pipeline at one of the redshifts
+    ``zs``, or, with ``on_device``, without the device ``method`` (NotImplementedError).  Returns K."""
+    from .models import paint_graph as PG
+    K = PG.check_draws(draws)
+    if batch_size is not None and (int(batch_size) < K or int(batch_size) % K):
+        raise ValueError(f"batch_size counts generator samples: {K} draws per tile must divide it, got {batch_size}")
+    if pixel_noise:
+        raise NotImplementedError(f"{what} has no pixel_noise: an ensemble block has no noise_org, so the overlapping "
+                                  "tiles of a plane could not share their noise lattice")
+    if not (hasattr(painter, "paint_ensemble") and hasattr(painter, "_device_paint_parameters")):
+        raise NotImplementedError(f"{what} needs a painter with paint_ensemble (a CVAEPainter: a CGAN has no latent to "
+                                  "draw from)")
+    if on_device and not hasattr(painter, method):
+        raise NotImplementedError(f"{what}(on_device=True) needs a painter with a device paint pipeline")
+    for z in zs:                                  # (NotImplementedError where the painter has no ensemble pipeline)
+        painter._device_paint_parameters(np.full(1, float(z)), ensemble=True)
+    return K
+
+
+def _fresh_seed(seed):
+    if seed is None:
+        import torch
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    return seed
+
+
+def paint_plane_ensemble(painter, delta, tile_relative_size, n_pixel_tile, z, draws, min_tile_overlap=0.5, falloff=0.05,
+                         sigma=0.5, regularise_std=None, batch_size=64, seed=None, first_tile_id=0, on_device=False,
+                         out=None, return_planes=False):
+    """The conditional mean and scatter of a painted PLANE at fixed dark matter: ``draws`` = K (1 ... 64) latent draws
+    of every tile of ``paint_plane``'s tiling, draw k of all tiles blended into plane k exactly as ``paint_plane``
+    blends (``falloff``, ``sigma``, ``regularise_std`` per draw and field), and the moments ACROSS the K planes:
+    returns (mean, var), float64 (n_plane, n_plane) -- (F, n_plane, n_plane) for a painter with F > 1 label fields --
+    with ``var`` the population variance (``ensemble_moments``).  ``return_planes=True`` adds the K planes,
+    (K, [F,] n_plane, n_plane).  Pixels no tile reaches are NaN in all three.
+
+    Draw l of tile (j, k) uses the Philox counter (g, l, ``first_tile_id`` + j * n_side + k) under the key ``seed``
+    (None: a fresh key from torch's global generator): plane 0 is the plane ``paint_plane`` paints for the same seed and
+    ids, and nothing depends on ``batch_size``, which counts generator samples -- K must divide it (ValueError), and a
+    batch carries ``batch_size // K`` tiles.  The painter needs ``paint_ensemble`` (a CVAEPainter; NotImplementedError
+    for a CGAN, which has no latent, and for transforms or models without an ensemble pipeline), checked before any
+    random number is drawn or any graph is captured.  There is no ``pixel_noise`` here and no sharding over ranks.
+
+    Host path: ``paint_plane``'s host cut and zoom, ``painter.paint_ensemble(..., return_draws=True)``, the host blend
+    per draw and field, ``ensemble_moments``.
+
+    ``on_device=True``: cut, zoom, the draws, the K blends (``bp_plane_blend_fields`` over K F planes) and the moments
+    (``bp_plane_moments``) run on the device on one stream; the conditioning of a tile runs once, not K times, and only
+    mean and variance (and the planes, if asked for) are downloaded.  ``out`` = (mean, var): two CUDA float64 tensors
+    of the result's shape that receive it; nothing is downloaded, and with ``return_planes`` the planes are a CUDA
+    tensor.  ``delta`` may be a CUDA tensor, used in place.  The K accumulator pairs take ``16 K F n_plane^2`` bytes of
+    device memory (4.3 GB at 4096^2 and K = 16), kept until ``painter.release_paint_buffers()``.  Parity with the
+    host path is ``paint_plane``'s: equal bits of cut and blend, 1 ulp (float32) in the resampled tiles, the tie band of
+    ``regularise_std``."""
+    K = _need_ensemble(painter, [z], draws, batch_size, False, on_device, "paint_plane_ensemble")
+    if out is not None and not on_device:
+        raise ValueError("out= needs on_device=True")
+    geo = plane_geometry(delta.shape[0], tile_relative_size, n_pixel_tile, min_tile_overlap)
+    n_plane, cut, n_tiles = geo["n_plane"], geo["cut"], len(geo["origins"])
+    per = min(int(batch_size) // K, n_tiles)                     # tiles per batch
+    ids = first_tile_id + np.arange(n_tiles, dtype=np.int64)
+    if on_device:
+        if cut != n_pixel_tile and int(round(cut * (n_pixel_tile / cut))) != n_pixel_tile:
+            raise ValueError(f"a {cut}-pixel cut does not zoom to {n_pixel_tile} pixels")
+        if (geo["dst"] + n_pixel_tile > n_plane).any():
+            raise ValueError("the tiling does not fit the plane")
+        w = make_weight_map((n_pixel_tile, n_pixel_tile), falloff=falloff, sigma=sigma)
+        return painter._paint_plane_device(delta, geo, z, w, batch_size=per, tile_ids=ids, seed=_fresh_seed(seed),
+                                           regularise_std=regularise_std, out=out, draws=K,
+                                           return_planes=return_planes)
+    origins, slices = generate_tiling(n_plane, n_pixel_tile, min_tile_overlap)
+    tiles = []
+    for xs in origins:
+        for ys in origins:
+            t = get_tile(delta, (xs, ys), tile_relative_size)
+            if t.shape[0] != n_pixel_tile:
+                import scipy.ndimage
+                t = scipy.ndimage.zoom(t, zoom=n_pixel_tile / t.shape[0], mode="reflect")
+            tiles.append(np.asarray(t, dtype=np.float32))
+    painted = painter.paint_ensemble(np.stack(tiles), z, draws=K, batch_size=per * K, tile_ids=ids,
+                                     seed=_fresh_seed(seed), return_draws=True)[2]
+    if painted.ndim == 4:                        # (N, K, H, W) -> (N, K, 1, H, W)
+        painted = painted[:, :, None]
+    planes = np.stack([np.stack([_blend_host(painted[:, k, f], slices, n_plane, falloff, sigma, regularise_std)
+                                 for f in range(painted.shape[2])]) for k in range(K)])
+    if painted.shape[2] == 1:
+        planes = planes[:, 0]
+    mean, var = ensemble_moments(planes)
+    return (mean, var, planes) if return_planes else (mean, var)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # From painted planes to one Compton-y map (process_SLICS.py:12-66), and the light cone end to end.
 
 _SLAB = 252.5                                     # comoving thickness of a SLICS slab in Mpc/h (process_SLICS.py:26, 29)
@@ -451,8 +572,10 @@ def paint_small_plane(painter, massplane, shift, delta_size, tile_size, mass_siz
 
 
 def _paint_small_plane_device(painter, massplane, shift, delta_size, tile_size, mass_size, n_pixel_tile, z, seed,
-                              tile_id, subtract_minimum, j, out, pixel_noise):
-    if not (hasattr(painter, "_paint_small_plane_device") and _streams(painter, z)):
+                              tile_id, subtract_minimum, j, out, pixel_noise, draws=None, return_planes=False,
+                              moments=True):
+    """``draws`` = K: the ensemble form (``paint_small_plane_ensemble``, which has checked the painter already)."""
+    if draws is None and not (hasattr(painter, "_paint_small_plane_device") and _streams(painter, z)):
         raise NotImplementedError("paint_small_plane(on_device=True) needs a painter with a device paint pipeline "
                                   "(CVAEPainter / CGANPainter .can_paint_stream)")
     import torch
@@ -481,6 +604,8 @@ def _paint_small_plane_device(painter, massplane, shift, delta_size, tile_size, 
     if seed is None:
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())
     kw = {"pixel_noise": True} if pixel_noise else {}
+    if draws is not None:
+        kw = {"draws": draws, "return_planes": return_planes, "moments": moments}
     return painter._paint_small_plane_device(plane, origin, cut, (geo["r0"], geo["c0"], geo["crop"]), z, tile_id, seed,
                                              subtract_minimum=subtract_minimum, field_index=j, out=out, **kw)
 
@@ -616,3 +741,164 @@ def paint_light_cone(painter, planes, z, delta_size, tile_size, n_pixel_tile, re
     if on_device and out is None:
         y_map = y_map.cpu().numpy()
     return (y_map, kept) if return_planes else y_map
+
+
+def paint_small_plane_ensemble(painter, massplane, shift, delta_size, tile_size, mass_size, n_pixel_tile, z, draws,
+                               seed=None, tile_id=0, subtract_minimum=False, field=None, pixel_noise=False,
+                               on_device=False, out=None, return_planes=False):
+    """``paint_small_plane`` for K = ``draws`` latent draws of its one tile: the central footprint of every draw, and
+    the moments across the K footprints (``ensemble_moments``): (mean, var), float64 (m, m), and with
+    ``return_planes=True`` the K planes (K, m, m).  Draw l uses the Philox counter (g, l, ``tile_id``) under ``seed``:
+    plane 0 is ``paint_small_plane``'s for the same seed and id.  ``field`` as there.  Refusals as in
+    ``paint_plane_ensemble``; ``pixel_noise=True`` is not offered (NotImplementedError).
+
+    Host path: ``paint_small_plane``'s cut and zoom, ``painter.paint_ensemble(..., return_draws=True)``, the crop per
+    draw.  ``on_device=True``: minimum, cut, zoom, ``model.paint_graph(1, draws=K)``, one ``bp_tile_crop`` per draw and
+    ``bp_plane_moments`` on one stream; ``out`` = (mean, var), two CUDA float64 (m, m) tensors, receives the result
+    (nothing is downloaded; the planes, if asked for, are then a CUDA tensor).  As for single paintings, the device's
+    resampled tile is within one float32 rounding of the host's and not bit-equal to it."""
+    j = _field_index(painter, field)
+    K = _need_ensemble(painter, [z], draws, None, pixel_noise, on_device, "paint_small_plane_ensemble",
+                       "_paint_small_plane_device")
+    if on_device:
+        return _paint_small_plane_device(painter, massplane, shift, delta_size, tile_size, mass_size, n_pixel_tile, z,
+                                         seed, tile_id, subtract_minimum, j, out, False, draws=K,
+                                         return_planes=return_planes)
+    if out is not None:
+        raise ValueError("out= needs on_device=True")
+    import scipy.ndimage
+    tile = get_tile(massplane, shift, tile_relative_size=delta_size / mass_size,
+                    expansion_factor=tile_size / delta_size)
+    if subtract_minimum:
+        tile = tile - tile.min()
+    tile = scipy.ndimage.zoom(tile, zoom=n_pixel_tile / tile.shape[0], mode="mirror")
+    if tile.shape != (n_pixel_tile, n_pixel_tile):
+        raise ValueError(f"the expanded tile zooms to {tile.shape}, not to {n_pixel_tile} pixels")
+    painted = painter.paint_ensemble(np.asarray(tile, dtype=np.float32)[None], z, draws=K, batch_size=K,
+                                     tile_ids=np.array([tile_id], dtype=np.int64), seed=_fresh_seed(seed),
+                                     return_draws=True)[2][0]
+    if j is not None:
+        painted = painted[:, j]
+    centre = (1 - delta_size / tile_size) / 2
+    planes = np.stack([get_tile(np.asarray(p, dtype=np.float64), shift=(centre, centre),
+                                tile_relative_size=delta_size / tile_size) for p in painted])
+    mean, var = ensemble_moments(planes)
+    return (mean, var, planes) if return_planes else (mean, var)
+
+
+def _check_map_pair(out, resolution, device):
+    if not (isinstance(out, (tuple, list)) and len(out) == 2):
+        raise ValueError("out must be the pair (y_mean, y_var)")
+    for t in out:
+        _check_map(t, resolution, device)
+    if out[0].data_ptr() == out[1].data_ptr():
+        raise ValueError("out must be two different tensors")
+
+
+def paint_light_cone_ensemble(painter, planes, z, delta_size, tile_size, n_pixel_tile, resolution, scales, draws,
+                              min_tile_overlap=0.5, falloff=0.05, sigma=0.5, regularise_std=None, batch_size=64, order=3,
+                              subtract_minimum=False, on_device=False, seed=None, out=None, field=None,
+                              pixel_noise=False, small_planes_on_device=False, return_maps=False):
+    """The conditional mean and scatter of the Compton-y map of a light cone at fixed dark matter: ``paint_light_cone``
+    with K = ``draws`` latent draws of every tile.  Every plane is painted as an ensemble (``paint_plane_ensemble`` /
+    ``paint_small_plane_ensemble``), draw k's finished plane is projected into y map k exactly as ``paint_light_cone``
+    projects, and after the last plane the moments are taken across the K maps: returns (y_mean, y_var), float64
+    (resolution, resolution), ``y_var`` the population variance (``ensemble_moments``); ``return_maps=True`` adds the K
+    maps (K, resolution, resolution).  Painted planes are not returned.
+
+    Tile ids are allocated as ``paint_light_cone`` allocates them, and draw l of a tile uses the counter (g, l, id)
+    under the one key ``seed``: map 0 is ``paint_light_cone``'s map for the same seed.  ``batch_size`` counts generator
+    samples: K must divide it.  Refusals as in ``paint_plane_ensemble`` (checked at every redshift, before any random
+    number is drawn), and ``pixel_noise=True`` is not offered (NotImplementedError).
+
+    ``on_device=True`` (orders 2 to 5): the K finished planes stay in the painter's accumulators (divided in place),
+    ``bp_plane_project_order`` adds plane k into map k of a (K, resolution, resolution) device buffer on the same
+    stream, and ``bp_plane_moments`` reduces the maps; only the moments (and the maps, if asked for) are downloaded.
+    ``out`` = (y_mean, y_var): two CUDA float64 (resolution, resolution) tensors that are FILLED (the moments of an
+    accumulated map would mean nothing) and returned; the maps are then a CUDA tensor.  ``small_planes_on_device`` as in
+    ``paint_light_cone``: without it small planes take the host path of ``paint_small_plane_ensemble`` and their K
+    planes are uploaded."""
+    z, delta_size = list(z), list(delta_size)
+    if not len(z) == len(delta_size) == len(scales):
+        raise ValueError("z, delta_size and scales need one entry per plane")
+    j = _field_index(painter, field)
+    K = _need_ensemble(painter, z, draws, batch_size, pixel_noise, on_device, "paint_light_cone_ensemble")
+    if out is not None and not on_device:
+        raise ValueError("out= needs on_device=True")
+    if small_planes_on_device and not on_device:
+        raise ValueError("small_planes_on_device=True needs on_device=True")
+    if on_device:
+        if order not in _DEVICE_ORDERS:
+            raise NotImplementedError("paint_light_cone_ensemble(on_device=True) resamples with splines of order 2 to 5 "
+                                      "only")
+        import torch
+        dev = torch.device(painter.model.device)
+        if out is not None:
+            _check_map_pair(out, resolution, dev)
+        y_maps = torch.zeros((K, resolution, resolution), dtype=torch.float64, device=dev)
+    else:
+        y_maps = np.zeros((K, resolution, resolution))
+    seed = _fresh_seed(seed)
+    tile_id = 0
+    n_done = 0
+    for i, entry in enumerate(planes):
+        if i >= len(z):
+            raise ValueError("more planes than redshifts")
+        n_done += 1
+        if delta_size[i] >= tile_size:
+            rel = tile_size / delta_size[i]
+            geo = plane_geometry(entry.shape[0], rel, n_pixel_tile, min_tile_overlap)
+            kw = dict(min_tile_overlap=min_tile_overlap, falloff=falloff, sigma=sigma, regularise_std=regularise_std,
+                      batch_size=batch_size, seed=seed, first_tile_id=tile_id)
+            tile_id += geo["n_side"] ** 2
+            if on_device:
+                drawn = _paint_plane_ensemble_planes(painter, entry, geo, n_pixel_tile, z[i], K, **kw)
+            else:
+                drawn = paint_plane_ensemble(painter, entry, rel, n_pixel_tile, z[i], K, return_planes=True, **kw)[2]
+            if j is not None:
+                drawn = drawn[:, j]                              # (K contiguous slices of the fields' planes)
+        else:
+            massplane, shift, mass_size = entry
+            args = (painter, massplane, shift, delta_size[i], tile_size, mass_size, n_pixel_tile, z[i])
+            kw = dict(seed=seed, tile_id=tile_id, subtract_minimum=subtract_minimum)
+            tile_id += 1
+            if small_planes_on_device:                           # one stream from the cut to the projection
+                drawn = _paint_small_plane_device(*args, j=j, out=None, pixel_noise=False, draws=K, moments=False, **kw)
+            else:
+                if on_device:                                    # paint_ensemble copies on streams of its own
+                    torch.cuda.current_stream(dev).synchronize()
+                drawn = paint_small_plane_ensemble(*args, K, field=field, return_planes=True, **kw)[2]
+                if on_device:
+                    drawn = torch.from_numpy(np.ascontiguousarray(drawn)).to(dev)
+        for k in range(K):
+            if on_device:
+                _project_device(drawn[k], scales[i], y_maps[k], order)
+            else:
+                _project_host(y_maps[k], drawn[k], scales[i], order)
+    if n_done != len(z):
+        raise ValueError("fewer planes than redshifts")
+    if not on_device:
+        mean, var = ensemble_moments(y_maps)
+        return (mean, var, y_maps) if return_maps else (mean, var)
+    import ctypes as C
+    from . import _lib as L
+    from .painter import _plane_moments
+    with torch.no_grad(), torch.cuda.device(dev):
+        sm = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        return _plane_moments(L.load(), y_maps, None, K, (resolution, resolution), out, y_maps if return_maps else None,
+                              sm)
+
+
+def _paint_plane_ensemble_planes(painter, delta, geo, n_pixel_tile, z, K, min_tile_overlap, falloff, sigma,
+                                 regularise_std, batch_size, seed, first_tile_id):
+    """The K finished planes of one tiled plane of a light-cone ensemble, on the device: a (K, [F,] n_plane, n_plane)
+    CUDA tensor in the painter's accumulator, valid until the painter paints its next plane."""
+    n_plane, cut, n_tiles = geo["n_plane"], geo["cut"], len(geo["origins"])
+    if cut != n_pixel_tile and int(round(cut * (n_pixel_tile / cut))) != n_pixel_tile:
+        raise ValueError(f"a {cut}-pixel cut does not zoom to {n_pixel_tile} pixels")
+    if (geo["dst"] + n_pixel_tile > n_plane).any():
+        raise ValueError("the tiling does not fit the plane")
+    ids = first_tile_id + np.arange(n_tiles, dtype=np.int64)
+    w = make_weight_map((n_pixel_tile, n_pixel_tile), falloff=falloff, sigma=sigma)
+    return painter._paint_plane_device(delta, geo, z, w, batch_size=min(int(batch_size) // K, n_tiles), tile_ids=ids,
+                                       seed=seed, regularise_std=regularise_std, draws=K, moments=False)

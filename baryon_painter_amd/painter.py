@@ -53,7 +53,7 @@ class Painter:
         parameter blocks plus up to four (batch, 1, H, W) fp32 buffers, 256 MiB of pinned memory at batch 64 of 512^2
         tiles ((batch, F, H, W) on the output side of a painter with F label fields), which otherwise live as long as the
         painter (page-locking them costs tens of milliseconds per call, hence the cache) -- and
-        ``_paint_plane_device``'s accumulators and scratch."""
+        ``_paint_plane_device``'s accumulators and scratch, the K accumulator pairs of a plane ensemble included."""
         self.__dict__.pop("_paint_host_buffers", None)
         self.__dict__.pop("_plane_device_buffers", None)
 
@@ -112,8 +112,18 @@ class Painter:
                                         out, scales, modes)
         return (result, (lo, hi)) if world_size > 1 else result
 
+    def _ensemble_parameters(self, zs, pixel_noise):
+        """``_device_paint_parameters(zs, ensemble=True)`` for the plane ensembles: NotImplementedError for a painter
+        without ``paint_ensemble`` (no latent to draw from) and for ``pixel_noise``.  No side effects."""
+        if not hasattr(self, "paint_ensemble"):
+            raise NotImplementedError(f"{type(self).__name__} has no latent to draw an ensemble from")
+        if pixel_noise:
+            raise NotImplementedError("an ensemble of planes has no pixel noise: an ensemble block has no noise_org, so "
+                                      "overlapping tiles could not share their noise lattice")
+        return self._device_paint_parameters(zs, ensemble=True)
+
     def _paint_plane_device(self, delta, geo, z, weight_map, batch_size, tile_ids, seed, regularise_std=None, out=None,
-                            pixel_noise=False):
+                            pixel_noise=False, draws=None, return_planes=False, moments=True):
         """The device form of ``lightcone.paint_plane`` (on_device=True): ``geo`` is ``lightcone.plane_geometry``'s,
         ``weight_map`` the host's ``make_weight_map`` (float64, uploaded as it is), ``tile_ids`` / ``seed`` / ``batch_size``
         those the host path hands to ``paint_stream``.  Per batch, on ONE stream: the tiles are cut (and resampled) from
@@ -123,7 +133,14 @@ class Painter:
         float64 tensor of that shape) filled in place.  A painter with F > 1 label fields blends its (B, F, tile, tile)
         ``out`` with bp_plane_blend_fields, each field into a plane of its own with its own regularisation mask: the
         plane, and ``out``, is (F, n_plane, n_plane).  ``pixel_noise``: as on the host path, every tile draws from the
-        lattice ``tile_ids[0]`` at its destination origin ``geo["dst"]``."""
+        lattice ``tile_ids[0]`` at its destination origin ``geo["dst"]``.
+
+        ``draws`` = K (``lightcone.paint_plane_ensemble``; a painter with ``paint_ensemble``, NotImplementedError
+        otherwise and with ``pixel_noise``; ``batch_size`` then counts TILES per batch): every draw is blended into a
+        plane of its own and the moments are taken across the K planes (``_paint_plane_ensemble_pipeline``).  Returns
+        (mean, var), with ``return_planes`` (mean, var, planes), planes (K, [F,] n_plane, n_plane); ``out`` is the pair
+        (mean, var) of CUDA float64 tensors.  ``moments=False``: the K finished planes alone, as a CUDA tensor that
+        lives in the cached accumulator until the next plane is painted.  Without ``draws`` nothing changes."""
         model = self.model
         model.train(False)
         tile, W = self._tile_shape()
@@ -131,6 +148,11 @@ class Painter:
             raise NotImplementedError("device planes need square tiles")
         if tuple(weight_map.shape) != (tile, tile):
             raise ValueError(f"weight map {weight_map.shape} does not match the model's {tile}^2 tiles")
+        if draws is not None:
+            K = PG.check_draws(draws)
+            params, scales, modes = self._ensemble_parameters(np.full(len(geo["origins"]), float(z)), pixel_noise)
+            return _paint_plane_ensemble_pipeline(self, model, tile, delta, geo, int(batch_size), K, params, tile_ids, seed,
+                                                  weight_map, regularise_std, out, scales, modes, return_planes, moments)
         if pixel_noise:
             self._need_pixel_noise()
         params, scales, modes = self._device_paint_parameters(np.full(len(geo["origins"]), float(z)))
@@ -143,7 +165,8 @@ class Painter:
                                      regularise_std, out, scales, modes)
 
     def _paint_small_plane_device(self, plane, origin, size, crop, z, tile_id, seed, subtract_minimum=False,
-                                  field_index=None, out=None, pixel_noise=False):
+                                  field_index=None, out=None, pixel_noise=False, draws=None, return_planes=False,
+                                  moments=True):
         """The device form of ``lightcone.paint_small_plane`` (on_device=True), on ONE stream and without a host
         synchronisation: ``plane`` is a contiguous 2-d CUDA float32 / float64 tensor on the model's device -- the
         periodic mass plane, or a window of it that the caller gathered -- and ``origin`` = (x0, y0), ``size`` the
@@ -153,12 +176,22 @@ class Painter:
         ``model.paint_graph(1)`` (bp_window_zoom), the parameter block of one tile with ``paint_stream``'s seed word and
         ``tile_id`` -- with ``pixel_noise`` the lattice ``tile_id`` at origin (0, 0), as on the host path -- the replay,
         and the crop of label field ``field_index`` (None: the only one) of the slot's ``out`` (bp_tile_crop).  Returns
-        the (m, m) float64 plane as NumPy, or ``out`` (a CUDA float64 (m, m) tensor) filled in place."""
+        the (m, m) float64 plane as NumPy, or ``out`` (a CUDA float64 (m, m) tensor) filled in place.
+
+        ``draws`` = K (``lightcone.paint_small_plane_ensemble``; refusals, ``out``, ``return_planes`` and ``moments`` as in
+        ``_paint_plane_device``): ``model.paint_graph(1, draws=K)`` with its draws, one crop per draw into (K, m, m) and
+        ``bp_plane_moments`` across them.  Without ``draws`` nothing changes."""
         model = self.model
         model.train(False)
         tile, W = self._tile_shape()
         if tile != W:
             raise NotImplementedError("device planes need square tiles")
+        if draws is not None:
+            K = PG.check_draws(draws)
+            params, scales, modes = self._ensemble_parameters(np.full(1, float(z)), pixel_noise)
+            return _paint_small_plane_pipeline(self, model, tile, plane, origin, int(size), crop, params,
+                                               np.array([tile_id], dtype=np.int64), seed, subtract_minimum, field_index,
+                                               out, scales, modes, ensemble=(K, return_planes, moments))
         if pixel_noise:
             self._need_pixel_noise()
         params, scales, modes = self._device_paint_parameters(np.full(1, float(z)))
@@ -604,8 +637,11 @@ class CVAEPainter(Painter):
         also a draw from the likelihood, draw k of a tile on the lattice ``noise_ids[i]`` [default: ``tile_ids[i]``] +
         (k << 40) at the origin (0, 0); the ids must lie in [0, 2^40) (ValueError before any capture).
 
-        Planes and light cones have no ensemble form: the moments of a feathered blend of overlapping tiles are not
-        the blend of the tiles' moments."""
+        These are the moments of TILES.  The moments of a feathered blend of overlapping tiles are not the blend of the
+        tiles' moments (the blend runs in physical units behind a non-linear inverse), so planes and light cones do
+        not blend ``mean`` and ``var``: ``lightcone.paint_plane_ensemble``, ``paint_small_plane_ensemble`` and
+        ``paint_light_cone_ensemble`` blend, or project, every draw on its own and take the moments across the K
+        planes, or y maps."""
         K = PG.check_draws(draws)
         B = int(batch_size)
         if B < K or B % K:
@@ -1104,11 +1140,133 @@ def _paint_plane_pipeline(painter, model, tile, delta, geo, B, params, tile_ids,
         return result.cpu().numpy()
 
 
+def _check_moments_out(out, shape, dev):
+    """``out`` of an ensemble: None, or the pair (mean, var) of two different contiguous CUDA float64 tensors of ``shape``
+    on ``dev`` (ValueError)."""
+    if out is None:
+        return
+    dev = torch.device(dev)
+    if not (isinstance(out, (tuple, list)) and len(out) == 2 and
+            all(isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.float64 and
+                tuple(t.shape) == tuple(shape) and t.is_contiguous() for t in out) and
+            out[0].data_ptr() != out[1].data_ptr()):
+        raise ValueError(f"out must be a pair (mean, var) of contiguous float64 ({', '.join(str(v) for v in shape)}) "
+                         f"tensors on {dev}")
+
+
+def _plane_moments(lib, acc, wsum, K, shape, out, planes, sm):
+    """``bp_plane_moments`` on stream ``sm`` over the contiguous CUDA float64 (K, *shape) ``acc`` and ``wsum`` (None: the
+    draws are ``acc`` itself, nothing is divided).  ``planes``: None, a (K, *shape) tensor that receives the K quotients,
+    or ``acc`` itself where ``wsum`` is None.  Returns (mean, var[, planes]): ``out`` = (mean, var) filled, everything
+    left on the device; without ``out`` NumPy arrays."""
+    from . import _lib as L
+    mean, var = out if out is not None else (torch.empty(shape, dtype=torch.float64, device=acc.device) for _ in range(2))
+    L.check(lib.bp_plane_moments(L.ptr(acc), L.ptr(wsum), K, int(np.prod(shape)), L.ptr(mean), L.ptr(var),
+                                 L.ptr(planes if planes is not acc else None), sm), "plane moments")
+    res = (mean, var) + ((planes,) if planes is not None else ())
+    if out is not None:
+        return res
+    return tuple(t.cpu().numpy() for t in res)
+
+
+def _paint_plane_ensemble_pipeline(painter, model, tile, delta, geo, B, K, params, tile_ids, seed, weight_map,
+                                   regularise_std, out, scales=None, modes=None, return_planes=False, moments=True):
+    """The ensemble form of ``_paint_plane_pipeline`` (``lightcone.paint_plane_ensemble(on_device=True)``): one plane
+    through ``model.paint_graph(B, draws=K)`` with its draws, ``B`` TILES per batch.  Per batch on ONE stream: cut,
+    parameter block (the four-double records of an ensemble block), replay, and ``bp_plane_blend_fields`` with
+    ``fields = K F`` over the slot's (B, K, F, tile, tile) ``draws`` into the (K, F, n_plane, n_plane) float64
+    accumulators -- the bits of plane (k, f) are ``bp_plane_blend``'s on draw k's tiles of field f.  Then
+    ``bp_plane_moments`` across the K planes: (mean, var[, planes]) as NumPy arrays, (n_plane, n_plane) and
+    (K, n_plane, n_plane), with a leading F behind K for F > 1 label fields; or ``out`` = (mean, var), CUDA float64
+    tensors, filled and returned (the planes then stay a CUDA tensor too).  ``moments=False``: the accumulators are
+    divided in place (``bp_plane_finish``) and returned, a (K, [F,] n_plane, n_plane) CUDA tensor that is valid until the
+    next plane of this painter is painted.
+
+    Memory: the accumulators are ``16 K F n_plane^2`` bytes (4.3 GB at 4096^2 and K = 16, F = 1), cached beside
+    ``_paint_plane_pipeline``'s until ``release_paint_buffers()``; ``return_planes`` adds ``8 K F n_plane^2``."""
+    import ctypes as C
+    from . import _lib as L
+    dev = model.device
+    cut, n_plane = geo["cut"], geo["n_plane"]
+    n = len(geo["origins"])
+    F = _n_fields(modes)
+    field = (F,) if F > 1 else ()
+    shape = (*field, n_plane, n_plane)
+    if isinstance(delta, torch.Tensor):
+        if delta.device != torch.device(dev):
+            raise ValueError(f"delta lives on {delta.device}, the painter on {dev}")
+        d = delta if delta.is_contiguous() else delta.contiguous()
+    else:
+        d = torch.from_numpy(np.ascontiguousarray(delta)).to(dev)
+    if d.dim() != 2 or d.dtype not in (torch.float32, torch.float64):
+        raise TypeError("delta must be a 2-d float32 or float64 plane")
+    _check_moments_out(out, shape, dev)
+    g = _paint_graph(model, B, scales, modes, False, {"draws": K, "return_draws": True})
+    block = g["param_block"]
+    n_batches = (n + B - 1) // B
+    blocks = torch.zeros((n_batches, g["block_bytes"]), dtype=torch.uint8)
+    for bi in range(n_batches):
+        hv = block.views(blocks[bi])
+        hv["seed"][0] = PG.seed_word(seed)
+        _fill_block(hv, params, tile_ids, bi * B, min(bi * B + B, n), B)
+    lib = L.load()
+    # the accumulators of the K planes are kept between calls, beside _paint_plane_pipeline's buffers and in their
+    # place: one large set at a time (release_paint_buffers() frees them)
+    cache = painter.__dict__.setdefault("_plane_device_buffers", {})
+    ws = int(lib.bp_plane_cut_workspace(B, cut, tile))
+    key = ("ensemble", K, n_plane, B, ws, str(dev), F)
+    if key not in cache:
+        for k in [k for k in cache if k[0] != "small"]:
+            del cache[k]
+        cache[key] = {"acc": torch.empty((K, F, n_plane, n_plane), dtype=torch.float64, device=dev),
+                      "wsum": torch.empty((K, F, n_plane, n_plane), dtype=torch.float64, device=dev),
+                      "scratch": torch.empty(max(ws // 8, 1), dtype=torch.float64, device=dev),
+                      "stats": torch.empty(2 * B * K * F, dtype=torch.float64, device=dev)}
+    buf = cache[key]
+    acc, wsum = buf["acc"], buf["wsum"]
+    with torch.no_grad():
+        blocks_d = blocks.to(dev)
+        org_d = torch.from_numpy(geo["origins"]).to(dev)
+        dst_d = torch.from_numpy(geo["dst"]).to(dev)
+        w_d = torch.from_numpy(np.ascontiguousarray(weight_map, dtype=np.float64)).to(dev)
+        acc.zero_()
+        wsum.zero_()
+        sm = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        dtype = L.F32 if d.dtype == torch.float32 else L.F64
+        reg = regularise_std is not None
+        rows, cols = d.shape
+        for bi in range(n_batches):
+            a, b = bi * B, min(bi * B + B, n)
+            m = b - a
+            gs = g["slots"][bi % 2]               # (one stream: the slots' reuse is ordered by the stream itself)
+            L.check(lib.bp_plane_cut(L.ptr(d), dtype, rows, cols, C.c_void_p(org_d.data_ptr() + 8 * a), m, cut,
+                                     tile, L.ptr(buf["scratch"]), ws, L.ptr(gs["raw"]), sm), "plane cut")
+            gs["block"].copy_(blocks_d[bi])
+            gs["graph"].replay()
+            box = geo["dst"][a:b]
+            # tile t's planes (k, f) are the K F "fields" of the blend: tiles[t * K F + k F + f] into plane k F + f
+            L.check(lib.bp_plane_blend_fields(L.ptr(gs["draws"]), m, K * F, tile, C.c_void_p(dst_d.data_ptr() + 8 * a),
+                                              int(box[:, 0].min()), int(box[:, 1].min()), int(box[:, 0].max()) + tile,
+                                              int(box[:, 1].max()) + tile, L.ptr(w_d), 1 if reg else 0,
+                                              float(regularise_std) if reg else 0.0, L.ptr(buf["stats"]), L.ptr(acc),
+                                              L.ptr(wsum), n_plane, n_plane, sm), "plane blend of the draws")
+        if not moments:                           # (finish_kernel reads and writes element i in one thread: in place)
+            L.check(lib.bp_plane_finish(L.ptr(acc), L.ptr(wsum), K * F * n_plane * n_plane, L.ptr(acc), sm),
+                    "plane finish of the draws")
+            return acc.view(K, *shape)
+        planes = torch.empty((K, *shape), dtype=torch.float64, device=dev) if return_planes else None
+        return _plane_moments(lib, acc, wsum, K, shape, out, planes, sm)
+
+
 def _paint_small_plane_pipeline(painter, model, tile, plane, origin, size, crop, params, ids, seed, subtract_minimum,
-                                field_index, out, scales=None, modes=None):
+                                field_index, out, scales=None, modes=None, ensemble=None):
     """One tile through ``model.paint_graph(1)`` on the device (``Painter._paint_small_plane_device``): minimum, zoom
     into slot 0's ``raw``, parameter block, replay, crop, on ONE stream.  ``modes`` of F > 1 label fields: the slot's
-    ``out`` is (1, F, tile, tile) and ``field_index`` says which field is cropped."""
+    ``out`` is (1, F, tile, tile) and ``field_index`` says which field is cropped.  ``ensemble`` = (K, return_planes,
+    moments): ``model.paint_graph(1, draws=K)`` with its ``draws`` (1, K, F, tile, tile), the field cropped once per draw
+    into (K, m, m) float64, and ``bp_plane_moments`` without weights across them: (mean, var[, planes]) as NumPy, or
+    ``out`` = (mean, var) filled (the planes then stay a CUDA tensor); ``moments`` False: the (K, m, m) CUDA tensor
+    alone."""
     import ctypes as C
     from . import _lib as L
     dev = torch.device(model.device)
@@ -1120,10 +1278,14 @@ def _paint_small_plane_pipeline(painter, model, tile, plane, origin, size, crop,
             plane.dtype not in (torch.float32, torch.float64)):
         raise TypeError(f"the plane must be a contiguous 2-d float32 or float64 tensor on {dev}")
     r0, c0, m = (int(v) for v in crop)
-    if out is not None and (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.float64 or
-                            tuple(out.shape) != (m, m) or not out.is_contiguous()):
+    if ensemble is not None:
+        K = ensemble[0]
+        _check_moments_out(out, (m, m), dev)
+    elif out is not None and (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.float64 or
+                              tuple(out.shape) != (m, m) or not out.is_contiguous()):
         raise ValueError(f"out must be a contiguous float64 ({m}, {m}) tensor on {dev}")
-    g = _paint_graph(model, 1, scales, modes, "noise_ids" in params)
+    g = _paint_graph(model, 1, scales, modes, "noise_ids" in params,
+                     None if ensemble is None else {"draws": K, "return_draws": True})
     block = g["param_block"]
     blk = torch.zeros(g["block_bytes"], dtype=torch.uint8)
     hv = block.views(blk)
@@ -1141,7 +1303,10 @@ def _paint_small_plane_pipeline(painter, model, tile, plane, origin, size, crop,
                       "min_scratch": torch.empty(ws_min // 8, dtype=torch.float64, device=dev),
                       "min": torch.empty(1, dtype=torch.float64, device=dev)}
     buf = cache[key]
-    result = out if out is not None else torch.empty((m, m), dtype=torch.float64, device=dev)
+    if ensemble is not None:
+        result = torch.empty((K, m, m), dtype=torch.float64, device=dev)
+    else:
+        result = out if out is not None else torch.empty((m, m), dtype=torch.float64, device=dev)
     with torch.no_grad(), torch.cuda.device(dev):
         sm = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         dtype = L.F32 if plane.dtype == torch.float32 else L.F64
@@ -1157,6 +1322,13 @@ def _paint_small_plane_pipeline(painter, model, tile, plane, origin, size, crop,
                                    buf["scratch"].numel() * 8, L.ptr(gs["raw"]), sm), "window zoom")
         gs["block"].copy_(blk.to(dev))
         gs["graph"].replay()
+        if ensemble is not None:
+            for k in range(K):                        # draw k, field j of the slot's (1, K, F, tile, tile) draws
+                img = C.c_void_p(gs["draws"].data_ptr() + 4 * (k * F + j) * tile * tile)
+                L.check(lib.bp_tile_crop(img, tile, r0, c0, m, L.ptr(result[k]), sm), "tile crop")
+            if not ensemble[2]:
+                return result
+            return _plane_moments(lib, result, None, K, (m, m), out, result if ensemble[1] else None, sm)
         img = C.c_void_p(gs["out"].data_ptr() + 4 * j * tile * tile)
         L.check(lib.bp_tile_crop(img, tile, r0, c0, m, L.ptr(result), sm), "tile crop")
         if out is not None:

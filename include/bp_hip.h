@@ -530,6 +530,27 @@ int bp_plane_blend_fields(const float* tiles, int32_t n, int32_t fields, int32_t
                           void* stream);
 int bp_plane_finish(const double* acc, const double* wsum, int64_t count, double* out, void* stream);
 
+/* ---- ensembles of planes and y maps (lightcone.paint_plane_ensemble / paint_light_cone_ensemble) -----------------
+ * K draws of a plane are blended into K accumulator pairs (bp_plane_blend_fields with fields = K * F over the
+ * (n, K, F, tile, tile) draws of an ensemble graph), K draws of a light cone are projected into K maps; the moments
+ * across the K finished planes, or maps, are taken here.
+ *   bp_plane_moments: acc and wsum are (draws, count) float64, draw-major; count = fields * rows * cols of a plane or
+ *                     res * res of a map.  Per element i: P_k = acc[k][i] / wsum[k][i], or acc[k][i] where wsum is
+ *                     NULL; then, in float64 without contraction and in ascending k, bp_paint_store_moments' sums:
+ *                     S = ((P_0 + P_1) + ...) + P_{K-1}, M = S / K, Q = ((P_0 - M)^2 + (P_1 - M)^2) + ...,
+ *                     mean[i] = M, var[i] = Q / K (the population variance, np.var(ddof=0); two passes, no
+ *                     E[P^2] - M^2).  Plain IEEE: 0 / 0 = NaN where no tile reaches, as bp_plane_finish; a NaN or
+ *                     infinite draw gives what NumPy gives; draws = 1 gives var = +0 where P_0 is finite.  planes, where
+ *                     not NULL, (draws, count), receives the P_k.  One thread owns an element and all its draws, a
+ *                     grid-stride loop over count: one launch, no atomics, no workspace, the same inputs give the same
+ *                     bits.  Up to 16 quotients stay in registers between the two sums; more are read and divided a
+ *                     second time.  16-byte accesses where every pointer is 16-byte aligned and count is even, 8-byte
+ *                     ones otherwise; the bits do not depend on either choice.  mean, var and planes must not overlap
+ *                     acc or wsum.  With nothing launched or written: BP_EINVAL for a null acc, mean or var, draws < 1
+ *                     or count < 1; BP_EUNSUPPORTED for draws > 64.  No host synchronisation. */
+int bp_plane_moments(const double* acc, const double* wsum, int32_t draws, int64_t count, double* mean, double* var,
+                     double* planes, void* stream);
+
 /* ---- Compton-y map of a light cone (lightcone.project_planes(on_device=True), process_SLICS.py:55-64) -----------
  * A painted plane is resampled to the map's resolution and added into the y map on the device, right behind
  * bp_plane_finish on the same stream: only the finished map comes back.
