@@ -99,8 +99,12 @@ def paint_plane(painter, delta, tile_relative_size, n_pixel_tile, z, min_tile_ov
     CUDA tensor -- and its tiles are cut, resampled (csrc/plane.hip), painted and blended on the device, with the same
     seeds, tile ids and batches as the host path; only the finished plane is downloaded.  ``out``: a CUDA float64
     (n_plane, n_plane) tensor that receives the plane instead (nothing is downloaded; ``out`` is returned).  The cut
-    without resampling and the blend give the host path's bits; the resampling is within 1 ulp (float32) of SciPy's;
-    with ``regularise_std`` the tile statistics are float64 sums where NumPy sums float32, so a pixel within about 1e-6
+    without resampling and the blend give the host path's bits; the resampling is the exact cubic spline under
+    half-sample symmetric boundaries, which for cuts of 12 pixels and more is SciPy's within 1 ulp (float32).  Below 12
+    SciPy's own "reflect" prefilter departs from the exact solve and the two paths differ by that much, relative to the
+    tile's largest value (measured on the CPU with SciPy 1.15.3, tests/test_plane_kernels_host.py): 6e-4, 1e-4, 7e-6,
+    3e-7, 5e-8, 2e-9, 3e-10, 1e-11, 5e-13 at cuts of 2 ... 10 pixels, 7e-15 at 12 (real planes cut hundreds).  With
+    ``regularise_std`` the tile statistics are float64 sums where NumPy sums float32, so a pixel within about 1e-6
     of the threshold may be kept by one path and dropped by the other.
 
     ``pixel_noise=True`` (a CVAEPainter whose model has a variance head; ValueError otherwise, before any random number

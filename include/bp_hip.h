@@ -502,7 +502,18 @@ int bp_likelihood_draw(const bp_view* mu, int32_t softplus, const bp_view* log_v
  *                    scipy.ndimage.zoom(cut_block, tile / cut, order=3, mode="reflect") in float64 (spline prefilter
  *                    along axis 0 then axis 1, tensor-product sampling at k (cut - 1) / (tile - 1)), rounded once to
  *                    float32; needs bp_plane_cut_workspace(n, cut, tile) bytes of `scratch` (less works in chunks of
- *                    tiles, down to one tile's share; BP_EWORKSPACE below that)
+ *                    tiles, down to one tile's share; BP_EWORKSPACE below that).  What is computed is the exact cubic
+ *                    spline under half-sample symmetric boundaries (the prefilter solves
+ *                    (c[k-1] + 4 c[k] + c[k+1]) / 6 = s[k] to rounding).  For cut >= 12 that is SciPy's zoom to
+ *                    1 float32 ulp.  Below 12 SciPy's own "reflect" prefilter departs from the exact solve, and the
+ *                    device differs from the host path (SciPy) by that much, relative to the tile's largest value
+ *                    (measured on the CPU, SciPy 1.15.3, tests/test_plane_kernels_host.py):
+ *                      cut   2     3     4     5     6     7     8     9     10    12    14
+ *                            6e-4  1e-4  7e-6  3e-7  5e-8  2e-9  3e-10 1e-11 5e-13 7e-15 2e-15
+ *                    BP_EINVAL for a null plane, origins or out, rows, cols, n, cut or tile <= 0, a dtype other than
+ *                    BP_F32 / BP_F64 and, where cut != tile, a null scratch or cut or tile of 1; then
+ *                    BP_EUNSUPPORTED for rows * cols, n * tile^2 or n * cut^2 >= 2^31; then BP_EWORKSPACE.  Nothing
+ *                    is written on a refusal
  *   bp_plane_blend : for t = 0 .. n-1 in order, acc[dst[t] + (i, j)] += w[i, j] * (double) tiles[t][i, j] and
  *                    wsum[...] += w[i, j], over the plane pixels of the bounding box [bx0, bx1) x [by0, by1) (pixels
  *                    of a tile outside it are not blended).  `weight` is the float64 (tile, tile) feathering map.

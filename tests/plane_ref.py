@@ -31,18 +31,30 @@ def prefilter_line(c):
         c[i] = z * (c[i + 1] - c[i])
 
 
+def exact_prefilter_line(s):
+    """The spline coefficients of one line by a dense solve of (c[k-1] + 4 c[k] + c[k+1]) / 6 = s[k] with
+    c[-1] = c[0] and c[n] = c[n-1] (half-sample symmetric boundaries).  For pinning prefilter_line only."""
+    s = np.asarray(s, np.float64)
+    n = len(s)
+    if n == 1:
+        return s.copy()
+    m = np.zeros((n, n))
+    for k in range(n):
+        m[k, k] += 4.0
+        m[k, max(k - 1, 0)] += 1.0
+        m[k, min(k + 1, n - 1)] += 1.0
+    return np.linalg.solve(m / 6.0, s)
+
+
 def prefilter(a):
-    """Both axes, axis 0 first (scipy.ndimage.spline_filter's order), in float64."""
+    """Both axes, axis 0 first (scipy.ndimage.spline_filter's order), in float64.  prefilter_line runs on all the
+    lines of an axis at once (c[i] is then a row of elements, one per line, and every operation is elementwise), which
+    leaves each line's operations and their order as they are."""
     c = np.array(a, dtype=np.float64)
-    for j in range(c.shape[1]):
-        line = c[:, j].copy()
-        prefilter_line(line)
-        c[:, j] = line
-    for i in range(c.shape[0]):
-        line = c[i].copy()
-        prefilter_line(line)
-        c[i] = line
-    return c
+    prefilter_line(c)                            # lines along axis 0
+    c = np.ascontiguousarray(c.T)
+    prefilter_line(c)                            # lines along axis 1
+    return np.ascontiguousarray(c.T)
 
 
 def _mirror(i, n):
@@ -85,6 +97,72 @@ def tile_stats(p):
     p = np.asarray(p, np.float64)
     m = p.mean()
     return m, np.sqrt(((p - m) ** 2).mean())
+
+
+RB = 256                                         # tile_stats_kernel's workgroup
+
+
+def _device_sum(v):
+    """tile_stats_kernel's fixed-order sum of a float64 vector: partial sum k adds v[k], v[k + 256], ... in turn from
+    0.0, then the halving tree red[i] += red[i + h], h = 128 ... 1."""
+    red = np.zeros(RB)
+    for a in range(0, len(v), RB):
+        part = v[a:a + RB]
+        red[:len(part)] = red[:len(part)] + part
+    h = RB // 2
+    while h > 0:
+        red[:h] = red[:h] + red[h:2 * h]
+        h //= 2
+    return red[0]
+
+
+def device_tile_stats(p):
+    """Mean and population standard deviation of a tile as tile_stats_kernel (csrc/plane.hip) sums them, in float64:
+    its strided partial sums and halving tree for the mean, then the same over (p - mean)^2."""
+    p = np.asarray(p, np.float64).ravel()
+    tt = float(len(p))
+    with np.errstate(invalid="ignore", over="ignore"):
+        mean = _device_sum(p) / tt
+        d = p - mean
+        return mean, np.sqrt(_device_sum(d * d) / tt)
+
+
+def blend_box(tiles, dst, rows, cols, weight, box, acc0, wsum0, stats=None, regularise_std=None):
+    """blend_kernel (csrc/plane.hip) pixel by pixel: over the pixels of box = (bx0, by0, bx1, by1) only, the tiles
+    (n, tile, tile) in ascending t, a += w * p then s += w in float64 with the product and the sum rounded separately,
+    starting from the prior content acc0 / wsum0 (rows, cols).  Tiles may lie partly or wholly outside the plane or the
+    box.  regularise_std: w = 0 where |p - mean| > std * regularise_std with stats[t] = (mean, std), by default
+    device_tile_stats of the tile (a comparison with a NaN is false: the weight is kept).  Returns (acc, wsum)."""
+    t = tiles.shape[-1]
+    bx0, by0, bx1, by1 = box
+    assert 0 <= bx0 < bx1 <= rows and 0 <= by0 < by1 <= cols
+    acc, wsum = np.array(acc0, np.float64), np.array(wsum0, np.float64)
+    assert acc.shape == wsum.shape == (rows, cols)
+    for k, (p, (x, y)) in enumerate(zip(tiles, dst)):
+        x, y = int(x), int(y)
+        p = p.astype(np.float64)
+        w = np.array(weight, np.float64)
+        if regularise_std is not None:
+            m, s = device_tile_stats(p) if stats is None else stats[k]
+            with np.errstate(invalid="ignore"):
+                w[np.abs(p - m) > s * regularise_std] = 0.0
+        x0, x1, y0, y1 = max(x, bx0), min(x + t, bx1), max(y, by0), min(y + t, by1)
+        if x0 >= x1 or y0 >= y1:
+            continue
+        ws, ps = w[x0 - x:x1 - x, y0 - y:y1 - y], p[x0 - x:x1 - x, y0 - y:y1 - y]
+        with np.errstate(invalid="ignore", over="ignore"):
+            acc[x0:x1, y0:y1] = acc[x0:x1, y0:y1] + ws * ps
+            wsum[x0:x1, y0:y1] = wsum[x0:x1, y0:y1] + ws
+    return acc, wsum
+
+
+def cut_ref(plane, x0, y0, cut):
+    """lightcone.get_tile's wrap-around cut for any int32 origin: the cut x cut block of ``plane`` at (x0, y0), rows
+    modulo plane.shape[0] and columns modulo plane.shape[1], with int64 index arithmetic.  (The indices are reduced
+    before np.take sees them: its "wrap" walks an index into range one period at a time.)"""
+    ix = (np.int64(x0) + np.arange(cut, dtype=np.int64)) % plane.shape[0]
+    iy = (np.int64(y0) + np.arange(cut, dtype=np.int64)) % plane.shape[1]
+    return plane.take(ix, axis=0, mode="wrap").take(iy, axis=1, mode="wrap")
 
 
 def blend(tiles, dst, n_plane, weight_map, regularise_std=None):
