@@ -160,6 +160,8 @@ SIGNATURES = {
     "bp_plane_blend_fields": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32,
                                         C.c_int32, _P, C.c_int32, C.c_double, _P, _P, _P, C.c_int32, C.c_int32, _P]),
     "bp_plane_finish": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
+    "bp_tile_outliers": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_double, _P, _P, _P]),
+    "bp_tile_keep": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     "bp_plane_moments": (C.c_int, [_P, _P, C.c_int32, C.c_int64, _P, _P, _P, _P]),
     "bp_plane_project_order_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "bp_plane_project_order": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_double, C.c_int32, _P, C.c_size_t, _P, C.c_int32,

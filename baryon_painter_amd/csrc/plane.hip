@@ -10,6 +10,9 @@
 //                    one accumulator plane per field, each field with its own regularisation mask: one launch over
 //                    (field, pixel)
 //   bp_plane_finish  acc / wsum (0 / 0 = NaN where no tile reaches, as in the reference)
+//   bp_tile_outliers the blend's tile statistics and, per tile, how many pixels its regularisation mask zeroes
+//   bp_tile_keep     the problematic tiles of a batch (a non-zero count in any field), raw and painted, into a capped
+//                    buffer behind a device cursor that also counts the tiles the buffer has no room for
 // The whole file is compiled without floating-point contraction: the host expressions these kernels restate round
 // every product and every sum separately.
 #include "common.hpp"
@@ -146,36 +149,141 @@ __global__ __launch_bounds__(RB) void zoom_sample_kernel(const double* b, int cu
   out[i] = (float)v;
 }
 
-// mean and population standard deviation of each painted tile in float64, one workgroup per tile, a fixed-order
-// reduction (strided partial sums, then a tree over the workgroup): stats[2t] = mean, stats[2t + 1] = std
-__global__ __launch_bounds__(RB) void tile_stats_kernel(const float* tiles, int tt, double* stats) {
-  __shared__ double red[RB];
-  const float* p = tiles + (size_t)blockIdx.x * tt;
+// op(p[k]) for k = threadIdx.x, threadIdx.x + RB, ... < tt in ascending order, the plain strided loop's order; the loads
+// of eight strides are issued before the first of them is used (one workgroup walks a whole tile: with one load in
+// flight per thread the walk waits out a memory latency per stride)
+template <typename Op>
+__device__ __forceinline__ void strided(const float* p, int tt, Op op) {
+  constexpr int U = 8;
+  int k = threadIdx.x;
+  for (; k + (U - 1) * RB < tt; k += U * RB) {
+    float v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) v[u] = p[k + u * RB];
+#pragma unroll
+    for (int u = 0; u < U; ++u) op(v[u]);
+  }
+  for (; k < tt; k += RB) op(p[k]);
+}
+
+// mean and population standard deviation of one painted tile of tt pixels in float64, by one workgroup of RB threads
+// through `red`: a fixed-order reduction (strided partial sums, then a tree over the workgroup).  Every thread returns
+// with the same mean and the same sum of squared deviations; the std is sqrt(that / tt).  The one reduction behind the
+// blend's masks and the outlier counts
+__device__ __forceinline__ void tile_moments(const float* p, int tt, double* red, double& mean, double& ssq) {
   double s = 0.0;
-  for (int k = threadIdx.x; k < tt; k += RB) s += (double)p[k];
+  strided(p, tt, [&](float v) { s += (double)v; });
   red[threadIdx.x] = s;
   __syncthreads();
   for (int h = RB / 2; h > 0; h /= 2) {
     if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
     __syncthreads();
   }
-  const double mean = red[0] / (double)tt;
+  mean = red[0] / (double)tt;
   __syncthreads();
   s = 0.0;
-  for (int k = threadIdx.x; k < tt; k += RB) {
-    const double d = (double)p[k] - mean;
+  strided(p, tt, [&](float v) {
+    const double d = (double)v - mean;
     s += d * d;
-  }
+  });
   red[threadIdx.x] = s;
   __syncthreads();
   for (int h = RB / 2; h > 0; h /= 2) {
     if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+    __syncthreads();
+  }
+  ssq = red[0];
+}
+
+// one workgroup per tile: stats[2t] = mean, stats[2t + 1] = std
+__global__ __launch_bounds__(RB) void tile_stats_kernel(const float* tiles, int tt, double* stats) {
+  __shared__ double red[RB];
+  double mean, ssq;
+  tile_moments(tiles + (size_t)blockIdx.x * tt, tt, red, mean, ssq);
+  if (threadIdx.x == 0) {
+    stats[2 * blockIdx.x] = mean;
+    stats[2 * blockIdx.x + 1] = sqrt(ssq / (double)tt);
+  }
+}
+
+// tile_stats_kernel, and counts[t] = the number of pixels the blend's mask would zero in tile t: the blend's own
+// expression on the blend's own mean and std (a NaN anywhere compares false: count 0)
+__global__ __launch_bounds__(RB) void tile_outliers_kernel(const float* tiles, int tt, double reg_std, double* stats,
+                                                           int* counts) {
+  __shared__ double red[RB];
+  __shared__ int cnt[RB];
+  const float* p = tiles + (size_t)blockIdx.x * tt;
+  double mean, ssq;
+  tile_moments(p, tt, red, mean, ssq);
+  const double sd = sqrt(ssq / (double)tt);
+  int c = 0;
+  strided(p, tt, [&](float v) {
+    if (fabs((double)v - mean) > sd * reg_std) ++c;
+  });
+  cnt[threadIdx.x] = c;
+  __syncthreads();
+  for (int h = RB / 2; h > 0; h /= 2) {
+    if ((int)threadIdx.x < h) cnt[threadIdx.x] += cnt[threadIdx.x + h];
     __syncthreads();
   }
   if (threadIdx.x == 0) {
     stats[2 * blockIdx.x] = mean;
-    stats[2 * blockIdx.x + 1] = sqrt(red[0] / (double)tt);
+    stats[2 * blockIdx.x + 1] = sd;
+    counts[blockIdx.x] = cnt[0];
   }
+}
+
+// is tile t of the batch problematic: any of its `fields` counts non-zero
+__device__ __forceinline__ bool tile_flagged(const int* counts, int fields, int t) {
+  for (int f = 0; f < fields; ++f)
+    if (counts[(size_t)t * fields + f] != 0) return true;
+  return false;
+}
+
+// blockIdx.y = tile t of the batch; a problematic tile's rank among the batch's problematic tiles (those before it,
+// counted by the workgroup) plus *cursor is its slot; below cap, the blocks of the tile copy its raw tile and its
+// painted field tiles there, as V = float4 (16-byte) or float words: items of tt / (sizeof(V) / 4) per image
+template <typename V>
+__global__ __launch_bounds__(RB) void tile_keep_kernel(const float* raw, const float* painted, const int* counts, int fields,
+                                                       int tt, int first_index, int cap, const int* cursor,
+                                                       int* kept_index, float* kept_raw, float* kept_painted) {
+  __shared__ int cnt[RB];
+  const int t = blockIdx.y;
+  if (!tile_flagged(counts, fields, t)) return;
+  int c = 0;
+  for (int u = threadIdx.x; u < t; u += RB) c += tile_flagged(counts, fields, u) ? 1 : 0;
+  cnt[threadIdx.x] = c;
+  __syncthreads();
+  for (int h = RB / 2; h > 0; h /= 2) {
+    if ((int)threadIdx.x < h) cnt[threadIdx.x] += cnt[threadIdx.x + h];
+    __syncthreads();
+  }
+  const int64_t slot = (int64_t)*cursor + cnt[0];
+  if (slot < 0 || slot >= cap) return;
+  if (blockIdx.x == 0 && threadIdx.x == 0) kept_index[slot] = first_index + t;
+  constexpr int per = (int)(sizeof(V) / sizeof(float));
+  const size_t items = (size_t)tt / per;                     // per image
+  const V* sr = reinterpret_cast<const V*>(raw + (size_t)t * tt);
+  V* dr = reinterpret_cast<V*>(kept_raw + (size_t)slot * tt);
+  const V* sp = reinterpret_cast<const V*>(painted + (size_t)t * fields * tt);
+  V* dp = reinterpret_cast<V*>(kept_painted + (size_t)slot * fields * tt);
+  const size_t stride = (size_t)gridDim.x * RB;
+  for (size_t i = (size_t)blockIdx.x * RB + threadIdx.x; i < items; i += stride) dr[i] = sr[i];
+  for (size_t i = (size_t)blockIdx.x * RB + threadIdx.x; i < items * fields; i += stride) dp[i] = sp[i];
+}
+
+// behind tile_keep_kernel on the same stream: *cursor += the batch's problematic tiles (one workgroup)
+__global__ __launch_bounds__(RB) void tile_keep_advance_kernel(const int* counts, int n, int fields, int* cursor) {
+  __shared__ int cnt[RB];
+  int c = 0;
+  for (int u = threadIdx.x; u < n; u += RB) c += tile_flagged(counts, fields, u) ? 1 : 0;
+  cnt[threadIdx.x] = c;
+  __syncthreads();
+  for (int h = RB / 2; h > 0; h /= 2) {
+    if ((int)threadIdx.x < h) cnt[threadIdx.x] += cnt[threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *cursor += cnt[0];
 }
 
 // one thread per plane pixel of the batch's bounding box [bx0, bx1) x [by0, by1); the covering tiles in tile order
@@ -338,6 +446,47 @@ int bp_plane_blend_fields(const float* tiles, int32_t n, int32_t fields, int32_t
   hipLaunchKernelGGL(blend_fields_kernel, dim3(nblocks(total), fields), dim3(RB), 0, sm, tiles, n, fields, tile, dst, bx0,
                      by0, by1 - by0, (unsigned)total, weight, regularise ? 1 : 0, regularise_std, (const double*)stats,
                      acc, wsum, rows, cols);
+  BP_CHECK_LAUNCH();
+  return BP_OK;
+}
+
+int bp_tile_outliers(const float* tiles, int32_t n_images, int32_t tile, double regularise_std, double* stats,
+                     int32_t* counts, void* stream) {
+  if (!tiles || !stats || !counts || n_images < 1 || tile < 1 || !(regularise_std >= 0.0) || isinf(regularise_std))
+    return BP_EINVAL;
+  if ((int64_t)n_images * tile * tile >= ((int64_t)1 << 31)) return BP_EUNSUPPORTED;
+  hipLaunchKernelGGL(tile_outliers_kernel, dim3(n_images), dim3(RB), 0, bp_stream(stream), tiles, tile * tile,
+                     regularise_std, stats, counts);
+  BP_CHECK_LAUNCH();
+  return BP_OK;
+}
+
+int bp_tile_keep(const float* raw, const float* painted, const int32_t* counts, int32_t n, int32_t fields, int32_t tile,
+                 int32_t first_index, int32_t cap, int32_t* cursor, int32_t* kept_index, float* kept_raw,
+                 float* kept_painted, void* stream) {
+  if (!raw || !painted || !counts || !cursor || n < 1 || fields < 1 || tile < 1 || first_index < 0 || cap < 0 ||
+      (cap > 0 && (!kept_index || !kept_raw || !kept_painted)))
+    return BP_EINVAL;
+  if ((int64_t)n * fields * tile * tile >= ((int64_t)1 << 31) || n > 65535 ||                  // (grid y)
+      (int64_t)first_index + n >= ((int64_t)1 << 31))
+    return BP_EUNSUPPORTED;
+  const hipStream_t sm = bp_stream(stream);
+  const int tt = tile * tile;
+  if (cap > 0) {
+    const bool vec = tt % 4 == 0 && ((reinterpret_cast<uintptr_t>(raw) | reinterpret_cast<uintptr_t>(painted) |
+                                      reinterpret_cast<uintptr_t>(kept_raw) | reinterpret_cast<uintptr_t>(kept_painted)) &
+                                     15) == 0;
+    const int64_t items = (int64_t)(vec ? tt / 4 : tt) * fields;
+    const dim3 grid((unsigned)std::min<int64_t>((items + RB - 1) / RB, 64), n);
+    if (vec)
+      hipLaunchKernelGGL(tile_keep_kernel<float4>, grid, dim3(RB), 0, sm, raw, painted, counts, fields, tt, first_index, cap,
+                         (const int*)cursor, kept_index, kept_raw, kept_painted);
+    else
+      hipLaunchKernelGGL(tile_keep_kernel<float>, grid, dim3(RB), 0, sm, raw, painted, counts, fields, tt, first_index, cap,
+                         (const int*)cursor, kept_index, kept_raw, kept_painted);
+    BP_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(tile_keep_advance_kernel, dim3(1), dim3(RB), 0, sm, counts, n, fields, cursor);
   BP_CHECK_LAUNCH();
   return BP_OK;
 }

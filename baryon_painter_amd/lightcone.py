@@ -74,9 +74,81 @@ def _need_pixel_noise(painter):
     painter._need_pixel_noise()
 
 
+class ProblematicTile:
+    """One entry of ``TileReport.tiles``: a painted tile with a pixel more than ``regularise_std`` tile standard
+    deviations from its tile mean, in any field.  ``tile`` is its number in its plane's tiling, ``position`` = (j, k)
+    with ``tile = j * n_side + k``, ``tile_id`` the Philox counter it was painted under, ``plane`` the number of its
+    plane in a light cone (None from ``paint_plane``), ``z`` its redshift, ``input`` the raw (tile, tile) float32 tile
+    that was painted (resampled, where the plane is), ``painted`` the (tile, tile) -- (F, tile, tile) for a painter with
+    F > 1 label fields -- float32 painting, ``n_outliers`` the (F,) int32 counts of offending pixels per field.
+    ``as_tuple()`` is the tuple the reference appends (process_SLICS.py:214): (z, input, painted)."""
+    __slots__ = ("tile", "position", "tile_id", "plane", "z", "input", "painted", "n_outliers")
+
+    def __init__(self, tile, position, tile_id, plane, z, input, painted, n_outliers):
+        self.tile, self.position, self.tile_id, self.plane, self.z = tile, position, tile_id, plane, z
+        self.input, self.painted, self.n_outliers = input, painted, n_outliers
+
+    def as_tuple(self):
+        return self.z, self.input, self.painted
+
+
+class TileReport:
+    """What ``paint_plane`` / ``paint_light_cone`` (``return_problematic_tiles=True``) say about the painted tiles.
+    Per tile and field, (n_tiles, F) arrays: ``mean`` and ``std`` (float64; the population std) and ``n_outliers``
+    (int32), the number of pixels with ``abs(p - mean) > std * regularise_std`` -- the pixels ``regularise=True`` masks.
+    A tile is problematic if any of its fields has one.  ``n_problematic`` counts all problematic tiles; ``tiles`` holds
+    the first ``max_problematic_tiles`` of them as ``ProblematicTile``s, in ascending tile order.  From a light cone
+    the three arrays are lists with one array per tiled plane, ``planes`` the numbers of those planes in the cone."""
+
+    def __init__(self, regularise_std, mean, std, n_outliers, n_problematic, tiles, planes=None):
+        self.regularise_std, self.mean, self.std, self.n_outliers = regularise_std, mean, std, n_outliers
+        self.n_problematic, self.tiles, self.planes = n_problematic, tiles, planes
+
+
+def _check_report(regularise_std, return_problematic_tiles, max_problematic_tiles):
+    """The refusals of a report, before any random number is drawn: ValueError without a ``regularise_std``, for one
+    that is negative or not finite, and for a negative cap."""
+    if not return_problematic_tiles:
+        return
+    if regularise_std is None:
+        raise ValueError("return_problematic_tiles=True needs a regularise_std: it defines what a problematic tile is")
+    if not (np.isfinite(regularise_std) and regularise_std >= 0):
+        raise ValueError(f"return_problematic_tiles=True needs a finite regularise_std >= 0, got {regularise_std}")
+    if int(max_problematic_tiles) < 0:
+        raise ValueError("max_problematic_tiles must not be negative")
+
+
+def _entries(numbers, inputs, painted, n_outliers, n_side, first_tile_id, z, plane=None):
+    """``ProblematicTile``s of one plane: tile numbers, their raw and painted tiles, the plane's (n_tiles, F) counts."""
+    out = []
+    for t, raw, p in zip(numbers, inputs, painted):
+        t = int(t)
+        out.append(ProblematicTile(t, divmod(t, n_side), int(first_tile_id) + t, plane, z, raw, p, n_outliers[t].copy()))
+    return out
+
+
+def _report_host(tiles, painted, regularise_std, cap, n_side, first_tile_id, z):
+    """The report of the host path: NumPy's own statistics of the painted tiles (float32 sums, as ``_blend_host``'s
+    mask), (N, H, W) or (N, F, H, W)."""
+    p4 = painted[:, None] if np.ndim(painted) == 3 else painted
+    n, F = p4.shape[:2]
+    mean, std = np.empty((n, F)), np.empty((n, F))
+    count = np.empty((n, F), dtype=np.int32)
+    for t in range(n):
+        for f in range(F):
+            p = p4[t, f]
+            mean[t, f], std[t, f] = p.mean(), p.std()
+            count[t, f] = np.count_nonzero(np.abs(p - p.mean()) > p.std() * regularise_std)
+    bad = np.flatnonzero((count != 0).any(axis=1))
+    keep = bad[:cap]
+    entries = _entries(keep, [np.asarray(tiles[t]) for t in keep], [np.asarray(painted[t]) for t in keep], count, n_side,
+                       first_tile_id, z)
+    return TileReport(regularise_std, mean, std, count, len(bad), entries)
+
+
 def paint_plane(painter, delta, tile_relative_size, n_pixel_tile, z, min_tile_overlap=0.5, falloff=0.05,
                 sigma=0.5, regularise_std=None, batch_size=64, seed=None, first_tile_id=0, on_device=False, out=None,
-                pixel_noise=False):
+                pixel_noise=False, regularise=True, return_problematic_tiles=False, max_problematic_tiles=16):
     """Paint a periodic mass plane tile by tile and blend (the inner loop of ``process_SLICS``,
     process_SLICS.py:198-220): tiles are cut with wrap-around, resampled to the network's tile size
     if necessary, painted in batches, weighted by ``make_weight_map`` and accumulated.
@@ -115,12 +187,29 @@ def paint_plane(painter, delta, tile_relative_size, n_pixel_tile, z, min_tile_ov
     feathered blend, which would lower the scatter wherever tiles overlap (about half the plane at
     ``min_tile_overlap=0.5``).  The blend runs in physical units, behind the non-linear inverse transform: a blended
     pixel is a weighted mean of two monotone functions of one normal (each tile's own mean and variance at that
-    pixel), not exactly one draw."""
+    pixel), not exactly one draw.
+
+    ``regularise`` (with a ``regularise_std``): True, the default here, zeroes the blend weights of the pixels beyond
+    ``regularise_std`` tile standard deviations, as this function always has.  The reference's default is False
+    (process_SLICS.py:179): there ``regularise_std`` alone only DETECTS.  ``regularise=False`` is that detect-only mode:
+    the plane is blended unmasked and is the plane without ``regularise_std``, bit for bit.
+
+    ``return_problematic_tiles=True`` (needs a finite ``regularise_std`` >= 0 and ``max_problematic_tiles`` >= 0;
+    ValueError otherwise, before any random number is drawn or any graph is captured), on either path and for either
+    value of ``regularise``: returns (plane, report), a ``TileReport`` with every tile's mean, std and number of
+    offending pixels per field and the first ``max_problematic_tiles`` problematic tiles with their inputs and
+    paintings (the reference's ``return_problematic_tiles``, process_SLICS.py:212-216).  On the device the counts
+    are taken and the tiles set aside between the paint graph and the blend (``bp_tile_outliers``, ``bp_tile_keep``)
+    and downloaded once behind the finished plane; the statistics are the blend's own float64 ones, the host path's
+    NumPy's float32 sums, so the two reports agree outside the tie band above.  Without the flag nothing is added to the
+    plane's launches."""
+    _check_report(regularise_std, return_problematic_tiles, max_problematic_tiles)
     if pixel_noise:
         _need_pixel_noise(painter)
     if on_device:
         return _paint_plane_device(painter, delta, tile_relative_size, n_pixel_tile, z, min_tile_overlap, falloff,
-                                   sigma, regularise_std, batch_size, seed, first_tile_id, out, pixel_noise)
+                                   sigma, regularise_std, batch_size, seed, first_tile_id, out, pixel_noise, regularise,
+                                   int(max_problematic_tiles) if return_problematic_tiles else None)
     if out is not None:
         raise ValueError("out= needs on_device=True")
     n_plane = int(n_pixel_tile / tile_relative_size)
@@ -151,10 +240,16 @@ def paint_plane(painter, delta, tile_relative_size, n_pixel_tile, z, min_tile_ov
         if pixel_noise:
             noise["seed"] = seed                 # (None: paint_batch draws a fresh key)
         painted = painter.paint_batch(np.stack(tiles), z, batch_size=batch_size, **noise)
+    mask_std = regularise_std if regularise else None
     if np.ndim(painted) == 4:                    # (N, F, H, W): one plane per label field, each with its own mask
-        return np.stack([_blend_host(painted[:, f], slices, n_plane, falloff, sigma, regularise_std)
-                         for f in range(painted.shape[1])])
-    return _blend_host(painted, slices, n_plane, falloff, sigma, regularise_std)
+        plane = np.stack([_blend_host(painted[:, f], slices, n_plane, falloff, sigma, mask_std)
+                          for f in range(painted.shape[1])])
+    else:
+        plane = _blend_host(painted, slices, n_plane, falloff, sigma, mask_std)
+    if return_problematic_tiles:
+        return plane, _report_host(tiles, painted, regularise_std, int(max_problematic_tiles), len(origins),
+                                   first_tile_id, z)
+    return plane
 
 
 def _blend_host(painted, slices, n_plane, falloff, sigma, regularise_std):
@@ -176,7 +271,11 @@ def _blend_host(painted, slices, n_plane, falloff, sigma, regularise_std):
 
 
 def _paint_plane_device(painter, delta, tile_relative_size, n_pixel_tile, z, min_tile_overlap, falloff, sigma,
-                        regularise_std, batch_size, seed, first_tile_id, out, pixel_noise=False):
+                        regularise_std, batch_size, seed, first_tile_id, out, pixel_noise=False, regularise=True,
+                        report_cap=None, keep=None, plane_number=None):
+    """``paint_plane(on_device=True)``.  ``report_cap``: the plane's own report is built and (plane, report) returned.
+    ``keep`` (``paint_light_cone``): the cone's ``painter.TileKeep``, in which this plane, number ``plane_number`` of
+    the cone, leaves its counts and its problematic tiles on the device; nothing is downloaded here."""
     if not (hasattr(painter, "_paint_plane_device") and painter.can_paint_stream(z)):
         raise NotImplementedError("paint_plane(on_device=True) needs a painter with a device paint pipeline "
                                   "(CVAEPainter / CGANPainter .can_paint_stream)")
@@ -193,8 +292,36 @@ def _paint_plane_device(painter, delta, tile_relative_size, n_pixel_tile, z, min
     ids = first_tile_id + np.arange(n_tiles, dtype=np.int64)
     w = make_weight_map((n_pixel_tile, n_pixel_tile), falloff=falloff, sigma=sigma)
     kw = {"pixel_noise": True} if pixel_noise else {}
-    return painter._paint_plane_device(delta, geo, z, w, batch_size=min(batch_size, n_tiles), tile_ids=ids, seed=seed,
-                                       regularise_std=regularise_std, out=out, **kw)
+    if not regularise:
+        kw["regularise"] = False
+    own = keep is None and report_cap is not None
+    if own:
+        from .painter import TileKeep
+        keep = TileKeep(painter, n_pixel_tile, report_cap, regularise_std)
+    if keep is not None:
+        # a lone plane's slots are numbered from 0, a cone's by its running tile id (first_tile_id there)
+        kw["keep"] = keep.plane(0 if own else first_tile_id, n_tiles, geo["n_side"], first_tile_id, z, plane_number)
+    plane = painter._paint_plane_device(delta, geo, z, w, batch_size=min(batch_size, n_tiles), tile_ids=ids, seed=seed,
+                                        regularise_std=regularise_std, out=out, **kw)
+    return (plane, _report_device(keep)[0]) if own else plane
+
+
+def _report_device(keep):
+    """Download what a ``painter.TileKeep`` holds, once, and build one ``TileReport`` per plane it has seen (in the order
+    painted; each with the entries of that plane that fit the shared cap and ``n_problematic`` of that plane alone)."""
+    reports = []
+    for rec, mean, std, count, numbers, raws, painted in keep.download():
+        entries = _entries(numbers, raws, painted, count, rec["n_side"], rec["first_tile_id"], rec["z"], rec["plane"])
+        reports.append(TileReport(keep.regularise_std, mean, std, count,
+                                  int(np.count_nonzero((count != 0).any(axis=1))), entries))
+    return reports
+
+
+def _cone_report(regularise_std, reports, numbers):
+    """One report for a light cone from its tiled planes' reports, in plane order."""
+    return TileReport(regularise_std, [r.mean for r in reports], [r.std for r in reports],
+                      [r.n_outliers for r in reports], sum(r.n_problematic for r in reports),
+                      [e for r in reports for e in r.tiles], planes=list(numbers))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -617,7 +744,8 @@ def _paint_small_plane_device(painter, massplane, shift, delta_size, tile_size, 
 def paint_light_cone(painter, planes, z, delta_size, tile_size, n_pixel_tile, resolution, scales, min_tile_overlap=0.5,
                      falloff=0.05, sigma=0.5, regularise_std=None, batch_size=64, order=3, subtract_minimum=False,
                      on_device=False, seed=None, out=None, return_planes=False, field=None, pixel_noise=False,
-                     small_planes_on_device=False):
+                     small_planes_on_device=False, regularise=True, return_problematic_tiles=False,
+                     max_problematic_tiles=16):
     """Mass planes in, one y map out (``process_SLICS`` followed by ``create_y_map``'s loop, process_SLICS.py:147-220 and
     55-64): plane i of the light cone is painted at redshift ``z[i]`` and projected into the (resolution, resolution)
     map with the factor ``scales[i]`` (``y_map_scales``) at once; no list of painted planes is kept.
@@ -655,10 +783,19 @@ def paint_light_cone(painter, planes, z, delta_size, tile_size, n_pixel_tile, re
     ``pixel_noise=True`` is passed to every plane (``paint_plane`` / ``paint_small_plane``: ValueError for a painter
     without a variance head, before any random number is drawn): a tiled plane's noise lattice is its first tile id.
 
-    Returns the map, or (map, painted planes as host arrays) with ``return_planes=True``."""
+    ``regularise`` and ``return_problematic_tiles`` are passed to every tiled plane (``paint_plane``; ValueError without
+    a ``regularise_std``, before any random number is drawn).  The cone has ONE report (``TileReport``): its per-tile
+    arrays are lists with one array per tiled plane, its entries carry the plane's number and the cone's running tile
+    id, and ``max_problematic_tiles`` caps the cone, not each plane.  Small planes are one unmasked tile and contribute
+    nothing, as in the reference.  With ``on_device=True`` one keep buffer and one device cursor serve the whole cone:
+    nothing of the report is downloaded, and the stream is not synchronised for it, until the last plane is enqueued.
+
+    Returns the map, or (map, painted planes as host arrays) with ``return_planes=True``; with
+    ``return_problematic_tiles=True`` the report is appended: (map, report) or (map, planes, report)."""
     z, delta_size = list(z), list(delta_size)
     if not len(z) == len(delta_size) == len(scales):
         raise ValueError("z, delta_size and scales need one entry per plane")
+    _check_report(regularise_std, return_problematic_tiles, max_problematic_tiles)
     j = _field_index(painter, field)
     noise = {}
     if pixel_noise:
@@ -691,6 +828,8 @@ def paint_light_cone(painter, planes, z, delta_size, tile_size, n_pixel_tile, re
     kept = []
     tile_id = 0
     n_done = 0
+    cap = int(max_problematic_tiles)
+    reports, tiled, keep = [], [], None          # the tiled planes' reports (host path), their numbers, the device's keep
     for i, entry in enumerate(planes):
         if i >= len(z):
             raise ValueError("more planes than redshifts")
@@ -700,6 +839,8 @@ def paint_light_cone(painter, planes, z, delta_size, tile_size, n_pixel_tile, re
             geo = plane_geometry(entry.shape[0], rel, n_pixel_tile, min_tile_overlap)
             kw = dict(min_tile_overlap=min_tile_overlap, falloff=falloff, sigma=sigma, regularise_std=regularise_std,
                       batch_size=batch_size, seed=seed, first_tile_id=tile_id, **noise)
+            if not regularise:
+                kw["regularise"] = False
             tile_id += geo["n_side"] ** 2
             if on_device:
                 n_plane = geo["n_plane"]
@@ -707,8 +848,26 @@ def paint_light_cone(painter, planes, z, delta_size, tile_size, n_pixel_tile, re
                     buf = None                                   # (let go of the smaller one first)
                     buf = torch.empty(n_f * n_plane * n_plane, dtype=torch.float64, device=dev)
                 shape = (n_plane, n_plane) if j is None else (n_f, n_plane, n_plane)
-                plane = paint_plane(painter, entry, rel, n_pixel_tile, z[i], on_device=True,
-                                    out=buf[:n_f * n_plane * n_plane].view(shape), **kw)
+                if return_problematic_tiles:     # paint_plane's device path, the plane's report left in the cone's keep
+                    if keep is None:
+                        from .painter import TileKeep
+                        keep = TileKeep(painter, n_pixel_tile, cap, regularise_std)
+                    tiled.append(i)
+                    plane = _paint_plane_device(painter, entry, rel, n_pixel_tile, z[i], min_tile_overlap, falloff,
+                                                sigma, regularise_std, batch_size, seed, kw["first_tile_id"],
+                                                buf[:n_f * n_plane * n_plane].view(shape), pixel_noise, regularise,
+                                                keep=keep, plane_number=i)
+                else:
+                    plane = paint_plane(painter, entry, rel, n_pixel_tile, z[i], on_device=True,
+                                        out=buf[:n_f * n_plane * n_plane].view(shape), **kw)
+            elif return_problematic_tiles:
+                left = max(cap - sum(len(r.tiles) for r in reports), 0)
+                plane, r = paint_plane(painter, entry, rel, n_pixel_tile, z[i], return_problematic_tiles=True,
+                                       max_problematic_tiles=left, **kw)
+                for e in r.tiles:
+                    e.plane = i
+                reports.append(r)
+                tiled.append(i)
             else:
                 plane = paint_plane(painter, entry, rel, n_pixel_tile, z[i], **kw)
             if j is not None:
@@ -744,6 +903,11 @@ def paint_light_cone(painter, planes, z, delta_size, tile_size, n_pixel_tile, re
         raise ValueError("fewer planes than redshifts")
     if on_device and out is None:
         y_map = y_map.cpu().numpy()
+    if return_problematic_tiles:
+        if keep is not None:                                     # behind the last plane: one download for the cone
+            reports = _report_device(keep)
+        report = _cone_report(regularise_std, reports, tiled)
+        return (y_map, kept, report) if return_planes else (y_map, report)
     return (y_map, kept) if return_planes else y_map
 
 

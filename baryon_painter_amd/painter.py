@@ -123,7 +123,8 @@ class Painter:
         return self._device_paint_parameters(zs, ensemble=True)
 
     def _paint_plane_device(self, delta, geo, z, weight_map, batch_size, tile_ids, seed, regularise_std=None, out=None,
-                            pixel_noise=False, draws=None, return_planes=False, moments=True):
+                            pixel_noise=False, draws=None, return_planes=False, moments=True, regularise=True,
+                            keep=None):
         """The device form of ``lightcone.paint_plane`` (on_device=True): ``geo`` is ``lightcone.plane_geometry``'s,
         ``weight_map`` the host's ``make_weight_map`` (float64, uploaded as it is), ``tile_ids`` / ``seed`` / ``batch_size``
         those the host path hands to ``paint_stream``.  Per batch, on ONE stream: the tiles are cut (and resampled) from
@@ -140,7 +141,11 @@ class Painter:
         plane of its own and the moments are taken across the K planes (``_paint_plane_ensemble_pipeline``).  Returns
         (mean, var), with ``return_planes`` (mean, var, planes), planes (K, [F,] n_plane, n_plane); ``out`` is the pair
         (mean, var) of CUDA float64 tensors.  ``moments=False``: the K finished planes alone, as a CUDA tensor that
-        lives in the cached accumulator until the next plane is painted.  Without ``draws`` nothing changes."""
+        lives in the cached accumulator until the next plane is painted.  Without ``draws`` nothing changes.
+
+        ``regularise=False`` (single draws only): the blend is not masked, whatever ``regularise_std`` says.  ``keep``: a
+        ``TileKeep.plane(...)`` record -- each batch's tiles are counted (bp_tile_outliers) and its problematic tiles
+        set aside (bp_tile_keep) between the replay and the blend; without it the plane's launches are unchanged."""
         model = self.model
         model.train(False)
         tile, W = self._tile_shape()
@@ -148,6 +153,8 @@ class Painter:
             raise NotImplementedError("device planes need square tiles")
         if tuple(weight_map.shape) != (tile, tile):
             raise ValueError(f"weight map {weight_map.shape} does not match the model's {tile}^2 tiles")
+        if draws is not None and (keep is not None or not regularise):
+            raise NotImplementedError("plane ensembles have no tile report and no detect-only mode")
         if draws is not None:
             K = PG.check_draws(draws)
             params, scales, modes = self._ensemble_parameters(np.full(len(geo["origins"]), float(z)), pixel_noise)
@@ -162,7 +169,7 @@ class Painter:
             n = len(geo["origins"])
             params = _with_noise(params, np.full(n, tile_ids[0], dtype=np.int64), geo["dst"], n, tile, tile, 0, n)
         return _paint_plane_pipeline(self, model, tile, delta, geo, int(batch_size), params, tile_ids, seed, weight_map,
-                                     regularise_std, out, scales, modes)
+                                     regularise_std if regularise else None, out, scales, modes, keep)
 
     def _paint_small_plane_device(self, plane, origin, size, crop, z, tile_id, seed, subtract_minimum=False,
                                   field_index=None, out=None, pixel_noise=False, draws=None, return_planes=False,
@@ -1059,12 +1066,59 @@ def _paint_stream_pipeline(painter, model, inputs, tile_shape, lo, hi, B, params
     return result
 
 
+class TileKeep:
+    """The device side of a ``lightcone.TileReport``, for one plane or for all tiled planes of a light cone: ``cap``
+    slots for problematic tiles -- index, raw (tile, tile) and painted (F, tile, tile) float32 -- behind ONE int32
+    cursor in device memory that ``bp_tile_keep`` advances batch after batch, plane after plane, on the painter's
+    stream, and per plane the (n_tiles * F) counts and statistics ``bp_tile_outliers`` leaves.  Nothing is read back
+    before ``download()``."""
+
+    def __init__(self, painter, tile, cap, regularise_std):
+        dev = painter.model.device
+        self.F = len(getattr(painter, "label_fields", None) or [None])
+        self.tile, self.cap, self.regularise_std = int(tile), int(cap), float(regularise_std)
+        slots = max(self.cap, 1)
+        self.cursor = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.index = torch.full((slots,), -1, dtype=torch.int32, device=dev)
+        self.raw = torch.empty((slots, self.tile, self.tile), dtype=torch.float32, device=dev)
+        self.painted = torch.empty((slots, self.F, self.tile, self.tile), dtype=torch.float32, device=dev)
+        self.planes = []
+
+    def plane(self, first_index, n_tiles, n_side, first_tile_id, z, number=None):
+        """The record of the next plane: its tiles take the slot indices ``first_index`` ... + ``n_tiles``."""
+        dev = self.cursor.device
+        rec = {"keep": self, "first_index": int(first_index), "n_tiles": int(n_tiles), "n_side": int(n_side),
+               "first_tile_id": int(first_tile_id), "z": z, "plane": number,
+               "counts": torch.empty(n_tiles * self.F, dtype=torch.int32, device=dev),
+               "stats": torch.empty(2 * n_tiles * self.F, dtype=torch.float64, device=dev)}
+        self.planes.append(rec)
+        return rec
+
+    def download(self):
+        """One synchronising download.  Per plane, in the order painted: (record, mean, std, n_outliers -- (n_tiles, F)
+        -- and of its kept tiles the tile numbers, the raw tiles and the paintings ((tile, tile) where F = 1))."""
+        kept = min(int(self.cursor.cpu()[0]), self.cap)
+        index = self.index[:kept].cpu().numpy()
+        raw, painted = self.raw[:kept].cpu().numpy(), self.painted[:kept].cpu().numpy()
+        if self.F == 1:
+            painted = painted[:, 0]
+        out = []
+        for rec in self.planes:
+            n, F = rec["n_tiles"], self.F
+            stats = rec["stats"].cpu().numpy().reshape(n, F, 2)
+            sel = np.flatnonzero((index >= rec["first_index"]) & (index < rec["first_index"] + n))
+            out.append((rec, stats[..., 0].copy(), stats[..., 1].copy(), rec["counts"].cpu().numpy().reshape(n, F),
+                        index[sel] - rec["first_index"], [raw[s] for s in sel], [painted[s] for s in sel]))
+        return out
+
+
 def _paint_plane_pipeline(painter, model, tile, delta, geo, B, params, tile_ids, seed, weight_map, regularise_std, out,
-                          scales=None, modes=None):
+                          scales=None, modes=None, keep=None):
     """One plane through ``model.paint_graph(B)`` on the device (``CVAEPainter._paint_plane_device``): cut, parameter
     block, replay, blend per batch on ONE stream, then the division.  ``modes`` of F > 1 label fields: the slots' ``out``
     is (B, F, tile, tile), blended by ``bp_plane_blend_fields`` into one accumulator plane per field; the result (and
-    ``out``) is (F, n_plane, n_plane)."""
+    ``out``) is (F, n_plane, n_plane).  ``keep``: the plane's ``TileKeep.plane`` record; between replay and blend every
+    batch then runs ``bp_tile_outliers`` on the slot's ``out`` and ``bp_tile_keep`` on the slot's ``raw`` and ``out``."""
     import ctypes as C
     from . import _lib as L
     dev = model.device
@@ -1084,6 +1138,10 @@ def _paint_plane_pipeline(painter, model, tile, delta, geo, B, params, tile_ids,
                             out.dtype != torch.float64 or tuple(out.shape) != shape or
                             not out.is_contiguous()):
         raise ValueError(f"out must be a contiguous float64 ({', '.join(str(v) for v in shape)}) tensor on {dev}")
+    tk = keep["keep"] if keep is not None else None
+    if tk is not None and (tk.F != F or tk.tile != tile or keep["n_tiles"] != n or tk.cursor.device != torch.device(dev)):
+        raise ValueError(f"the tile keep is for {keep['n_tiles']} tiles of {tk.F} x {tk.tile}^2 on {tk.cursor.device}, "
+                         f"the plane has {n} of {F} x {tile}^2 on {dev}")
     g = _paint_graph(model, B, scales, modes, "noise_ids" in params)
     # per-plane parameter blocks, one per batch, built like paint_stream's pinned ones and uploaded once: a batch
     # then costs one device-to-device copy of its block into the slot
@@ -1127,6 +1185,14 @@ def _paint_plane_pipeline(painter, model, tile, delta, geo, B, params, tile_ids,
                                      tile, L.ptr(buf["scratch"]), ws, L.ptr(gs["raw"]), sm), "plane cut")
             gs["block"].copy_(blocks_d[bi])
             gs["graph"].replay()
+            if keep is not None:
+                counts = C.c_void_p(keep["counts"].data_ptr() + 4 * a * F)
+                L.check(lib.bp_tile_outliers(L.ptr(gs["out"]), m * F, tile, tk.regularise_std,
+                                             C.c_void_p(keep["stats"].data_ptr() + 16 * a * F), counts, sm),
+                        "tile outliers")
+                L.check(lib.bp_tile_keep(L.ptr(gs["raw"]), L.ptr(gs["out"]), counts, m, F, tile,
+                                         keep["first_index"] + a, tk.cap, L.ptr(tk.cursor), L.ptr(tk.index),
+                                         L.ptr(tk.raw), L.ptr(tk.painted), sm), "tile keep")
             box = geo["dst"][a:b]
             blend = (lib.bp_plane_blend, (m,)) if F == 1 else (lib.bp_plane_blend_fields, (m, F))
             L.check(blend[0](L.ptr(gs["out"]), *blend[1], tile, C.c_void_p(dst_d.data_ptr() + 8 * a),

@@ -541,6 +541,40 @@ int bp_plane_blend_fields(const float* tiles, int32_t n, int32_t fields, int32_t
                           void* stream);
 int bp_plane_finish(const double* acc, const double* wsum, int64_t count, double* out, void* stream);
 
+/* ---- problematic tiles of a plane (lightcone.paint_plane(return_problematic_tiles=True), process_SLICS.py:212-216) --
+ * Which painted tiles hold a pixel more than regularise_std tile standard deviations from the tile mean, how many
+ * such pixels, and the offending tiles themselves, on the device between the paint graph and the blend.
+ *   bp_tile_outliers: tiles is (n_images, tile, tile) float32; for the (n, fields, tile, tile) tiles of a painter with
+ *                    several label fields an image is one (tile, field) pair, row t * fields + f.  One workgroup per
+ *                    image: stats[2i] = mean, stats[2i + 1] = population std in float64, by the reduction of
+ *                    bp_plane_blend (the same device function: the same bits), and counts[i] (int32) = the number of
+ *                    pixels with fabs((double) p - mean) > std * regularise_std, the blend's own expression:
+ *                    counts[i] > 0 exactly where bp_plane_blend(regularise = 1) zeroes a weight of image i.  A NaN
+ *                    in an image gives a NaN mean and count 0 (every comparison is false, as NumPy's), an infinite
+ *                    pixel likewise, a constant image std 0 and count 0.  BP_EINVAL for a null pointer, n_images or
+ *                    tile < 1, a regularise_std that is negative or not finite; then BP_EUNSUPPORTED for
+ *                    n_images * tile^2 >= 2^31
+ *   bp_tile_keep   : tile t of the batch (raw (n, tile, tile) as bp_plane_cut wrote it, painted (n, fields, tile,
+ *                    tile), counts (n, fields) from bp_tile_outliers) is problematic if any of its `fields` counts is
+ *                    non-zero.  The j-th problematic tile in ascending t takes slot s = *cursor + j; while s < cap:
+ *                    kept_index[s] = first_index + t, kept_raw[s] (tile, tile) and kept_painted[s] (fields, tile,
+ *                    tile) receive its tiles bit for bit.  Then *cursor += the number of problematic tiles of the
+ *                    batch, those beyond cap included.  cursor is one int32 in device memory that the caller zeroes
+ *                    once and carries from batch to batch on ONE stream: two ordered launches, the copy, which reads
+ *                    it, then the advance.  Slots that are not written stay untouched; cap = 0 only counts.  16-byte
+ *                    copies where tile^2 is a multiple of four and raw, painted, kept_raw, kept_painted are 16-byte
+ *                    aligned, 4-byte ones otherwise; the bits do not depend on it.  BP_EINVAL for a null raw,
+ *                    painted, counts or cursor, null kept_* with cap > 0, n, fields or tile < 1, first_index or
+ *                    cap < 0; then BP_EUNSUPPORTED for n * fields * tile^2 >= 2^31, n > 65535 or
+ *                    first_index + n >= 2^31
+ * Nothing is launched or written on a refusal.  No atomics, no workspace, no host synchronisation: the same inputs
+ * give the same bits. */
+int bp_tile_outliers(const float* tiles, int32_t n_images, int32_t tile, double regularise_std, double* stats,
+                     int32_t* counts, void* stream);
+int bp_tile_keep(const float* raw, const float* painted, const int32_t* counts, int32_t n, int32_t fields, int32_t tile,
+                 int32_t first_index, int32_t cap, int32_t* cursor, int32_t* kept_index, float* kept_raw,
+                 float* kept_painted, void* stream);
+
 /* ---- ensembles of planes and y maps (lightcone.paint_plane_ensemble / paint_light_cone_ensemble) -----------------
  * K draws of a plane are blended into K accumulator pairs (bp_plane_blend_fields with fields = K * F over the
  * (n, K, F, tile, tile) draws of an ensemble graph), K draws of a light cone are projected into K maps; the moments
