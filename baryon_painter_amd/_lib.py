@@ -124,6 +124,7 @@ SIGNATURES = {
     "bp_sums_to_float": (C.c_int, [_P, C.c_int32, _P, _P]),
     "bp_prelu_slope_grad": (C.c_int, [_P, C.c_int32, _P, _P]),
     "bp_residual_forward": (C.c_int, [_VP, _PWP, _VP, _PWP, C.c_float, _VP, _P]),
+    "bp_view_cast": (C.c_int, [_VP, _PWP, _VP, _P]),
     "bp_nchw_to_view": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _VP, _P]),
     "bp_view_to_nchw": (C.c_int, [_VP, _PWP, C.c_int32, _P, _P]),
     "bp_fill": (C.c_int, [_P, C.c_int64, C.c_float, _P]),

@@ -38,7 +38,8 @@ int bp_set_option(const char* name, int value) {
   if (!strcmp(name, "bf16_ws")) { bp_bf16_ws_set(value); return BP_OK; }
   if (!strcmp(name, "f32_ws")) { bp_f32_ws_set(value); return BP_OK; }
   if (!strcmp(name, "f32_wgrad_ws")) { bp_f32_wgrad_ws_set(value); return BP_OK; }
-  if (!strcmp(name, "bf16_wgrad_ws")) { bp_bf16_wgrad_ws_set(value); return BP_OK; }
+  // (also under the name of the environment variable that sets its default)
+  if (!strcmp(name, "bf16_wgrad_ws") || !strcmp(name, "BP_BF16_WGRAD_WS")) { bp_bf16_wgrad_ws_set(value); return BP_OK; }
   return BP_EUNSUPPORTED;
 }
 

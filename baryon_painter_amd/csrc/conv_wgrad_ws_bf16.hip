@@ -32,6 +32,7 @@ struct WoArgs {
   PW pwx;
   float* ws;                         // [split][tap 9][co 128][ci 128]
   int BR, bands, nsplit;
+  int w, strips;                     // STRIPS: image width in pixels, 64-pixel column strips per image
 };
 
 template <int G> struct WoGeom {
@@ -51,8 +52,13 @@ __device__ __forceinline__ bf8 wo_frag(s4 a, s4 b) {
   return __builtin_bit_cast(bf8, v);
 }
 
-template <int G, bool ACT>
+// STRIPS: the image is cut into column strips of W = 64 pixels and a work item is image-band x strip.  An X ring row's two
+// halo columns then hold the neighbouring strips' pixels (zero at the image edge), loaded, activated and written WITH the
+// row by sixteen lanes (tile 4 x half 2 x side 2), so no separate fill can race a commit; dY rows have no halo.  The LDS
+// images are those of the 64-pixel kernel: the halo pixel has always been part of the row (RPX = W + 2).
+template <int G, bool ACT, bool STRIPS = false>
 __global__ __launch_bounds__(256) void wgrad_ws_bf16_kernel(WoArgs a) {
+  static_assert(!STRIPS || G == 4, "column strips are 64 pixels wide");
   using GM = WoGeom<G>;
   constexpr int W = GM::W, RPX = GM::RPX, XT = GM::XT, YT = GM::YT;
   constexpr int KS = W / 32;                            // k-steps per row
@@ -70,7 +76,9 @@ __global__ __launch_bounds__(256) void wgrad_ws_bf16_kernel(WoArgs a) {
   const int split = (int)(blockIdx.x & 7) + 8 * (int)(blockIdx.x >> 5), pair = (blockIdx.x >> 3) & 3;
   if (split >= a.nsplit) return;                        // (uniform per block; the grid is padded to a multiple of 32)
   const int cib = pair & 1, cob = pair >> 1;
-  const int n = split / a.bands, band = split % a.bands;
+  const int item = STRIPS ? split / a.strips : split, strip = STRIPS ? split % a.strips : 0;
+  const int n = item / a.bands, band = item % a.bands;
+  const int IW = STRIPS ? a.w : W;                      // pixels per image row
   const int y0 = band * a.BR;
   const int y1 = min(y0 + a.BR, a.h);
 
@@ -79,18 +87,31 @@ __global__ __launch_bounds__(256) void wgrad_ws_bf16_kernel(WoArgs a) {
   const int s_half = lane & 1, s_tile = (lane >> 3) & 3;
   const int s_px = ((lane >> 1) & 3) + 4 * (lane >> 5) + 8 * wave;              // + 32 i
   const int s_oct = 2 * s_tile + s_half;
-  const char* x_img = reinterpret_cast<const char*>(a.X + (int64_t)n * a.h * W * a.x_cs + a.x_co + WB_B * cib);
-  const char* y_img = reinterpret_cast<const char*>(a.Y + (int64_t)n * a.h * W * a.y_cs + a.y_co + WB_B * cob);
-  const unsigned x_row = (unsigned)(W * a.x_cs) * 2u, y_row = (unsigned)(W * a.y_cs) * 2u;
+  const char* x_img = reinterpret_cast<const char*>(a.X + ((int64_t)n * a.h * IW + W * strip) * a.x_cs + a.x_co + WB_B * cib);
+  const char* y_img = reinterpret_cast<const char*>(a.Y + ((int64_t)n * a.h * IW + W * strip) * a.y_cs + a.y_co + WB_B * cob);
+  const unsigned x_row = (unsigned)(IW * a.x_cs) * 2u, y_row = (unsigned)(IW * a.y_cs) * 2u;
   const unsigned x_off = (unsigned)(s_px * a.x_cs + 8 * s_oct) * 2u, x_st = (unsigned)(32 * a.x_cs) * 2u;
   const unsigned y_off = (unsigned)(s_px * a.y_cs + 8 * s_oct) * 2u, y_st = (unsigned)(32 * a.y_cs) * 2u;
   // (a row's units as NAMED members: arrays carried from one k-step's code to the next ended up in scratch memory)
   struct Raw { uint4 u0, u1; };
+  struct RawH { uint4 u0, u1, uh; };                    // + the halo unit of lanes 0 .. 15
+  using RawX = std::conditional_t<STRIPS, RawH, Raw>;
+  // halo unit of lane tid < 16: side = tid >> 3 (left, right), 16-byte unit tid & 7 of the pixel's 64 channels.  Where the
+  // strip has no neighbour on that side the lane loads the strip's own first pixel and keeps nothing of it.
+  const bool h_lane = STRIPS && tid < 16;
+  const int h_side = (tid >> 3) & 1, h_oct = tid & 7;
+  const bool h_has = h_side ? strip + 1 < a.strips : strip > 0;
+  const unsigned h_keep = h_has ? 0xffffffffu : 0u;
+  const int h_off = ((h_has ? (h_side ? W : -1) * a.x_cs : 0) + 8 * h_oct) * 2;
   auto load_x = [&](int r) {
     const char* rowp = x_img + (size_t)((unsigned)r * x_row);
-    Raw raw;
+    RawX raw;
     raw.u0 = *reinterpret_cast<const uint4*>(rowp + x_off);
     raw.u1 = NU > 1 ? *reinterpret_cast<const uint4*>(rowp + (x_off + x_st)) : make_uint4(0u, 0u, 0u, 0u);
+    if constexpr (STRIPS) {
+      raw.uh = make_uint4(0u, 0u, 0u, 0u);
+      if (h_lane) raw.uh = *reinterpret_cast<const uint4*>(rowp + (ptrdiff_t)h_off);
+    }
     return raw;
   };
   auto load_y = [&](int r) {
@@ -100,7 +121,7 @@ __global__ __launch_bounds__(256) void wgrad_ws_bf16_kernel(WoArgs a) {
     raw.u1 = NU > 1 ? *reinterpret_cast<const uint4*>(rowp + (y_off + y_st)) : make_uint4(0u, 0u, 0u, 0u);
     return raw;
   };
-  auto act8 = [&](uint4 v) {
+  auto act8 = [&](uint4 v, int s_oct) {
     if constexpr (ACT) {
       const unsigned wd[4] = {v.x, v.y, v.z, v.w};
       unsigned o[4];
@@ -119,14 +140,22 @@ __global__ __launch_bounds__(256) void wgrad_ws_bf16_kernel(WoArgs a) {
     }
     return v;
   };
-  auto put_x = [&](int r, unsigned keep, const Raw raw) {              // X row r -> ring slot (r + 1) & 7, columns 1 .. W
+  auto put_x = [&](int r, unsigned keep, const RawX raw) {             // X row r -> ring slot (r + 1) & 7, columns 1 .. W
     const int rr = (r + 1) & (WB_RX - 1);
     u16* base = xs + s_tile * XT + ((rr * RPX + 1 + s_px) * 16 + 8 * s_half);
-    const uint4 v = act8(raw.u0);
+    const uint4 v = act8(raw.u0, s_oct);
     *reinterpret_cast<uint4*>(base) = make_uint4(v.x & keep, v.y & keep, v.z & keep, v.w & keep);
     if constexpr (NU > 1) {
-      const uint4 w = act8(raw.u1);
+      const uint4 w = act8(raw.u1, s_oct);
       *reinterpret_cast<uint4*>(base + 32 * 16) = make_uint4(w.x & keep, w.y & keep, w.z & keep, w.w & keep);
+    }
+    if constexpr (STRIPS) {                                             // ... and column 0 or W + 1
+      if (h_lane) {
+        const uint4 e = act8(raw.uh, h_oct);
+        const unsigned k2 = keep & h_keep;
+        *reinterpret_cast<uint4*>(xs + (h_oct >> 1) * XT + ((rr * RPX + (h_side ? RPX - 1 : 0)) * 16 + 8 * (h_oct & 1))) =
+            make_uint4(e.x & k2, e.y & k2, e.z & k2, e.w & k2);
+      }
     }
   };
   auto put_y = [&](int r, const Raw raw) {                             // dY row r -> ring slot r & 3
@@ -137,8 +166,8 @@ __global__ __launch_bounds__(256) void wgrad_ws_bf16_kernel(WoArgs a) {
   };
 
   // ---- prologue: X rows y0 - 1 .. y0 + 2, dY rows y0, y0 + 1
-  Raw rx, ry;
-  if (tid < 128) {                                      // zero columns 0 and W + 1: [tile 4][ring 8][side 2] x two 16-byte halves
+  RawX rx, ry;
+  if (!STRIPS && tid < 128) {                           // zero columns 0 and W + 1: [tile 4][ring 8][side 2] x two 16-byte halves
     const int t = tid >> 5, rr = (tid >> 2) & 7, side = (tid >> 1) & 1, hf = tid & 1;
     *reinterpret_cast<uint4*>(xs + t * XT + ((rr * RPX + (side ? RPX - 1 : 0)) * 16 + 8 * hf)) = make_uint4(0u, 0u, 0u, 0u);
   }
@@ -158,10 +187,16 @@ __global__ __launch_bounds__(256) void wgrad_ws_bf16_kernel(WoArgs a) {
     ry = load_x(i3 ? y0 + 2 : y0);
     put_x(y0 + 1, i2 ? 0xffffffffu : 0u, rx);
     put_x(y0 + 2, i3 ? 0xffffffffu : 0u, ry);
-    rx = load_y(y0);
-    ry = load_y(i2 ? y0 + 1 : y0);
-    put_y(y0, rx);
-    put_y(y0 + 1, ry);
+    if constexpr (STRIPS) {
+      const Raw qx = load_y(y0), qy = load_y(i2 ? y0 + 1 : y0);
+      put_y(y0, qx);
+      put_y(y0 + 1, qy);
+    } else {
+      rx = load_y(y0);
+      ry = load_y(i2 ? y0 + 1 : y0);
+      put_y(y0, rx);
+      put_y(y0 + 1, ry);
+    }
   }
   __syncthreads();
 
@@ -192,7 +227,8 @@ __global__ __launch_bounds__(256) void wgrad_ws_bf16_kernel(WoArgs a) {
   // busy and the matrix pipe 35 %.  Fragment pipeline at TAP granularity: a tap's X fragment is re-requested for the NEXT
   // k-step right behind the MFMA that consumed it (eight MFMAs of cover); the next k-step is the same row's, or k-step 0 of
   // row y + 1 (resident since the barrier that ended row y - 1).
-  Raw sx[3], sy[3];
+  RawX sx[3];
+  Raw sy[3];
   auto ld_x = [&](int r) { return load_x(r < a.h ? r : a.h - 1); };
   auto ld_y = [&](int r) { return load_y(r < a.h ? r : a.h - 1); };
   sx[0] = ld_x(y0 + 3); sy[0] = ld_y(y0 + 2);
@@ -269,20 +305,22 @@ bool wo_enabled() {
 int g_wo_override = -1;
 
 int wo_G(int w) { return w == 64 ? 4 : w == 32 ? 2 : 0; }
+// column strips of 64 pixels: the widths the forward strip kernel takes (conv_bf16_ws.hip), 128 .. 256
+int wo_strips(int w) { return w > 64 && w <= 256 && w % 64 == 0 ? w / 64 : 0; }
 
-void wo_bands(int n, int h, int* BR, int* bands) {      // ~256 workgroups = 64 splits x 4 channel-block pairs
+void wo_bands(int n, int h, int strips, int* BR, int* bands) {      // ~256 workgroups = 64 splits x 4 channel-block pairs
   int br = h;
-  while (br > 8 && (int64_t)n * bp_ceil_div(h, br) < 64) br = bp_ceil_div(br, 2);
+  while (br > 8 && (int64_t)n * strips * bp_ceil_div(h, br) < 64) br = bp_ceil_div(br, 2);
   *BR = br;
   *bands = bp_ceil_div(h, br);
 }
 
-template <int G, bool ACT>
+template <int G, bool ACT, bool STRIPS = false>
 int wo_launch(const WoArgs& a, unsigned grid, hipStream_t st) {
-  static const hipError_t optin = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_ws_bf16_kernel<G, ACT>),
+  static const hipError_t optin = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_ws_bf16_kernel<G, ACT, STRIPS>),
                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)WoGeom<G>::lds_bytes);
   if (optin != hipSuccess) return BP_ELAUNCH;
-  hipLaunchKernelGGL((wgrad_ws_bf16_kernel<G, ACT>), dim3(grid), dim3(256), WoGeom<G>::lds_bytes, st, a);
+  hipLaunchKernelGGL((wgrad_ws_bf16_kernel<G, ACT, STRIPS>), dim3(grid), dim3(256), WoGeom<G>::lds_bytes, st, a);
   BP_CHECK_LAUNCH();
   return BP_OK;
 }
@@ -297,14 +335,15 @@ int bp_wgrad_ws_bf16(const bp_conv* cv, const bp_view* X, const PW& pwx, const b
   if (!(g_wo_override < 0 ? wo_enabled() : g_wo_override != 0)) return BP_EUNSUPPORTED;
   if (cv->transposed || cv->k != 3 || cv->stride != 1 || cv->pad != 1 || cv->cin != WB_C || cv->cout != WB_C) return BP_EUNSUPPORTED;
   if (X->dtype != BP_BF16 || Y->dtype != BP_BF16 || X->c != WB_C || Y->c != WB_C || pwy.scale) return BP_EUNSUPPORTED;
-  if (X->n != Y->n || X->h != Y->h || X->w != Y->w || !wo_G(X->w)) return BP_EUNSUPPORTED;
+  const int strips = wo_strips(X->w);
+  if (X->n != Y->n || X->h != Y->h || X->w != Y->w || (!wo_G(X->w) && !strips)) return BP_EUNSUPPORTED;
   if (X->cstride % 8 || X->coff % 8 || reinterpret_cast<uintptr_t>(X->ptr) % 16) return BP_EUNSUPPORTED;
   if (Y->cstride % 8 || Y->coff % 8 || reinterpret_cast<uintptr_t>(Y->ptr) % 16) return BP_EUNSUPPORTED;
   if ((int64_t)X->h * X->w * X->cstride * 2 >= (int64_t)1 << 31 || (int64_t)Y->h * Y->w * Y->cstride * 2 >= (int64_t)1 << 31)
     return BP_EUNSUPPORTED;
   WoArgs a{};
-  wo_bands(X->n, X->h, &a.BR, &a.bands);
-  const int64_t splits = (int64_t)X->n * a.bands;
+  wo_bands(X->n, X->h, strips ? strips : 1, &a.BR, &a.bands);
+  const int64_t splits = (int64_t)X->n * a.bands * (strips ? strips : 1);
   if (splits * 4 + 32 > 0x7fffffff) return BP_EUNSUPPORTED;
   *nsplit = (int)splits; *cxp = WB_C; *cyp = WB_C;
   *need = (size_t)splits * 9 * WB_C * WB_C * sizeof(float);
@@ -313,8 +352,10 @@ int bp_wgrad_ws_bf16(const bp_conv* cv, const bp_view* X, const PW& pwx, const b
   a.X = reinterpret_cast<const u16*>(X->ptr); a.x_cs = X->cstride; a.x_co = X->coff;
   a.Y = reinterpret_cast<const u16*>(Y->ptr); a.y_cs = Y->cstride; a.y_co = Y->coff;
   a.n = X->n; a.h = X->h; a.pwx = pwx; a.ws = ws; a.nsplit = (int)splits;
+  a.w = X->w; a.strips = strips ? strips : 1;
   const bool act = pwx.scale != nullptr;
   const unsigned grid = (unsigned)(bp_ceil_div((int)splits, 8) * 32);          // (split_lo 8) x (pair 4) x split_hi
+  if (strips) return act ? wo_launch<4, true, true>(a, grid, st) : wo_launch<4, false, true>(a, grid, st);
   if (wo_G(X->w) == 4) return act ? wo_launch<4, true>(a, grid, st) : wo_launch<4, false>(a, grid, st);
   return act ? wo_launch<2, true>(a, grid, st) : wo_launch<2, false>(a, grid, st);
 }

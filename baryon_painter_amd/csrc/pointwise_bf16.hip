@@ -263,7 +263,115 @@ static inline unsigned stream_blocks(int64_t total8) {
   return (unsigned)nb;
 }
 
+// ---- fp32 <-> bf16 over NHWC views (bp_view_cast): the two ends of a bf16 trunk between fp32 layers
+struct CastArgs {
+  const void* src; void* dst;
+  int c, s_cs, s_co, d_cs, d_co;
+  int64_t npix;
+  PW pw;
+};
+
+// 8 channels of one pixel per thread and trip: one 16-byte access on the bf16 side, two on the fp32 side.  FIXED: the
+// grid's stride is a multiple of the c / 8 units of a pixel, so a thread keeps its channels and loads their pointwise once.
+template <bool TO_BF16, bool FIXED>
+__global__ __launch_bounds__(RB) void view_cast8_kernel(CastArgs a) {
+  const int G = a.c / 8;
+  const int64_t total = a.npix * G, stride = (int64_t)gridDim.x * RB;
+  const bool on = a.pw.scale != nullptr;
+  auto load_pw = [&](int ch0) {
+    Pw8 r;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      r.sc[j] = on ? a.pw.scale[ch0 + j] : 1.f;
+      r.sf[j] = on ? a.pw.shift[ch0 + j] : 0.f;
+      r.sl[j] = on ? a.pw.slope[ch0 + j] : 1.f;
+    }
+    return r;
+  };
+  int64_t u = (int64_t)blockIdx.x * RB + threadIdx.x;
+  Pw8 p = load_pw(FIXED ? 8 * (int)(u % G) : 0);
+  for (; u < total; u += stride) {
+    const int64_t px = u / G;
+    const int ch0 = 8 * (int)(u - px * G);
+    if constexpr (!FIXED) {
+      if (on) p = load_pw(ch0);
+    }
+    float v[8];
+    if constexpr (TO_BF16) {
+      const float* s = reinterpret_cast<const float*>(a.src) + px * a.s_cs + a.s_co + ch0;
+      const float4 lo = *reinterpret_cast<const float4*>(s), hi = *reinterpret_cast<const float4*>(s + 4);
+      v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w; v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
+    } else {
+      unpack8(*reinterpret_cast<const uint4*>(reinterpret_cast<const u16*>(a.src) + px * a.s_cs + a.s_co + ch0), v);
+    }
+    if (on) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float t = fmaf(v[j], p.sc[j], p.sf[j]);
+        v[j] = t > 0.f ? t : t * p.sl[j];
+      }
+    }
+    if constexpr (TO_BF16) {
+      *reinterpret_cast<uint4*>(reinterpret_cast<u16*>(a.dst) + px * a.d_cs + a.d_co + ch0) = pack8(v);
+    } else {
+      float* d = reinterpret_cast<float*>(a.dst) + px * a.d_cs + a.d_co + ch0;
+      *reinterpret_cast<float4*>(d) = make_float4(v[0], v[1], v[2], v[3]);
+      *reinterpret_cast<float4*>(d + 4) = make_float4(v[4], v[5], v[6], v[7]);
+    }
+  }
+}
+
+// ragged views (a channel count, stride or offset that is no multiple of 8, an unaligned base): one element per thread and trip
+template <bool TO_BF16>
+__global__ __launch_bounds__(RB) void view_cast1_kernel(CastArgs a) {
+  const int64_t total = a.npix * a.c, stride = (int64_t)gridDim.x * RB;
+  for (int64_t e = (int64_t)blockIdx.x * RB + threadIdx.x; e < total; e += stride) {
+    const int64_t px = e / a.c;
+    const int ch = (int)(e - px * a.c);
+    float v;
+    if constexpr (TO_BF16) v = reinterpret_cast<const float*>(a.src)[px * a.s_cs + a.s_co + ch];
+    else v = bf2f(reinterpret_cast<const u16*>(a.src)[px * a.s_cs + a.s_co + ch]);
+    v = pw_apply(a.pw, ch, v);
+    if constexpr (TO_BF16) reinterpret_cast<u16*>(a.dst)[px * a.d_cs + a.d_co + ch] = f2bf(v);
+    else reinterpret_cast<float*>(a.dst)[px * a.d_cs + a.d_co + ch] = v;
+  }
+}
+
+static inline bool cast_vec8(const bp_view* v) {
+  return v->c % 8 == 0 && v->cstride % 8 == 0 && v->coff % 8 == 0 && reinterpret_cast<uintptr_t>(v->ptr) % 16 == 0;
+}
+
 }  // namespace
+
+extern "C" int bp_view_cast(const bp_view* src, const bp_pointwise* pw, const bp_view* dst, void* stream) {
+  if (!bp_view_ok_any(src) || !bp_view_ok_any(dst) || src->dtype == dst->dtype) return BP_EINVAL;
+  if (src->n != dst->n || src->h != dst->h || src->w != dst->w || src->c != dst->c) return BP_EINVAL;
+  CastArgs a{};
+  a.src = src->ptr; a.dst = dst->ptr; a.c = src->c;
+  a.s_cs = src->cstride; a.s_co = src->coff; a.d_cs = dst->cstride; a.d_co = dst->coff;
+  a.npix = bp_view_pixels(src); a.pw = bp_pw(pw);
+  const bool to_bf16 = dst->dtype == BP_BF16;
+  hipStream_t st = bp_stream(stream);
+  const dim3 block(RB);
+  if (cast_vec8(src) && cast_vec8(dst)) {
+    const int G = a.c / 8;
+    const dim3 grid(stream_blocks(a.npix * G));
+    const bool fixed = ((int64_t)grid.x * RB) % G == 0;
+    if (to_bf16) {
+      if (fixed) hipLaunchKernelGGL((view_cast8_kernel<true, true>), grid, block, 0, st, a);
+      else hipLaunchKernelGGL((view_cast8_kernel<true, false>), grid, block, 0, st, a);
+    } else {
+      if (fixed) hipLaunchKernelGGL((view_cast8_kernel<false, true>), grid, block, 0, st, a);
+      else hipLaunchKernelGGL((view_cast8_kernel<false, false>), grid, block, 0, st, a);
+    }
+  } else {
+    const dim3 grid(stream_blocks(a.npix * a.c));
+    if (to_bf16) hipLaunchKernelGGL((view_cast1_kernel<true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((view_cast1_kernel<false>), grid, block, 0, st, a);
+  }
+  BP_CHECK_LAUNCH();
+  return BP_OK;
+}
 
 bool bp_bf16_dense_ok(const bp_view* v) {
   return v && v->dtype == BP_BF16 && v->cstride == v->c && v->coff == 0 && v->c >= 8 && v->c <= 1024 &&

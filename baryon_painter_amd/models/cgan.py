@@ -26,9 +26,46 @@ from . import paint_graph as PG
 
 
 class _GanPlan(PlanBase):
+    """The training plan: generator, discriminator (both halves, and the fake half alone) and their backward passes.
+
+    ``train_dtype="bf16"``: the residual blocks of the generator, and only they, run on the bf16 matrix-core kernels with
+    bf16 slots -- both convolutions of every block (forward, data gradient, weight gradient), the block tails forward and
+    backward, the batch-norm and activation backward passes between them.  The k9 stem, both stride-2 encoders, both
+    transposed decoders, the k9 head, the whole discriminator, the losses, spectral norm and the optimizer (fp32 master
+    weights) read and write fp32.  The biased 64 <-> 128 boundary layers stay fp32 on purpose (unlike the paint plan): the
+    bf16 training epilogues take no bias and there is no bf16 weight gradient for their shapes.  Two ``CastUnit`` s stand at
+    the ends of the trunk.  A tensor is rounded to bf16 (to nearest even) at exactly these points:
+
+      forward
+        * entry: A0 = leaky(batchnorm(raw)) of the last encoder, from its fp32 raw output and batch statistics, rounded
+          once and stored -- the operand of the first block's first convolution AND that block's skip;
+        * the weights of the residual convolutions (the packed images; the master weights and dW stay fp32);
+        * the stored raw output of every residual convolution (fp32 accumulation, one rounding; its batch statistics are
+          those of the values as stored);
+        * the staged activated input of every residual convolution, leaky(batchnorm(stored raw)), in the forward and again,
+          from the same values, in the weight gradient (a block's first convolution reads a stored block output: no-op);
+        * every block's output, leaky(batchnorm(raw) + skip);
+        * exit: the last block's stored output is converted exactly to fp32 for the decoder.
+      backward (every gradient tensor of a bf16 slot is bf16)
+        * exit: the decoder's fp32 data gradient, rounded once;
+        * g_t of a block tail, (d1 + d2) * leaky'(out), the sum of the block output's consumers formed in fp32;
+        * d(loss)/d(raw) of both convolutions of a block (the batch-norm backward map, evaluated in fp32);
+        * the data gradient of both convolutions (fp32 accumulation, one rounding);
+        * entry: d1 + d2 of A0's two consumers (first convolution, skip), summed in fp32, rounded once, then converted
+          exactly to fp32; the encoder's fp32 activation and batch-norm backward follows unchanged.
+
+    The weight gradients accumulate in fp32 and are reduced in a fixed order: two iterations from one state are bit-equal."""
+
+    TRAIN_DTYPES = ("fp32", "bf16")
+
     def __init__(self, model, n):
         self.model, self.lib, self.device, self.impl, self.sync = model, model._lib, model.device, L.IMPL_AUTO, model.sync
         self.n, self.ws = n, None
+        self.train_dtype = getattr(model, "train_dtype", "fp32")
+        if self.train_dtype not in self.TRAIN_DTYPES:
+            raise ValueError(f"train_dtype {self.train_dtype!r}: one of {self.TRAIN_DTYPES}")
+        self._bf16_convs, self._bf16_first, self._f32_first = \
+            self.bf16_policy(model.g_arch) if self.train_dtype == "bf16" else ((), None, None)
         H, W = model.tile_size, model.tile_size
         dev = self.device
         self.y2 = Slot.new(n, H, W, 2, dev)
@@ -39,6 +76,9 @@ class _GanPlan(PlanBase):
         if gs.shape() != (n, H, W, 1) or gs.pw is not None:
             raise ValueError(f"generator output {gs.shape()}")
         self.g_units, self.g_raw = gu, gs
+        for u in self.flat_units(gu):
+            if self.bf16_unit(u.name) != bool(u.bf16):      # (a missing kernel is an error, never a quiet fp32 layer)
+                raise NotImplementedError(f"{u.name}: the bf16 training kernels do not take this layer")
         # discriminator input: [dm, z-1, pressure] for the real (first n) and the fake (last n) half
         self.d_in = Slot.new(2 * n, H, W, 3, dev, cstride=4)
         # (the discriminator step needs no d(loss)/d(input): its first layer computes no data gradient)
@@ -84,6 +124,30 @@ class _GanPlan(PlanBase):
         self.v_dfake = L.View(self.d_in_fake.grad_buf.data_ptr(), n, h_, w_, 1, di.cstride, 2)
         self.cnt_d = float(n * ds.h * ds.w)           # discriminator outputs per half
         self.cnt_px = float(n * H * W)
+
+    # ---- bf16 policy of ``train_dtype="bf16"`` (see the class docstring)
+    @staticmethod
+    def bf16_policy(g_arch, prefix="generator."):
+        """(name prefixes of the convolutions that run and store bf16: the bodies of the residual blocks; name of the first
+        block: it reads bf16; name of the convolution behind the last block: it reads fp32).  Needs no device."""
+        names = [layer[0].lower() for layer in g_arch]
+        res = [i for i, nm in enumerate(names) if nm == "residual block"]
+        if not res:
+            return (), None, None
+        convs = [i for i, nm in enumerate(names) if nm in ("conv", "transp conv")]
+        if res != list(range(res[0], res[-1] + 1)) or not any(i < res[0] for i in convs) \
+                or not any(i > res[-1] for i in convs):
+            raise NotImplementedError("train_dtype='bf16': the residual blocks must stand together between two convolutions")
+        return (tuple(f"{prefix}{i}.res_block." for i in res), f"{prefix}{res[0]}",
+                f"{prefix}{min(i for i in convs if i > res[-1])}")
+
+    def bf16_unit(self, name):
+        return name.startswith(self._bf16_convs) if self._bf16_convs else False
+
+    bf16_out = bf16_unit
+
+    def in_dtype(self, name):
+        return L.BF16 if name == self._bf16_first else L.F32 if name == self._f32_first else None
 
     # ---- forward pieces
     def generate(self, y, zc, training):
@@ -237,15 +301,23 @@ class CGAN(torch.nn.Module):
     """Generator + discriminator with their alternating training step."""
 
     def __init__(self, tile_size=512, device="cuda:0", n_res=9, lambda_perceptual=2.5, g_arch=None, d_arch=None,
-                 sync=None, paint_dtype="fp32"):
+                 sync=None, paint_dtype="fp32", train_dtype="fp32"):
         """``paint_dtype``: "fp32" or "bf16" -- the storage and matrix-core type of the 128-channel trunk in the
         INFERENCE plan (eval-mode ``generate``, ``paint_graph``; see ``_GanPaintPlan``).  Training ignores it.
+
+        ``train_dtype``: "fp32" or "bf16" -- the same for the residual blocks of the TRAINING plan (``_GanPlan``: what runs
+        in bf16 and where a tensor is rounded).  Independent of ``paint_dtype``; not available together with ``sync``.
 
         ``sync`` (baryon_painter_amd.dist.Sync): data parallel, one process per GPU -- the generator's batch-norm
         statistics become those of the global batch, the discriminator's and the generator's gradients are averaged
         over ranks as ONE flat buffer each, right after their backward pass (the spectral-norm power iteration is
         parameter-side arithmetic and identical on every rank)."""
         super().__init__()
+        if train_dtype not in _GanPlan.TRAIN_DTYPES:
+            raise ValueError(f"train_dtype {train_dtype!r}: one of {_GanPlan.TRAIN_DTYPES}")
+        if train_dtype == "bf16" and sync is not None:
+            raise NotImplementedError("train_dtype='bf16' is single-device: data-parallel bf16 CGAN training is not built")
+        self.train_dtype = train_dtype
         self.sync = sync
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -307,9 +379,10 @@ class CGAN(torch.nn.Module):
                 torch.nn.init.zeros_(m.bias)
 
     def _plan(self, n):
-        if n not in self._plans:
-            self._plans[n] = _GanPlan(self, n)
-        return self._plans[n]
+        key = n if self.train_dtype == "fp32" else (n, self.train_dtype)
+        if key not in self._plans:
+            self._plans[key] = _GanPlan(self, n)
+        return self._plans[key]
 
     def g_parameters(self):
         return list(self.generator.parameters())

@@ -327,6 +327,11 @@ class PlanBase:
     def bf16_out(self, name):
         return False
 
+    def in_dtype(self, name):
+        """L.F32 / L.BF16: the element type the top-level convolution or residual block of that name must read -- a
+        ``CastUnit`` goes in front of it where its input has the other one; None: whatever its input has."""
+        return None
+
     @staticmethod
     def flat_units(units):
         """``units`` with every residual block replaced by the units of its body."""
@@ -1099,6 +1104,74 @@ class UnaryUnit:
         yield
 
 
+class CastUnit:
+    """fp32 <-> bf16 between two layers (bp_view_cast): the two ends of a bf16 trunk whose neighbours stay fp32
+    (``PlanBase.in_dtype``).  Like a ``UnaryUnit`` it materialises: it reads ``inp`` through ``inp.pw`` and writes ``out``
+    with nothing pending.
+      fp32 -> bf16   out = round(act(inp)), once, to nearest even.  Backward: the bf16 gradients of ``out``'s (at most two)
+                     consumers are added in fp32 and rounded once (bp_act_backward with no pointwise, in place), then
+                     converted exactly to the fp32 d/d(activated inp); the producer's own backward follows unchanged.
+      bf16 -> fp32   exact.  Backward: the fp32 gradient is rounded once to the bf16 d/d(activated inp)."""
+
+    bf16 = False
+    _sub = None
+    ws_name = "ws"
+
+    def __init__(self, plan, name, inp, to_bf16, need_dgrad=True):
+        self.plan, self.name = plan, name
+        self.inp, self.need_dgrad = inp, need_dgrad
+        if (inp.dt == L.BF16) == bool(to_bf16):
+            raise ValueError(f"{name}: the input already has the requested element type")
+        self.out = Slot.new(inp.n, inp.h, inp.w, inp.c, plan.device, pw=None, bf16=bool(to_bf16))
+        self.out.producer = self
+        self.sums = torch.zeros(3 * inp.c, device=plan.device, dtype=torch.float64)
+        self.dx = None
+
+    def _ws(self):
+        return getattr(self.plan, self.ws_name)
+
+    def macs(self, kind="forward"):
+        return 0
+
+    def algorithmic_bytes(self, kind, nstreams=1):
+        """One fp32 and one bf16 tensor; the entry's backward reads a second bf16 gradient."""
+        px = self.out.n * self.out.h * self.out.w * self.out.c
+        return px * (6 + (2 if kind != "forward" and self.out.grad2 is not None else 0))
+
+    def maybe_pack(self):
+        pass
+
+    def maybe_bn_eval(self):
+        pass
+
+    def forward(self, training):
+        plan = self.plan
+        t0 = plan.prof_begin()
+        L.check(plan.lib.bp_view_cast(C.byref(self.inp.view), self.inp.pw_struct(), C.byref(self.out.view), _stream()),
+                f"{self.name} cast")
+        plan.prof_end(t0, self, "forward")
+
+    def prepare_backward(self):
+        if not self.need_dgrad:
+            return
+        self.out.ensure_grad()
+        self.dx = self.inp.claim_grad()
+        if self.out.dt == L.BF16:
+            self.plan.need_ws(self.plan.lib.bp_act_backward_workspace(C.byref(self.out.view)))
+
+    def backward(self, grads):
+        if self.dx is None:
+            return
+        plan, lib, out, st = self.plan, self.plan.lib, self.out, _stream()
+        t0 = plan.prof_begin()
+        if out.grad2 is not None:          # (bf16: g = d1 + d2, the sum in fp32, stored over d1)
+            L.check(lib.bp_act_backward(C.byref(out.grad), C.byref(out.grad2), C.byref(out.view), None, None,
+                                        C.byref(out.grad), L.ptr(self.sums), L.ptr(self._ws()), plan.ws_bytes, st),
+                    f"{self.name} gradient sum")
+        L.check(lib.bp_view_cast(C.byref(out.grad), None, C.byref(self.dx), st), f"{self.name} cast backward")
+        plan.prof_end(t0, self, "cast_backward", 2 + 2 * (out.grad2 is not None))
+
+
 class PackBatch:
     """All weight re-layouts of a plan in one launch (``bp_conv_pack_jobs``) instead of two per layer.
 
@@ -1378,6 +1451,12 @@ def compile_sequential(plan, prefix, architecture, holders, inp, out_slot=None, 
                 first = False
             i = b["end"]
             continue
+        if name in _CONV_LIKE:
+            want = getattr(plan, "in_dtype", lambda n_: None)(f"{prefix}{i}")
+            if want is not None and want != cur.dt:
+                u = CastUnit(plan, f"{prefix}{i}.cast", cur, want == L.BF16, need_dgrad=(need_input_grad or not first))
+                units.append(u)
+                cur = u.out
         if name in ("conv", "sn conv", "transp conv"):
             holder = holders[i]
             j = i + 1

@@ -1525,21 +1525,25 @@ class CGANPainter(Painter):
     transforms with its statistics."""
 
     K = (4.0, 1.0)
-    META_KEYS = ("stats", "K", "tile_size", "n_res", "input_field", "label_fields", "paint_dtype")
-    OPTIONAL_META = {"paint_dtype": "fp32"}          # keys a checkpoint written before they existed lacks: their meaning there
+    META_KEYS = ("stats", "K", "tile_size", "n_res", "input_field", "label_fields", "paint_dtype",
+                 "train_dtype")
+    OPTIONAL_META = {"paint_dtype": "fp32", "train_dtype": "fp32"}          # keys a checkpoint written before they existed lacks: their meaning there
 
     def __init__(self, training_data_set=None, tile_size=512, compute_device="cuda:0", n_res=9, filename=None,
-                 paint_dtype="fp32"):
+                 paint_dtype="fp32", train_dtype="fp32"):
+        """``paint_dtype`` / ``train_dtype``: "fp32" or "bf16", the arithmetic of the generator's 128-channel trunk when
+        painting / of its residual blocks when training (models/cgan.py); a ``(state, meta)`` checkpoint brings its own."""
         from .models.cgan import CGAN
         self.compute_device = compute_device
         self.training_data = training_data_set
         self.stats = None if training_data_set is None else training_data_set.stats
         self.input_field, self.label_fields = "dm", ["pressure"]
         self.tile_size, self.n_res = tile_size, n_res
-        self.paint_dtype = paint_dtype
+        self.paint_dtype, self.train_dtype = paint_dtype, train_dtype
         if isinstance(filename, (tuple, list)):
             self._apply_meta(self._read_meta(filename[1]))          # (the model's geometry comes from the checkpoint)
-        self.model = CGAN(tile_size=self.tile_size, device=compute_device, n_res=self.n_res, paint_dtype=self.paint_dtype)
+        self.model = CGAN(tile_size=self.tile_size, device=compute_device, n_res=self.n_res, paint_dtype=self.paint_dtype,
+                          train_dtype=self.train_dtype)
         if filename is not None:
             self.load_state_from_file(filename, compute_device)
 
@@ -1675,7 +1679,7 @@ class CGANPainter(Painter):
         """What a painter needs besides the state dict to paint in another process."""
         return {"stats": self.stats, "K": tuple(self.K), "tile_size": self.tile_size, "n_res": self.n_res,
                 "input_field": self.input_field, "label_fields": list(self.label_fields),
-                "paint_dtype": getattr(self, "paint_dtype", "fp32")}
+                "paint_dtype": getattr(self, "paint_dtype", "fp32"), "train_dtype": getattr(self, "train_dtype", "fp32")}
 
     def _apply_meta(self, d):
         missing = [k for k in self.META_KEYS if k not in d and k not in self.OPTIONAL_META]
@@ -1687,6 +1691,9 @@ class CGANPainter(Painter):
         self.paint_dtype = d.get("paint_dtype", self.OPTIONAL_META["paint_dtype"])
         if self.paint_dtype not in ("fp32", "bf16"):
             raise ValueError(f"CGAN checkpoint metadata: paint_dtype {self.paint_dtype!r}")
+        self.train_dtype = d.get("train_dtype", self.OPTIONAL_META["train_dtype"])
+        if self.train_dtype not in ("fp32", "bf16"):
+            raise ValueError(f"CGAN checkpoint metadata: train_dtype {self.train_dtype!r}")
 
     @staticmethod
     def _read_meta(path):
@@ -1711,5 +1718,6 @@ class CGANPainter(Painter):
                                  f"model a {self.model.tile_size}^2 / {self.n_res}-block one")
             self._apply_meta(d)
             self.model.paint_dtype = self.paint_dtype          # (the inference plans are cached per dtype)
+            self.model.train_dtype = self.train_dtype          # (... and the training plans)
             filename = filename[0]
         self.model.load_state_dict(torch.load(filename, map_location=torch.device(compute_device)))

@@ -319,6 +319,12 @@ int bp_prelu_slope_grad(const double* sums, int32_t c, float* dslope, void* stre
 int bp_residual_forward(const bp_view* raw, const bp_pointwise* pw, const bp_view* skip,
                         const bp_pointwise* skip_pw, float slope, const bp_view* out, void* stream);
 
+/* ---- element type conversion: dst = act(src*scale+shift) (pw NULL: dst = src), fp32 -> bf16 (round to nearest even,
+ * after the pointwise, which is evaluated in fp32) or bf16 -> fp32 (exact).  Views of any channel stride / offset; 16
+ * bytes per lane where both have channel counts, strides and offsets that are multiples of 8 and 16-byte aligned bases.
+ * BP_EINVAL for views of one element type or of different shapes. */
+int bp_view_cast(const bp_view* src, const bp_pointwise* pw, const bp_view* dst, void* stream);
+
 /* ---- layout glue ---------------------------------------------------------------------------- */
 
 /* NCHW (N,c,H,W) -> channels [coff, coff+c) of `out`, and the aux label(s) (N,caux) broadcast to
