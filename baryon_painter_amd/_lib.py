@@ -202,6 +202,7 @@ SIGNATURES = {
                                          C.c_size_t, _P, _P]),
     "bp_gather_tiles_scales_mode": (C.c_int, [C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                               _P, _P, _P, C.c_size_t, _P, _P]),
+    "bp_gather_tiles_gan": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _VP, _VP, _VP, _P, _P]),
     "bp_adam_step": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
                                C.c_int32, _P]),
     "bp_adam_step_dev": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, _P]),

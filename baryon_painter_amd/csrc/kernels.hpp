@@ -172,6 +172,13 @@ int bp_sum_partials_strided(const double* partial, int nblk, int stride, int n, 
 int bp_sum_partials_req(const double* partial, int nblk, int n, const IgemmStatsReq* sr, hipStream_t st);
 int bp_sum_partials3(const double* partial, int nblk, int c, double* sums, hipStream_t st);
 
+// assemble_gan.hip: the CGAN's training batch in one launch (an entry point of include/bp_hip.h defined in a file of its
+// own; the descriptors and the pixel's value are assemble.hpp's, the transform is range_compress.hpp's rc_shift_log_cam)
+int bp_gather_tiles_gan(const void* in100, const void* in150, const void* in_xform, const float* in_minima,
+                        const void* lab100, const void* lab150, const void* lab_xform, const double* cam,
+                        const float* aux, int32_t n, int32_t tile, const bp_view* gen_in, const bp_view* d_real,
+                        const bp_view* d_fake_cond, float* x_nchw, void* stream);
+
 // pointwise_bf16.hip: the streaming kernels on dense bf16 views
 bool bp_bf16_dense_ok(const bp_view* v);
 size_t bp_bf16_reduce_workspace(const bp_view* x, int nsums);

@@ -263,8 +263,7 @@ __global__ __launch_bounds__(RB) void paint_load_cam_kernel(const float* src, in
   float v;
   if (ch < c) {
     // np.log(x / sigma + 1) / k0 - k1 with float32 x and float64 sigma: evaluated in double, stored as float32
-    const double x = (double)src[(n * c + ch) * hw + yx];
-    v = (float)(log(x / xf[3 * n] + 1.0) / xf[3 * n + 1] - xf[3 * n + 2]);
+    v = rc_shift_log_cam(src[(n * c + ch) * hw + yx], xf[3 * n], xf[3 * n + 1], xf[3 * n + 2]);
   } else {
     v = aux[n * caux + (ch - c)];
   }

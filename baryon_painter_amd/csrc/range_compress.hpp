@@ -62,6 +62,15 @@ __device__ __forceinline__ float rc_forward(const RcRec& r, float xf) {
   return t > -1.0 ? (float)(2.0 / (t + 1.0) - 1.001) : -1.0f;
 }
 
+// The CGAN's "shift-log-cam" map into the tanh range, np.log(x / sigma + 1) / k0 - k1 with a float32 x and float64
+// statistics (painter.CGANPainter.transform): evaluated in double, rounded to float32 once.  Not one of the six modes:
+// ONE definition all the same, shared by the paint path (paint.hip, bp_paint_load_cam) and the CGAN's batch assembly
+// (assemble_gan.hip), so that a tile a painter trains on and the same tile it later paints are the same bits.
+__device__ __forceinline__ float rc_shift_log_cam(float xf, double sigma, double k0, double k1) {
+#pragma clang fp contract(off)
+  return (float)(log((double)xf / sigma + 1.0) / k0 - k1);
+}
+
 __device__ __forceinline__ float rc_expf(float t) { return (float)exp((double)t); }   // correctly rounded float32 exp
 
 // float32 activation -> physical value (the float64 the host holds, rounded to float32 once)

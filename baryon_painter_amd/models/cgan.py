@@ -120,6 +120,7 @@ class _GanPlan(PlanBase):
         self.v_fake_cond = L.View(di.buf[n:].data_ptr(), n, h_, w_, 2, di.cstride, 0)
         self.v_real_x = L.View(di.buf.data_ptr(), n, h_, w_, 1, di.cstride, 2)
         self.v_fake_x = L.View(di.buf[n:].data_ptr(), n, h_, w_, 1, di.cstride, 2)
+        self.v_real = L.View(di.buf.data_ptr(), n, h_, w_, 3, di.cstride, 0)        # [dm, aux, pressure] of the real half
         self.d_in_fake.ensure_grad()
         self.v_dfake = L.View(self.d_in_fake.grad_buf.data_ptr(), n, h_, w_, 1, di.cstride, 2)
         self.cnt_d = float(n * ds.h * ds.w)           # discriminator outputs per half
@@ -155,10 +156,22 @@ class _GanPlan(PlanBase):
         self._keep = (y.contiguous(), zc.reshape(self.n, 1).contiguous())
         L.check(lib.bp_nchw_to_view(L.ptr(self._keep[0]), 1, L.ptr(self._keep[1]), 1, C.byref(self.y2.view), st),
                 "generator input")
+        self.forward_g(training)
+
+    def forward_g(self, training):
+        """The generator over ``y2`` as it stands; fake = tanh(g_raw), written into the pressure channel of the fake half
+        of the D input."""
         for u in self.g_units:
             u.forward(training)
-        # fake = tanh(g_raw), written into the pressure channel of the fake half of the D input
-        L.check(lib.bp_unary_forward(C.byref(self.g_raw.view), None, 1, C.byref(self.v_fake_x), st), "tanh")
+        L.check(self.lib.bp_unary_forward(C.byref(self.g_raw.view), None, 1, C.byref(self.v_fake_x), _stream()), "tanh")
+
+    def fill(self, fn):
+        """Let ``fn`` write the step's inputs in place of ``generate``'s and ``load_real``'s copies:
+        ``fn(gen_in, d_real, d_fake_cond, x_nchw)`` receives the generator's input ``y2.view`` (c = 2: [dm, aux]), the real
+        half of ``d_in`` as one view (c = 3: [dm, aux, pressure]), the conditioning channels of the fake half (c = 2) and
+        the dense ``x_nchw`` tensor (pressure).  It owns exactly those channels: the pad channel of ``d_in`` belongs to
+        ``Slot.new`` and the fake half's pressure channel to the generator's tanh.  ``fn`` enqueues on the current stream."""
+        fn(self.y2.view, self.v_real, self.v_fake_cond, self.x_nchw)
 
     def load_real(self, x):
         lib, st = self.lib, _stream()
@@ -488,6 +501,25 @@ class CGAN(torch.nn.Module):
             self._attach_grads()
             plan.generate(y, zc, self.training)
             plan.load_real(x)
+            return self._iterate(plan, opt_g, opt_d, capture)
+
+    def train_step_assembled(self, fill, n, opt_g, opt_d, capture=None):
+        """``train_step`` for a batch of ``n`` that is assembled on the device: ``fill(plan)`` writes the step's inputs
+        straight into the training plan's buffers, through ``plan.fill`` (``_GanPlan.fill`` hands out the four
+        destinations) -- e.g. ``lambda plan: assembler.gather_gan(indices, cam, aux, plan)``, one ``bp_gather_tiles_gan``
+        launch (utils.datasets.DeviceTileAssembler) -- in place of the upload, the copies and the four layout launches of
+        ``train_step``.  From there on the two methods run the same function: the same inputs give the same bits.
+        Returns the loss terms as device scalars."""
+        with torch.no_grad():
+            plan = self._plan(int(n))
+            self._attach_grads()
+            fill(plan)
+            plan.forward_g(self.training)
+            return self._iterate(plan, opt_g, opt_d, capture)
+
+    def _iterate(self, plan, opt_g, opt_d, capture):
+        """The alternating iteration over a plan whose inputs are in place and whose generator has run."""
+        with torch.no_grad():
             # ---- discriminator step
             plan.discriminate(self.training)
             plan.d_losses()

@@ -1570,8 +1570,22 @@ class CGANPainter(Painter):
         sched = [torch.optim.lr_scheduler.StepLR(o, step_size=lr_decay_every, gamma=lr_decay) for o in (opt_g, opt_d)]
         ds, log = self.training_data, []
         rng = np.random.default_rng(0)
+        asm = getattr(self, "device_assembler", None)
+        pending = []                                 # device path: loss dicts still on the device
         for it in range(n_iter):
             idx = rng.integers(0, len(ds), batch_size)
+            if asm is not None:                      # index arithmetic and launches only: nothing waits for the device
+                cam, aux = self._cam_rows([ds.sample_idx_to_redshift(int(i)) for i in idx])
+                pending.append(m.train_step_assembled(lambda plan: asm.gather_gan(idx, cam, aux, plan), batch_size,
+                                                      opt_g, opt_d))
+                for s in sched:
+                    s.step()
+                if it == n_iter - 1 or (verbose and it % 50 == 0):
+                    log.extend(self._download_losses(pending))
+                    pending = []
+                    if verbose and it % 50 == 0:
+                        print(it, log[-1])
+                continue
             dm, pr, zs = [], [], []
             for i in idx:
                 d, p, z = ds.raw_fields(int(i)) if hasattr(ds, "raw_fields") else self._raw(ds, int(i))
@@ -1591,6 +1605,46 @@ class CGANPainter(Painter):
     def _raw(ds, i):
         z = ds.sample_idx_to_redshift(i)
         return ds.get_input_sample(i, transform=False), ds.get_label_sample(i, transform=False)[0], z
+
+    # ---- training batches assembled on the device
+    def use_device_assembly(self):
+        """Keep the training stacks in HBM and let ``train`` assemble every batch there: one ``bp_gather_tiles_gan`` launch
+        per iteration cuts, permutes, adds, scales and transforms the tiles of both fields and writes them straight into
+        the training plan's inputs (utils.datasets.DeviceTileAssembler.gather_gan, CGAN.train_step_assembled), and the
+        loop never waits for the device.  Same index sequence, optimisers, schedulers and log as the host loop.
+        NotImplementedError, before anything is uploaded, for a training set without slab stacks (``SyntheticTileDataset``
+        makes its tiles on the host)."""
+        ds = self.training_data
+        if ds is None:
+            raise RuntimeError("use_device_assembly needs a training set")
+        need = ("data", "sample_idx_to_tile", "sample_idx_to_tile_permutation", "apply_tile_permutation")
+        if not all(hasattr(ds, a) for a in need):
+            raise NotImplementedError(f"{type(ds).__name__} has no slab stacks to keep in HBM: the device assembly "
+                                      "serves BAHAMASDataset-like training sets")
+        if ds.input_field != self.input_field or list(ds.label_fields)[:1] != self.label_fields:
+            raise NotImplementedError(f"the CGAN trains on {self.input_field} -> {self.label_fields[0]}; the training set "
+                                      f"holds {ds.input_field} -> {list(ds.label_fields)}")
+        self.device_assembler = datasets.DeviceTileAssembler(ds, self.compute_device, mode=None)
+
+    def _cam_rows(self, zs):
+        """(cam (n, 2, 3) float64, aux (n,) float32) of ``bp_gather_tiles_gan`` for samples at redshifts ``zs``:
+        {sigma, k0, k1} of the input and of the label field with the sigma ``transform`` divides by, and z - 1 in float32
+        as ``CGAN._inputs`` forms it.  One row per redshift is computed once."""
+        memo = self.__dict__.setdefault("_cam_memo", {})
+        for z in zs:
+            if z not in memo:
+                memo[z] = [[self._sigma(f, z), self.K[0], self.K[1]] for f in (self.input_field, self.label_fields[0])]
+        return (np.array([memo[z] for z in zs], np.float64),
+                np.asarray(zs, np.float64).astype(np.float32) - np.float32(1.0))
+
+    @staticmethod
+    def _download_losses(pending):
+        """Loss dicts of device scalars -> dicts of floats, in one download."""
+        if not pending:
+            return []
+        keys = list(pending[0])
+        vals = torch.stack([d[k] for d in pending for k in keys]).cpu().tolist()
+        return [dict(zip(keys, vals[i * len(keys):(i + 1) * len(keys)])) for i in range(len(pending))]
 
     # ------------------------------------------------------------------------------ inference
     def paint(self, input, z=0.0, transform=True, inverse_transform=True, pixel_noise=False):

@@ -386,6 +386,15 @@ class DeviceTileAssembler:
         return 1 if self.scales is None else self.scales["n_scale"] + int(self.scales["include_original"])
 
     def _perm_affine(self, p):
+        """``_perm_affine_compute(p)``, computed once per assembler and code: the two t x t index grids it builds cost more
+        than a training step at 512^2 when every sample asks for them four times."""
+        memo = self.__dict__.setdefault("_affine_memo", {})
+        key = (self.ds.tile_size, int(p))
+        if key not in memo:
+            memo[key] = self._perm_affine_compute(p)
+        return memo[key]
+
+    def _perm_affine_compute(self, p):
         """(r0, rr, rc, c0, cr, cc) of ``apply_tile_permutation`` for code p, from the images of three
         index points under the very same NumPy operations."""
         t = self.ds.tile_size
@@ -465,3 +474,76 @@ class DeviceTileAssembler:
         z = torch.tensor([ds.sample_idx_to_redshift(int(i)) for i in indices], device=self.device,
                          dtype=torch.float32)
         return torch.cat(outs[1:], dim=1), outs[0], z
+
+    def _gan_block(self, indices, cam, aux):
+        """The packed host image of one ``bp_gather_tiles_gan`` call: {name: (byte offset, array)} and its size.  The tile
+        descriptors of both fields (those of ``_descriptors``, with the index arithmetic done once per sample), the two
+        scale records, ``cam`` (n, 2, 3) float64 and ``aux`` (n,) float32, every part 8-byte aligned."""
+        ds, t = self.ds, self.ds.tile_size
+        fields = (ds.input_field, ds.label_fields[0])
+        rows = {(f, slab): [] for f in fields for slab in ("100", "150")}
+        for idx in indices:
+            idx = int(idx)
+            z = ds.sample_idx_to_redshift(idx)
+            s100, y100, x100, s150, y150, x150 = ds.sample_idx_to_tile(idx)
+            p100, p150 = ds.sample_idx_to_tile_permutation(idx)
+            for slab, s, ty, tx, p in (("100", s100, y100, x100, p100), ("150", s150, y150, x150, p150)):
+                aff = self._perm_affine(p)
+                for f in fields:
+                    st = self.stacks[(f, z, slab)]
+                    g = st.shape[-1]
+                    rows[(f, slab)].append((st.data_ptr() + 4 * ((s * g + ty * t) * g + tx * t), g) + aff + (0,))
+        n = len(indices)
+        xf = {f: np.zeros(n, self.XF) for f in fields}
+        xf[fields[0]]["scale"] = slics_scale(ds.n_grid) if ds.scale_to_SLICS else 1.0
+        xf[fields[1]]["scale"] = 1.0
+        cam = np.ascontiguousarray(cam, dtype=np.float64)
+        aux = np.ascontiguousarray(aux, dtype=np.float32)
+        if cam.shape != (n, 2, 3) or aux.shape != (n,):
+            raise ValueError(f"cam {cam.shape} / aux {aux.shape}: expected ({n}, 2, 3) and ({n},)")
+        parts = [("in100", np.array(rows[(fields[0], "100")], self.REC100)),
+                 ("in150", np.array(rows[(fields[0], "150")], self.REC100)), ("in_xf", xf[fields[0]]),
+                 ("lab100", np.array(rows[(fields[1], "100")], self.REC100)),
+                 ("lab150", np.array(rows[(fields[1], "150")], self.REC100)), ("lab_xf", xf[fields[1]]),
+                 ("cam", cam), ("aux", aux)]
+        layout, off = {}, 0
+        for name, a in parts:
+            layout[name] = (off, a)
+            off += (a.nbytes + 7) // 8 * 8
+        return layout, off
+
+    def gather_gan(self, indices, cam, aux, plan):
+        """One CGAN training batch, written straight into the inputs of the training plan ``plan`` (models.cgan._GanPlan of
+        ``len(indices)`` samples) by ONE ``bp_gather_tiles_gan`` launch on the current stream: the generator's input, both
+        halves' conditioning channels and the real field of the discriminator's input, and the dense label plane.
+
+        ``cam``: (n, 2, 3) float64, {sigma, k0, k1} of the input field and of the label field per sample (the CGAN's
+        "shift-log-cam" transform); ``aux``: (n,) float32, the conditioning value.  The assembler is one built with
+        ``mode=None``: no chain is read, of the scale records only ``scale`` is used.  ``subtract_minimum`` sets get the
+        input field's ``bp_tile_minima`` in front.  Descriptors, ``cam`` and ``aux`` go up as one packed block in one
+        host-to-device copy from pinned memory; nothing waits for the device: the block (and the minima) are stream-ordered
+        memory of the caching allocator and may be released as soon as the launches are enqueued."""
+        torch, L, ds, t = self.torch, self.L, self.ds, self.ds.tile_size
+        n = len(indices)
+        if plan.n != n:
+            raise ValueError(f"the plan holds {plan.n} samples, the batch {n}")
+        layout, nbytes = self._gan_block(indices, cam, aux)
+        host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)     # (the caching host allocator keeps it until
+        hv = host.numpy()                                                  # the copy below has run)
+        for off, a in layout.values():
+            hv[off:off + a.nbytes] = a.reshape(-1).view(np.uint8)
+        dev = host.to(self.device, non_blocking=True)
+        base = dev.data_ptr()
+        p = {name: C.c_void_p(base + off) for name, (off, _) in layout.items()}
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        minima = None
+        if ds.subtract_minimum:
+            minima = torch.empty(n, device=self.device)
+            L.check(self.lib.bp_tile_minima(p["in100"], p["in150"], p["in_xf"], n, t, L.ptr(minima), st), "tile minima")
+
+        def fill(gen_in, d_real, d_fake_cond, x_nchw):
+            L.check(self.lib.bp_gather_tiles_gan(p["in100"], p["in150"], p["in_xf"], L.ptr(minima), p["lab100"],
+                                                 p["lab150"], p["lab_xf"], p["cam"], p["aux"], n, t, C.byref(gen_in),
+                                                 C.byref(d_real), C.byref(d_fake_cond), L.ptr(x_nchw), st),
+                    "gather tiles (CGAN)")
+        plan.fill(fill)

@@ -847,6 +847,29 @@ int bp_gather_tiles_scales_mode(int32_t mode, const double* records, const void*
                                 const void* xform, const float* minima, int32_t n, int32_t tile, int32_t n_scale,
                                 int32_t include_original, const double* weights, const int32_t* radii, void* scratch,
                                 size_t scratch_bytes, float* out_nchw, void* stream);
+/* The CGAN's training batch in ONE launch, written straight into the inputs of its training plan (models/cgan.py).
+ * in100 / in150 / in_xform and lab100 / lab150 / lab_xform: bp_gather_tiles' records of the input field (dm) and of the
+ * label field (pressure); of the xform records only `scale` is read.  in_minima: NULL, or the bp_tile_minima of the input
+ * field, subtracted in float32 in front of the transform (subtract_minimum sets).  cam: (n, 2, 3) float64, the rows
+ * {sigma, k0, k1} of the input field and then of the label field.  aux: n float32, the conditioning value z - 1.
+ * A pixel is  (float) (log((double) s / sigma + 1) / k0 - k1),  s = scale * (tile100 + tile150) [- minimum]: the value
+ * bp_gather_tiles forms at mode 0 under bp_paint_load_cam's transform, bit for bit (one shared device function).
+ * Destinations, all (n, tile, tile) fp32 views:
+ *   gen_in      c = 2: [dm, aux]             the generator's input
+ *   d_real      c = 3: [dm, aux, pressure]   the real half of the discriminator's input
+ *   d_fake_cond c = 2: [dm, aux]             the conditioning channels of the fake half
+ *   x_nchw      (n, 1, tile, tile) dense     pressure, as bp_l1_sum and bp_tanh_l1_backward read it
+ * Only the named channels are written: the bytes between coff + c and cstride of a pixel (a pad channel, the fake half's
+ * pressure channel) are left alone.  Every stack value is read once; dm is stored three times, pressure twice.  A lane
+ * owns four consecutive pixels of a row: 16-byte stores where a destination is dense and aligned, 8- and 4-byte stores
+ * with the same values otherwise.  Any tile >= 1 with tile^2 < 2^31, any n >= 1, 64-bit addressing of the destinations.
+ * No atomics, no workspace, no host synchronisation.  Before anything is written: BP_EINVAL for a NULL argument other
+ * than in_minima, n <= 0, tile <= 0, a view that is not (n, tile, tile) or has another channel count; BP_EUNSUPPORTED for
+ * a bf16 view. */
+int bp_gather_tiles_gan(const void* in100, const void* in150, const void* in_xform, const float* in_minima,
+                        const void* lab100, const void* lab150, const void* lab_xform, const double* cam,
+                        const float* aux, int32_t n, int32_t tile, const bp_view* gen_in, const bp_view* d_real,
+                        const bp_view* d_fake_cond, float* x_nchw, void* stream);
 
 /* ---- optimiser (replaces torch.optim.Adam.step, painter.py:93,228; same arithmetic) --------- */
 int bp_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
