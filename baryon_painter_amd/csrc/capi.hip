@@ -230,19 +230,34 @@ int bp_conv_backward_data(const bp_conv* cv, const bp_view* dy, const float* pac
                           bp_stream(stream));
 }
 
-size_t bp_conv_backward_weight_workspace(const bp_conv* cv, const bp_view* x, const bp_view* dy) {
-  if (!conv_ok(cv) || !shapes_ok(cv, x, dy, true)) return 0;
-  const bp_view* X = cv->transposed ? dy : x;
-  const bp_view* Y = cv->transposed ? x : dy;
-  // (the larger of the fp32 and the bf16 kernel's needs: the caller sizes one workspace per layer)
-  size_t main = (x->dtype == BP_F32 && dy->dtype == BP_F32) ? bp_wgrad_mfma_workspace(cv, X, Y) : 0;
-  const size_t mb = bp_wgrad_bf16_workspace(cv, X, Y);
-  if (mb > main) main = mb;
-  return align256(main) + align256(bp_channel_sums_workspace(dy)) + align256((size_t)2 * dy->c * sizeof(double));
+// The workspace of one layer: main, then the channel sums of dy, then 2 * c doubles.  `main_f32`: what the fp32 table
+// asks for the layer's workspace query (0: fp32 not asked, or unsupported); the bf16 table's need is taken in as well,
+// since the caller sizes one workspace per layer.
+static size_t weight_workspace(const WgradCall& query, size_t main_f32, const bp_view* dy) {
+  WgradSelection b;
+  const size_t main_bf16 = bp_wgrad_select(true, query, &b) == BP_OK ? b.ws_bytes : 0;
+  return align256(main_f32 > main_bf16 ? main_f32 : main_bf16) + align256(bp_channel_sums_workspace(dy)) +
+         align256((size_t)2 * dy->c * sizeof(double));
 }
 
-// One walk for the call and for bp_conv_backward_weight_plan (`plan`: nothing is launched, no workspace is asked for;
-// plan = {family, nsplit, cxp, cyp} of the kernel the call would run).
+// (a workspace query: no pointwise operand, un-shared)
+static WgradCall weight_query(const bp_conv* cv, const bp_view* x, const bp_view* dy) {
+  const PW none{nullptr, nullptr, nullptr};
+  return WgradCall{cv, cv->transposed ? dy : x, none, cv->transposed ? x : dy, none, false};
+}
+
+size_t bp_conv_backward_weight_workspace(const bp_conv* cv, const bp_view* x, const bp_view* dy) {
+  if (!conv_ok(cv) || !shapes_ok(cv, x, dy, true)) return 0;
+  const WgradCall query = weight_query(cv, x, dy);
+  WgradSelection f;
+  const bool f32 = x->dtype == BP_F32 && dy->dtype == BP_F32 && bp_wgrad_select(false, query, &f) == BP_OK;
+  return weight_workspace(query, f32 ? f.ws_bytes : 0, dy);
+}
+
+// The call and bp_conv_backward_weight_plan (`plan`: nothing is launched, no workspace is asked for; plan = {family,
+// nsplit, cxp, cyp} of the kernel the call would run).  The table is walked once for the layer's workspace query; that
+// selection is the call's own unless the call carries what the query does not (a pointwise operand, BP_IMPL_SHARED),
+// and then the table is walked once more for the call.
 static int backward_weight(const bp_conv* cv, const bp_view* x, const bp_pointwise* x_pw, const bp_view* dy,
                            float* dw_torch, float* dbias, void* workspace, size_t workspace_bytes, int impl,
                            void* stream, int32_t* plan) {
@@ -250,33 +265,41 @@ static int backward_weight(const bp_conv* cv, const bp_view* x, const bp_pointwi
   const WgradPrivateWs priv(!plan && (impl & BP_IMPL_DEFER) != 0);      // (this call's reduction may wait for the flush)
   impl &= ~(BP_IMPL_SHARED | BP_IMPL_DEFER);
   if (!conv_ok(cv) || !shapes_ok(cv, x, dy, impl == BP_IMPL_BF16) || (!plan && !dw_torch)) return BP_EINVAL;
-  const bp_view* X = cv->transposed ? dy : x;
-  const bp_view* Y = cv->transposed ? x : dy;
-  const PW none{nullptr, nullptr, nullptr};
-  const PW pwx = cv->transposed ? none : bp_pw(x_pw);
-  const PW pwy = cv->transposed ? bp_pw(x_pw) : none;
+  const bool bf16 = impl == BP_IMPL_BF16;
+  const WgradCall query = weight_query(cv, x, dy);
+  WgradCall call = query;
+  (cv->transposed ? call.pwy : call.pwx) = bp_pw(x_pw);
+  call.shared = shared && !bf16;             // (the bf16 kernels have no shared form)
   hipStream_t st = bp_stream(stream);
-  if (impl == BP_IMPL_BF16) {
-    if (dbias) return BP_EUNSUPPORTED;       // (bias gradients: the fp32 path; the CVAE's convolutions have none)
-    const size_t need = bp_wgrad_bf16_workspace(cv, X, Y);
-    if (!need) return BP_EUNSUPPORTED;
-    if (!plan && (!workspace || workspace_bytes < need)) return BP_EWORKSPACE;
-    return bp_wgrad_bf16_run(cv, X, pwx, Y, pwy, dw_torch, workspace, workspace_bytes, st, plan);
-  }
-  const size_t ws_main = align256(bp_wgrad_mfma_workspace(cv, X, Y));
-  if (impl == BP_IMPL_AUTO) impl = ws_main ? BP_IMPL_MFMA : BP_IMPL_DIRECT;
-  if (!plan && (impl == BP_IMPL_MFMA || dbias)) {
-    if (!workspace || workspace_bytes < bp_conv_backward_weight_workspace(cv, x, dy)) return BP_EWORKSPACE;
+  if (bf16 && dbias) return BP_EUNSUPPORTED;       // (bias gradients: the fp32 path; the CVAE's convolutions have none)
+  WgradSelection sel;
+  const bool found = bp_wgrad_select(bf16, query, &sel) == BP_OK;
+  if (bf16 && !found) return BP_EUNSUPPORTED;
+  size_t ws_main = bf16 ? workspace_bytes : 0;      // bytes of `workspace` the kernel may use
+  if (bf16) {
+    if (!plan && (!workspace || workspace_bytes < sel.ws_bytes)) return BP_EWORKSPACE;
+  } else {
+    ws_main = found ? align256(sel.ws_bytes) : 0;
+    if (impl == BP_IMPL_AUTO) impl = found ? BP_IMPL_MFMA : BP_IMPL_DIRECT;
+    if (!plan && (impl == BP_IMPL_MFMA || dbias)) {
+      if (!workspace || workspace_bytes < weight_workspace(query, found ? sel.ws_bytes : 0, dy)) return BP_EWORKSPACE;
+    }
+    if (impl == BP_IMPL_MFMA && !found) return BP_EUNSUPPORTED;
   }
   int rc;
-  if (impl == BP_IMPL_MFMA) {
-    if (!ws_main) return BP_EUNSUPPORTED;
-    rc = bp_wgrad_mfma(cv, X, pwx, Y, pwy, dw_torch, workspace, ws_main, st, shared, plan);
+  if (bf16 || impl == BP_IMPL_MFMA) {
+    if ((call.pwx.scale || call.pwy.scale || call.shared) && bp_wgrad_select(bf16, call, &sel) != BP_OK)
+      return BP_EUNSUPPORTED;
+    if (plan) {
+      plan[0] = sel.row.id; plan[1] = sel.row.nsplit; plan[2] = sel.row.cxp; plan[3] = sel.row.cyp;
+      return BP_OK;
+    }
+    rc = bp_wgrad_run(sel, call, dw_torch, workspace, ws_main, st);
   } else if (plan) {
     plan[0] = BP_WG_DIRECT; plan[1] = plan[2] = plan[3] = 0;
     rc = BP_OK;
   } else {
-    rc = bp_direct_wgrad(cv, X, pwx, Y, pwy, dw_torch, st);
+    rc = bp_direct_wgrad(cv, call.X, call.pwx, call.Y, call.pwy, dw_torch, st);
   }
   if (rc != BP_OK || plan) return rc;
   if (dbias) {

@@ -724,13 +724,14 @@ const ConvFamily& bp_family_enc() {
 
 // Weight gradient of the same layer (either orientation: X is the 8-channel tensor at 4x the resolution of the
 // 16-channel Y).  Same contract as bp_wgrad_small (conv_wgrad.hip reduces the partials).
-int bp_wgrad_enc(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* ws,
-                 size_t ws_bytes, size_t* need, int* nsplit, int* cxp, int* cyp, hipStream_t st, bool dry) {
+static int wgrad_enc(const WgradCall& c, float* ws, size_t ws_bytes, WgradRow* row, hipStream_t st, bool dry) {
+  const bp_conv* cv = c.cv;
+  const bp_view *X = c.X, *Y = c.Y;
   if (enc_off() || cv->k != 8 || cv->stride != 4 || cv->pad != 2 || X->c != 8 || Y->c != 16) return BP_EUNSUPPORTED;
   EncWArgs a{};
   a.X = X->ptr; a.xh = X->h; a.xw = X->w; a.xcs = X->cstride; a.xco = X->coff;
   a.Y = Y->ptr; a.yh = Y->h; a.yw = Y->w; a.ycs = Y->cstride; a.yco = Y->coff;
-  a.pwx = pwx; a.pwy = pwy; a.n = X->n;
+  a.pwx = c.pwx; a.pwy = c.pwy; a.n = X->n;
   a.tiles_x = bp_ceil_div(Y->w, 16);
   a.tiles_y = bp_ceil_div(Y->h, EW_R);
   const int64_t nt = (int64_t)X->n * a.tiles_x * a.tiles_y;
@@ -738,14 +739,18 @@ int bp_wgrad_enc(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_vi
   a.ntiles = (int)nt;
   static const int cap = getenv("BP_ENC_WSPLIT") ? atoi(getenv("BP_ENC_WSPLIT")) : 768;      // (41 KB of LDS: three workgroups per CU)
   const int grid = a.ntiles < cap ? a.ntiles : cap;
-  *need = (size_t)grid * 8192 * sizeof(float);
-  *nsplit = grid; *cxp = 8; *cyp = 16;
+  *row = WgradRow{BP_WG_ENC, grid, 8, 16, (size_t)grid * 8192 * sizeof(float)};
   if (dry) return BP_OK;
-  if (!ws || ws_bytes < *need) return BP_EWORKSPACE;
+  if (!ws || ws_bytes < row->bytes) return BP_EWORKSPACE;
   a.ws = ws;
   a.xvec = bp_view_vec4(X) ? 1 : 0;
   a.yvec = bp_view_vec4(Y) ? 1 : 0;
   hipLaunchKernelGGL(enc_wgrad_kernel, dim3(grid), dim3(256), EW_LDS, st, a);
   BP_CHECK_LAUNCH();
   return BP_OK;
+}
+
+const WgradFamily& bp_wgrad_family_enc() {
+  static const WgradFamily f = {"enc", bp_wgrad_plan_of<wgrad_enc>, bp_wgrad_run_of<wgrad_enc>, false, false};
+  return f;
 }

@@ -378,33 +378,30 @@ const ConvFamily& bp_family_stem() {
 }
 
 // ---- weight gradient
-bool bp_stem_wgrad_ok(const bp_conv* cv, const bp_view* X, const bp_view* Y, const PW& pwy, const float* dbias) {
+static bool stem_wgrad_plan(const WgradCall& c, WgradRow* row) {
   static const bool off = getenv("BP_NOSTEM") != nullptr;
-  return !off && !cv->transposed && cv->k == K5 && cv->stride == 1 && cv->pad == 2 && cv->cin == CI3 &&
-         cv->cout == CO16 && X->c == CI3 && Y->c == CO16 && X->h == Y->h && X->w == Y->w && pwy.scale == nullptr &&
-         dbias == nullptr && X->dtype == BP_F32 && Y->dtype == BP_F32;
-}
-
-static int stem_wgrad_tiles(const bp_view* X) { return bp_ceil_div(X->w, TW) * bp_ceil_div(X->h, TH) * X->n; }
-
-int bp_stem_wgrad_grid(const bp_view* X) { return stem_wgrad_grid(stem_wgrad_tiles(X)); }
-
-size_t bp_stem_wgrad_workspace(const bp_view* X) {
-  const int grid = stem_wgrad_grid(stem_wgrad_tiles(X));
+  const bp_conv* cv = c.cv;
+  const bp_view *X = c.X, *Y = c.Y;
+  if (off || cv->transposed || cv->k != K5 || cv->stride != 1 || cv->pad != 2 || cv->cin != CI3 || cv->cout != CO16 ||
+      X->c != CI3 || Y->c != CO16 || X->h != Y->h || X->w != Y->w || c.pwy.scale != nullptr || X->dtype != BP_F32 ||
+      Y->dtype != BP_F32)
+    return false;
+  const int grid = stem_wgrad_grid(bp_ceil_div(X->w, TW) * bp_ceil_div(X->h, TH) * X->n);
   const int chunks = bp_ceil_div(grid, FOLD_ROWS);
-  return (size_t)grid * WG_ELEMS * sizeof(float) + (size_t)chunks * WG_ELEMS * sizeof(double);
+  *row = WgradRow{BP_WG_STEM, grid, 0, 0, (size_t)grid * WG_ELEMS * sizeof(float) + (size_t)chunks * WG_ELEMS * sizeof(double)};
+  return true;
 }
 
-int bp_stem_wgrad(const bp_view* X, const PW& pwx, const bp_view* Y, float* dst, void* workspace, size_t workspace_bytes,
-                  hipStream_t st) {
-  if (!workspace || workspace_bytes < bp_stem_wgrad_workspace(X)) return BP_EWORKSPACE;
+static int stem_wgrad_run(const WgradCall& c, const WgradRow& row, float* dst, void* workspace, size_t workspace_bytes,
+                          hipStream_t st) {
+  const bp_view *X = c.X, *Y = c.Y;
+  if (!workspace || workspace_bytes < row.bytes) return BP_EWORKSPACE;
   StemWgradArgs a{};
   a.x = X->ptr; a.h = X->h; a.w = X->w; a.x_cs = X->cstride; a.x_co = X->coff;
-  a.dy = Y->ptr; a.dy_cs = Y->cstride; a.dy_co = Y->coff; a.pw = pwx; a.n = X->n;
+  a.dy = Y->ptr; a.dy_cs = Y->cstride; a.dy_co = Y->coff; a.pw = c.pwx; a.n = X->n;
   a.tiles_x = bp_ceil_div(X->w, TW); a.tiles_y = bp_ceil_div(X->h, TH);
   a.x_vec = (X->cstride >= 4 && bp_view_vec4(X)) ? 1 : 0;
-  const int ntiles = stem_wgrad_tiles(X);
-  const int grid = stem_wgrad_grid(ntiles);
+  const int grid = row.nsplit;
   const int chunks = bp_ceil_div(grid, FOLD_ROWS);
   a.partial = reinterpret_cast<float*>(workspace);
   double* part2 = reinterpret_cast<double*>(a.partial + (size_t)grid * WG_ELEMS);
@@ -417,4 +414,10 @@ int bp_stem_wgrad(const bp_view* X, const PW& pwx, const bp_view* Y, float* dst,
                      reinterpret_cast<const float*>(part2), chunks, 0, (double*)nullptr, dst);
   BP_CHECK_LAUNCH();
   return BP_OK;
+}
+
+// (may_requalify: the predicate looks at the pointwise operand of Y, which a workspace query does not pass)
+const WgradFamily& bp_wgrad_family_stem() {
+  static const WgradFamily f = {"stem", stem_wgrad_plan, stem_wgrad_run, true, true};
+  return f;
 }

@@ -11,7 +11,6 @@
 // kernel adds them in a fixed order, so the gradient is bitwise reproducible (no float atomics).
 #include "common.hpp"
 #include "kernels.hpp"
-#include <cstdlib>
 #include <vector>
 
 namespace {
@@ -204,74 +203,7 @@ __global__ __launch_bounds__(64 * WR_GRP) void wgrad_reduce_batch_kernel(Wreduce
   wgrad_reduce_block<WR_GRP>(b.job[j], blk - b.first[j], sh);
 }
 
-struct WgradPlan {
-  int NTY, ncxt, ncyg, nsplit, tiles_x, tiles_y, IW, IWq, CXP, CYP;
-  size_t lds_bytes, ws_bytes;
-  bool ok;
-};
-
-WgradPlan wgrad_plan(const bp_conv* cv, const bp_view* X, const bp_view* Y) {
-  WgradPlan p{};
-  if (cv->k > KW_MAX) return p;
-  p.NTY = (Y->c > 16) ? 2 : 1;
-  const int CYB = 16 * p.NTY;
-  p.ncxt = bp_ceil_div(X->c, 16);
-  p.ncyg = bp_ceil_div(Y->c, CYB);
-  p.CXP = p.ncxt * 16;
-  p.CYP = p.ncyg * CYB;
-  p.tiles_x = bp_ceil_div(Y->w, WG_BW);
-  p.tiles_y = bp_ceil_div(Y->h, WG_BH);
-  const int64_t ntiles = (int64_t)Y->n * p.tiles_x * p.tiles_y;
-  const int64_t base = (int64_t)p.ncxt * p.ncyg * cv->k;
-  int64_t ns = (2048 + base - 1) / base;
-  if (ns > ntiles) ns = ntiles;
-  if (ns < 1) ns = 1;
-  if (ns > 65535) ns = 65535;
-  p.nsplit = (int)ns;
-  p.IW = (WG_BW - 1) * cv->stride + cv->k;
-  p.IWq = bp_ceil_div(p.IW, cv->stride);
-  const size_t lds_main = ((size_t)WG_BH * cv->stride * p.IWq * 16 + (size_t)p.NTY * WG_BH * WG_BW * 16) * 4;
-  const size_t lds_red = (size_t)4 * p.NTY * 64 * 4 * 4;
-  p.lds_bytes = lds_main > lds_red ? lds_main : lds_red;
-  p.ws_bytes = (size_t)p.nsplit * cv->k * cv->k * p.CYP * p.CXP * sizeof(float);
-  p.ok = p.lds_bytes <= 64 * 1024;
-  return p;
-}
-
 }  // namespace
-
-// the k8 stride-4 encoder layer (conv_enc.hip), one-channel tails (conv_wgrad_thin.hip), the tap-packed few-channel
-// kernel, then the tap-blocked one;
-// BP_EUNSUPPORTED -> generic kernel
-// *family (bp_conv_backward_weight_plan): the BP_WG_* value of the kernel that answered
-static int wgrad_fast(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* ws,
-                      size_t ws_bytes, size_t* need, int* nsplit, int* cxp, int* cyp, hipStream_t st, bool dry,
-                      int* family) {
-  // the output-stationary kernel of the 128 <-> 128 k3 trunk layers (conv_wgrad_ws_f32.hip)
-  int rc = bp_wgrad_ws_f32(cv, X, pwx, Y, pwy, ws, ws_bytes, need, nsplit, cxp, cyp, st, dry);
-  *family = BP_WG_WS_F32;
-  if (rc == BP_OK && dry) {        // (size the workspace for either kernel: bp_set_option may switch later)
-    size_t need2 = 0;
-    int ns2, cx2, cy2;
-    if (bp_wgrad_tiles(cv, X, pwx, Y, pwy, ws, ws_bytes, &need2, &ns2, &cx2, &cy2, st, true) == BP_OK && need2 > *need) *need = need2;
-  }
-  if (rc != BP_EUNSUPPORTED) return rc;
-  rc = bp_wgrad_enc(cv, X, pwx, Y, pwy, ws, ws_bytes, need, nsplit, cxp, cyp, st, dry);
-  *family = BP_WG_ENC;
-  if (rc == BP_EUNSUPPORTED) {
-    rc = bp_wgrad_thin(cv, X, pwx, Y, pwy, ws, ws_bytes, need, nsplit, cxp, cyp, st, dry);
-    *family = X->c == 1 ? BP_WG_THIN_C1 : BP_WG_THIN_CY1;
-  }
-  if (rc == BP_EUNSUPPORTED) {
-    rc = bp_wgrad_small(cv, X, pwx, Y, pwy, ws, ws_bytes, need, nsplit, cxp, cyp, st, dry);
-    *family = BP_WG_SMALL;
-  }
-  if (rc == BP_EUNSUPPORTED) {
-    rc = bp_wgrad_tiles(cv, X, pwx, Y, pwy, ws, ws_bytes, need, nsplit, cxp, cyp, st, dry);
-    *family = bp_wgrad_tiles_last_dma() ? BP_WG_TILES_DMA : BP_WG_TILES;
-  }
-  return rc;
-}
 
 // Per host thread: between bp_wgrad_defer_begin() and bp_wgrad_defer_flush() the reductions of calls flagged
 // BP_IMPL_DEFER are collected, not launched: the flag is the caller's promise that the call's workspace is its own
@@ -279,6 +211,8 @@ static int wgrad_fast(const bp_conv* cv, const bp_view* X, const PW& pwx, const 
 struct DeferState { bool on = false, private_ws = false; std::vector<WreduceArgs> jobs; };
 static thread_local DeferState t_defer;
 
+// (fills in the position of the (cx, cy) block inside dW: a WreduceArgs built with cx_total left at 0 wrote every
+//  produced channel onto the first one's row)
 static int wgrad_reduce(const float* ws, float* dst, int k, int cx, int cy, int CXP, int CYP, int nsplit,
                         hipStream_t st, int cx_total = -1, int cx_off = 0, int cy_off = 0, bool may_defer = true) {
   WreduceArgs r{};
@@ -339,176 +273,161 @@ int bp_wgrad_defer_flush_impl(hipStream_t st, int end) {
   return rc;
 }
 
+namespace {
+
+// The generic kernel: every layer of k <= 9 whose staged tiles fit the LDS.
+int wgrad_general(const WgradCall& c, float* ws, size_t ws_bytes, WgradRow* row, hipStream_t st, bool dry) {
+  const bp_conv* cv = c.cv;
+  const bp_view *X = c.X, *Y = c.Y;
+  if (cv->k > KW_MAX) return BP_EUNSUPPORTED;
+  const int NTY = (Y->c > 16) ? 2 : 1;
+  const int CYB = 16 * NTY;
+  WgradArgs a{};
+  a.ncxt = bp_ceil_div(X->c, 16);
+  a.ncyg = bp_ceil_div(Y->c, CYB);
+  a.CXP = a.ncxt * 16;
+  a.CYP = a.ncyg * CYB;
+  a.tiles_x = bp_ceil_div(Y->w, WG_BW);
+  a.tiles_y = bp_ceil_div(Y->h, WG_BH);
+  const int64_t ntiles = (int64_t)Y->n * a.tiles_x * a.tiles_y;
+  const int64_t base = (int64_t)a.ncxt * a.ncyg * cv->k;
+  int64_t ns = (2048 + base - 1) / base;
+  if (ns > ntiles) ns = ntiles;
+  if (ns < 1) ns = 1;
+  if (ns > 65535) ns = 65535;
+  a.nsplit = (int)ns;
+  a.IW = (WG_BW - 1) * cv->stride + cv->k;
+  a.IWq = bp_ceil_div(a.IW, cv->stride);
+  const size_t lds_main = ((size_t)WG_BH * cv->stride * a.IWq * 16 + (size_t)NTY * WG_BH * WG_BW * 16) * 4;
+  const size_t lds_red = (size_t)4 * NTY * 64 * 4 * 4;
+  const size_t lds_bytes = lds_main > lds_red ? lds_main : lds_red;
+  if (lds_bytes > 64 * 1024) return BP_EUNSUPPORTED;
+  *row = WgradRow{BP_WG_GENERAL, a.nsplit, a.CXP, a.CYP, (size_t)a.nsplit * cv->k * cv->k * a.CYP * a.CXP * sizeof(float)};
+  if (dry) return BP_OK;
+  if (!ws || ws_bytes < row->bytes) return BP_EWORKSPACE;
+  a.X = X->ptr; a.xh = X->h; a.xw = X->w; a.xcs = X->cstride; a.xco = X->coff; a.cx = X->c;
+  a.Y = Y->ptr; a.yh = Y->h; a.yw = Y->w; a.ycs = Y->cstride; a.yco = Y->coff; a.cy = Y->c;
+  a.n = X->n; a.k = cv->k; a.stride = cv->stride; a.pad = cv->pad; a.pwx = c.pwx; a.pwy = c.pwy;
+  a.ws = ws;
+  dim3 grid((unsigned)(a.ncxt * a.ncyg), (unsigned)cv->k, (unsigned)a.nsplit);
+  if (NTY == 2)
+    hipLaunchKernelGGL((wgrad_kernel<2>), grid, dim3(256), lds_bytes, st, a);
+  else
+    hipLaunchKernelGGL((wgrad_kernel<1>), grid, dim3(256), lds_bytes, st, a);
+  BP_CHECK_LAUNCH();
+  return BP_OK;
+}
+
+const WgradFamily& wgrad_family_general() {
+  static const WgradFamily f = {"general", bp_wgrad_plan_of<wgrad_general>, bp_wgrad_run_of<wgrad_general>, false, false};
+  return f;
+}
+
 // One or two channels on one side and many on the other (the k9 stem / head of the CGAN generator): the tap-packed
 // few-channel kernel runs once per 16-channel chunk of the wide side, each chunk reduced into its block of dW.
-static bool wide_side_chunks(const bp_conv* cv, const bp_view* X, const bp_view* Y, bool* on_x) {
-  if (X->c > 16 && Y->c <= 2) *on_x = true;
-  else if (Y->c > 16 && X->c <= 2) *on_x = false;
+bool wide_side(const WgradCall& c, bool* on_x) {
+  if (c.X->c > 16 && c.Y->c <= 2) *on_x = true;
+  else if (c.Y->c > 16 && c.X->c <= 2) *on_x = false;
   else return false;
+  return true;
+}
+
+// chunk c0 of the wide side: its views, and the pointwise operand moved to its channels
+struct Chunk {
+  bp_view sub;
+  WgradCall call;
+  Chunk(const WgradCall& c, bool on_x, int c0, int nc) : sub(on_x ? *c.X : *c.Y), call(c) {
+    sub.c = nc;
+    sub.coff += c0;
+    PW& p = on_x ? call.pwx : call.pwy;
+    if (p.scale) p = PW{p.scale + c0, p.shift + c0, p.slope + c0};
+    (on_x ? call.X : call.Y) = &sub;
+  }
+  Chunk(const Chunk&) = delete;
+};
+
+bool chunked_plan(const WgradCall& c, WgradRow* row) {
+  bool on_x = false;
+  if (!wide_side(c, &on_x)) return false;
   // every chunk size that occurs needs an instantiation: the full 16 channels and the ragged tail (33 = 2 x 16 + 1 has
   // a one-channel tail without one -- such a layer is not chunked at all, rather than refused after two chunks of dW)
-  const int wide = *on_x ? X->c : Y->c;
-  const PW none{nullptr, nullptr, nullptr};
-  for (int c = 16; c > 0; c = (c == 16 ? wide % 16 : 0)) {
-    bp_view sub = *on_x ? *X : *Y;
-    sub.c = c;
-    size_t need = 0;
-    int ns, cxp, cyp;
-    if (bp_wgrad_small(cv, *on_x ? &sub : X, none, *on_x ? Y : &sub, none, nullptr, 0, &need, &ns, &cxp, &cyp, nullptr,
-                       true) != BP_OK)
-      return false;
+  const int wide = on_x ? c.X->c : c.Y->c;
+  for (int nc = 16; nc > 0; nc = (nc == 16 ? wide % 16 : 0)) {
+    const Chunk ch(c, on_x, 0, nc);
+    WgradRow r;
+    if (bp_wgrad_small(ch.call, nullptr, 0, &r, nullptr, true) != BP_OK) return false;
+    if (nc == 16) *row = WgradRow{BP_WG_SMALL_CHUNKED, r.nsplit, r.cxp, r.cyp, r.bytes};
+    else if (r.bytes > row->bytes) row->bytes = r.bytes;
   }
   return true;
 }
 
-static PW pw_offset(const PW& p, int c0) {
-  return p.scale ? PW{p.scale + c0, p.shift + c0, p.slope + c0} : p;
-}
-
-static int wgrad_chunked(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* dst,
-                         float* ws, size_t ws_bytes, size_t* need_out, hipStream_t st, bool dry, bool on_x,
-                         int32_t* plan = nullptr) {
-  const int wide = on_x ? X->c : Y->c;
-  size_t need_max = 0;
+int chunked_run(const WgradCall& c, const WgradRow&, float* dst, void* ws, size_t ws_bytes, hipStream_t st) {
+  bool on_x = false;
+  wide_side(c, &on_x);
+  const int wide = on_x ? c.X->c : c.Y->c;
   for (int c0 = 0; c0 < wide; c0 += 16) {
-    bp_view sub = on_x ? *X : *Y;
-    sub.c = wide - c0 < 16 ? wide - c0 : 16;
-    sub.coff += c0;
-    const bp_view* Xc = on_x ? &sub : X;
-    const bp_view* Yc = on_x ? Y : &sub;
-    const PW px = on_x ? pw_offset(pwx, c0) : pwx, py = on_x ? pwy : pw_offset(pwy, c0);
-    size_t need = 0;
-    int ns, cxp, cyp;
-    const int rc = bp_wgrad_small(cv, Xc, px, Yc, py, ws, ws_bytes, &need, &ns, &cxp, &cyp, st, dry);
+    const Chunk ch(c, on_x, c0, wide - c0 < 16 ? wide - c0 : 16);
+    WgradRow r;
+    int rc = bp_wgrad_small(ch.call, reinterpret_cast<float*>(ws), ws_bytes, &r, st, false);
+    if (rc == BP_OK)
+      rc = wgrad_reduce(reinterpret_cast<const float*>(ws), dst, c.cv->k, ch.call.X->c, ch.call.Y->c, r.cxp, r.cyp,
+                        r.nsplit, st, c.X->c, on_x ? c0 : 0, on_x ? 0 : c0, /*may_defer=*/false);      // (the chunks share one workspace)
     if (rc != BP_OK) return rc;
-    if (need > need_max) need_max = need;
-    if (plan && c0 == 0) { plan[0] = BP_WG_SMALL_CHUNKED; plan[1] = ns; plan[2] = cxp; plan[3] = cyp; }
-    if (!dry) {
-      const int rr = wgrad_reduce(ws, dst, cv->k, Xc->c, Yc->c, cxp, cyp, ns, st, X->c, on_x ? c0 : 0, on_x ? 0 : c0,
-                                  /*may_defer=*/false);      // (the chunks share one workspace)
-      if (rr != BP_OK) return rr;
-    }
   }
-  *need_out = need_max;
   return BP_OK;
 }
 
-// bf16 matrix-core weight gradient (conv_wgrad_bf16.hip) + the same fixed-order reduction; operands may be fp32 or bf16
-size_t bp_wgrad_bf16_workspace(const bp_conv* cv, const bp_view* X, const bp_view* Y) {
-  size_t need = 0;
-  int ns, cxp, cyp;
-  const PW none{nullptr, nullptr, nullptr};
-  return bp_wgrad_bf16(cv, X, none, Y, none, nullptr, 0, &need, &ns, &cxp, &cyp, nullptr, true) == BP_OK ? need : 0;
+const WgradFamily& wgrad_family_chunked() {
+  static const WgradFamily f = {"small_chunked", chunked_plan, chunked_run, true, false};
+  return f;
 }
 
-int bp_wgrad_bf16_run(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* dst,
-                      void* workspace, size_t workspace_bytes, hipStream_t st, int32_t* plan) {
-  size_t need = 0;
-  int ns, cxp, cyp;
-  const int rc = bp_wgrad_bf16(cv, X, pwx, Y, pwy, reinterpret_cast<float*>(workspace), workspace_bytes, &need, &ns,
-                               &cxp, &cyp, st, plan != nullptr);
-  if (rc != BP_OK) return rc;
-  if (plan) { plan[0] = bp_wgrad_bf16_last_family(); plan[1] = ns; plan[2] = cxp; plan[3] = cyp; return BP_OK; }
-  return wgrad_reduce(reinterpret_cast<const float*>(workspace), dst, cv->k, X->c, Y->c, cxp, cyp, ns, st);
-}
+// The two tables are the one place the priority order is written: bp_wgrad_select() walks them for the call, for the
+// plan query and for the workspace query alike.  A new family: write its WgradFamily record next to its kernels, declare
+// its accessor in kernels.hpp, insert it here.
+//
+// fp32.  stem, flat and flat_s2 are kernels of one layer each, disjoint among themselves; they come first because the
+// kernels behind them take their layers too (small the stem's and the head's, tiles the stride-2 k4 layers').  chunked
+// stands before tiles, which accepts its k9 layers whole; thin never sees them (its Y has one channel, its X at most
+// eight).  ws_f32 stands before tiles (both take the 128 <-> 128 k3 layers), enc before small and tiles (both take the
+// k8 stride-4 layer), thin before small (which has instantiations for three of thin's layers), small before tiles (which
+// takes any channel count at its (k, stride)), and general, which takes every k <= 9, last.
+// may_requalify: stem, flat and flat_s2 look at the pointwise operands, ws_f32 at an option.
+using FamilyFn = const WgradFamily& (*)();
+const FamilyFn F32_FAMILIES[] = {bp_wgrad_family_stem,  bp_wgrad_family_flat, bp_wgrad_family_flat_s2, wgrad_family_chunked,
+                                 bp_wgrad_family_ws_f32, bp_wgrad_family_enc,  bp_wgrad_family_thin,    bp_wgrad_family_small,
+                                 bp_wgrad_family_tiles,  wgrad_family_general};
+// bf16 (operands may be fp32 or bf16).  wf, sf and wh are kernels of one layer each, disjoint among themselves; the
+// tiled kernels take their layers too.  ws_bf16 stands before tiled: both take the 128 <-> 128 k3 layers.
+// may_requalify: ws_bf16 looks at an option.  wf, sf and wh refuse a pointwise operand on Y and are NOT marked: the
+// workspace has always been sized for them alone.  bp_conv_backward_weight cannot reach the other branch -- they accept
+// plain convolutions only, whose pointwise operand lands on X -- and a caller of these tables that could would be
+// answered BP_EWORKSPACE where the tiled kernel needs more.
+const FamilyFn BF16_FAMILIES[] = {bp_wgrad_family_bf16_wf, bp_wgrad_family_bf16_sf, bp_wgrad_family_bf16_wh,
+                                  bp_wgrad_family_ws_bf16, bp_wgrad_family_bf16_tiled};
 
-static size_t wgrad_general_workspace(const bp_conv* cv, const bp_view* X, const bp_view* Y);
-
-size_t bp_wgrad_mfma_workspace(const bp_conv* cv, const bp_view* X, const bp_view* Y) {
-  const size_t general = wgrad_general_workspace(cv, X, Y);
-  if (bp_stem_wgrad_ok(cv, X, Y, PW{nullptr, nullptr, nullptr}, nullptr)) {
-    const size_t stem = bp_stem_wgrad_workspace(X);
-    return stem > general ? stem : general;
-  }
-  if (bp_wgrad_flat_ok(cv, X, Y, PW{nullptr, nullptr, nullptr})) {
-    const size_t flat = bp_wgrad_flat_workspace(X);
-    return flat > general ? flat : general;
-  }
-  if (bp_wgrad_flat_s2_ok(cv, X, Y, PW{nullptr, nullptr, nullptr}, PW{nullptr, nullptr, nullptr})) {
-    const size_t flat = bp_wgrad_flat_s2_workspace(Y);
-    return flat > general ? flat : general;
-  }
-  return general;
-}
-
-static size_t wgrad_general_workspace(const bp_conv* cv, const bp_view* X, const bp_view* Y) {
-  size_t need = 0;
-  int ns, cxp, cyp;
-  const PW none{nullptr, nullptr, nullptr};
-  bool on_x = false;
-  if (wide_side_chunks(cv, X, Y, &on_x) &&
-      wgrad_chunked(cv, X, none, Y, none, nullptr, nullptr, 0, &need, nullptr, true, on_x) == BP_OK)
-    return need;
-  int family;
-  if (wgrad_fast(cv, X, none, Y, none, nullptr, 0, &need, &ns, &cxp, &cyp, nullptr, true, &family) == BP_OK) return need;
-  const WgradPlan p = wgrad_plan(cv, X, Y);
-  return p.ok ? p.ws_bytes : 0;
-}
-
-namespace {
-struct SharedTarget {                        // for the duration of one bp_wgrad_mfma call on this thread
-  explicit SharedTarget(bool shared) {
-    static const int t = getenv("BP_WT_SHARED_TARGET") ? atoi(getenv("BP_WT_SHARED_TARGET")) : 448;
-    bp_wgrad_tiles_target(shared ? t : 0);
-  }
-  ~SharedTarget() { bp_wgrad_tiles_target(0); }
-};
 }  // namespace
 
-int bp_wgrad_mfma(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy,
-                  float* dst, void* workspace, size_t workspace_bytes, hipStream_t st, bool shared, int32_t* plan) {
-  // `plan` (bp_conv_backward_weight_plan): the same walk, dry -- {family, nsplit, cxp, cyp} of the kernel it ends at
-  // instead of its launch
-  const SharedTarget guard(shared);
-  const bool dry = plan != nullptr;
-  auto planned = [&](int family, int ns, int cxp, int cyp) {
-    plan[0] = family; plan[1] = ns; plan[2] = cxp; plan[3] = cyp;
-    return BP_OK;
-  };
-  if (bp_stem_wgrad_ok(cv, X, Y, pwy, nullptr))
-    return dry ? planned(BP_WG_STEM, bp_stem_wgrad_grid(X), 0, 0) : bp_stem_wgrad(X, pwx, Y, dst, workspace, workspace_bytes, st);
-  if (bp_wgrad_flat_ok(cv, X, Y, pwy))
-    return dry ? planned(BP_WG_FLAT, bp_wgrad_flat_grid(X, shared), 0, 0)
-               : bp_wgrad_flat(X, pwx, Y, dst, workspace, workspace_bytes, st, shared);
-  if (bp_wgrad_flat_s2_ok(cv, X, Y, pwx, pwy))
-    return dry ? planned(BP_WG_FLAT_S2, bp_wgrad_flat_s2_grid(Y, shared), 0, 0)
-               : bp_wgrad_flat_s2(X, pwx, Y, pwy, dst, workspace, workspace_bytes, st, shared);
-  {
-    bool on_x = false;
-    if (wide_side_chunks(cv, X, Y, &on_x)) {
-      size_t need = 0;
-      return wgrad_chunked(cv, X, pwx, Y, pwy, dst, reinterpret_cast<float*>(workspace), workspace_bytes, &need, st,
-                           dry, on_x, plan);
-    }
+int bp_wgrad_select(bool bf16, const WgradCall& c, WgradSelection* s) {
+  const FamilyFn* table = bf16 ? BF16_FAMILIES : F32_FAMILIES;
+  const size_t count = bf16 ? sizeof(BF16_FAMILIES) / sizeof(FamilyFn) : sizeof(F32_FAMILIES) / sizeof(FamilyFn);
+  *s = WgradSelection{};
+  for (size_t i = 0; i < count; ++i) {
+    const WgradFamily& f = table[i]();
+    WgradRow row;
+    if (!f.plan(c, &row)) continue;
+    if (!s->family) { s->family = &f; s->row = row; }
+    if (row.bytes > s->ws_bytes) s->ws_bytes = row.bytes;
+    if (!f.may_requalify) break;      // (the families behind it: only for the size of the workspace)
   }
-  {
-    size_t need = 0;
-    int ns, cxp, cyp, family;
-    const int rc = wgrad_fast(cv, X, pwx, Y, pwy, reinterpret_cast<float*>(workspace), workspace_bytes, &need,
-                              &ns, &cxp, &cyp, st, dry, &family);
-    if (rc == BP_OK)
-      return dry ? planned(family, ns, cxp, cyp)
-                 : wgrad_reduce(reinterpret_cast<const float*>(workspace), dst, cv->k, X->c, Y->c, cxp, cyp, ns, st);
-    if (rc != BP_EUNSUPPORTED) return rc;
-  }
-  const WgradPlan p = wgrad_plan(cv, X, Y);
-  if (!p.ok) return BP_EUNSUPPORTED;
-  if (dry) return planned(BP_WG_GENERAL, p.nsplit, p.CXP, p.CYP);
-  if (!workspace || workspace_bytes < p.ws_bytes) return BP_EWORKSPACE;
-  WgradArgs a{};
-  a.X = X->ptr; a.xh = X->h; a.xw = X->w; a.xcs = X->cstride; a.xco = X->coff; a.cx = X->c;
-  a.Y = Y->ptr; a.yh = Y->h; a.yw = Y->w; a.ycs = Y->cstride; a.yco = Y->coff; a.cy = Y->c;
-  a.n = X->n; a.k = cv->k; a.stride = cv->stride; a.pad = cv->pad; a.pwx = pwx; a.pwy = pwy;
-  a.ws = reinterpret_cast<float*>(workspace);
-  a.ncxt = p.ncxt; a.ncyg = p.ncyg; a.nsplit = p.nsplit; a.tiles_x = p.tiles_x; a.tiles_y = p.tiles_y;
-  a.IW = p.IW; a.IWq = p.IWq; a.CXP = p.CXP; a.CYP = p.CYP;
-  dim3 grid((unsigned)(p.ncxt * p.ncyg), (unsigned)cv->k, (unsigned)p.nsplit);
-  if (p.NTY == 2)
-    hipLaunchKernelGGL((wgrad_kernel<2>), grid, dim3(256), p.lds_bytes, st, a);
-  else
-    hipLaunchKernelGGL((wgrad_kernel<1>), grid, dim3(256), p.lds_bytes, st, a);
-  BP_CHECK_LAUNCH();
-  // (the same reduction as every other kernel's partial sums: it fills in the position of this block inside dW --
-  //  a WreduceArgs built here with cx_total left at 0 wrote every produced channel onto the first one's row)
-  return wgrad_reduce(a.ws, dst, cv->k, X->c, Y->c, p.CXP, p.CYP, p.nsplit, st);
+  return s->family ? BP_OK : BP_EUNSUPPORTED;
+}
+
+int bp_wgrad_run(const WgradSelection& s, const WgradCall& c, float* dst, void* workspace, size_t workspace_bytes,
+                 hipStream_t st) {
+  const int rc = s.family->run(c, s.row, dst, workspace, workspace_bytes, st);
+  if (rc != BP_OK || s.family->reduces_itself) return rc;
+  return wgrad_reduce(reinterpret_cast<const float*>(workspace), dst, c.cv->k, c.X->c, c.Y->c, s.row.cxp, s.row.cyp,
+                      s.row.nsplit, st);
 }

@@ -453,14 +453,15 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16_kernel(WbArgs a) {
 }
 
 template <int KHB, int KW, int S, int NTX, int NTY, int WX, int WY, int BH, bool WT = false>
-int wb_launch(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* ws,
-              size_t ws_bytes, size_t* need, int* nsplit_out, int* cxp, int* cyp, hipStream_t st, bool dry) {
+int wb_launch(const WgradCall& c, float* ws, size_t ws_bytes, WgradRow* row, hipStream_t st, bool dry) {
   using Cfg = WbCfg<KHB, KW, S, NTX, NTY, WX, WY, BH>;
   static_assert(Cfg::LDS <= 80 * 1024, "LDS budget: two workgroups per CU");
+  const bp_conv* cv = c.cv;
+  const bp_view *X = c.X, *Y = c.Y;
   WbArgs a{};
   a.X = X->ptr; a.xh = X->h; a.xw = X->w; a.xcs = X->cstride; a.xco = X->coff; a.cx = X->c; a.x_bf16 = X->dtype == BP_BF16;
   a.Y = Y->ptr; a.yh = Y->h; a.yw = Y->w; a.ycs = Y->cstride; a.yco = Y->coff; a.cy = Y->c; a.y_bf16 = Y->dtype == BP_BF16;
-  a.n = X->n; a.k = cv->k; a.pad = cv->pad; a.pwx = pwx; a.pwy = pwy; a.ws = ws;
+  a.n = X->n; a.k = cv->k; a.pad = cv->pad; a.pwx = c.pwx; a.pwy = c.pwy; a.ws = ws;
   a.ncxb = bp_ceil_div(X->c, Cfg::CXC);
   const int ncyb = bp_ceil_div(Y->c, Cfg::CYC);
   a.CXP = a.ncxb * Cfg::CXC;
@@ -476,10 +477,9 @@ int wb_launch(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view*
   if (ns < 1) ns = 1;
   if (ns > 65535) ns = 65535;
   a.nsplit = (int)ns;
-  *need = (size_t)a.nsplit * cv->k * cv->k * a.CYP * a.CXP * sizeof(float);
-  *nsplit_out = a.nsplit; *cxp = a.CXP; *cyp = a.CYP;
+  *row = WgradRow{BP_WG_BF16_TILED, a.nsplit, a.CXP, a.CYP, (size_t)a.nsplit * cv->k * cv->k * a.CYP * a.CXP * sizeof(float)};
   if (dry) return BP_OK;
-  if (!ws || ws_bytes < *need) return BP_EWORKSPACE;
+  if (!ws || ws_bytes < row->bytes) return BP_EWORKSPACE;
   dim3 grid((unsigned)(a.ncxb * ncyb), (unsigned)kyg, (unsigned)a.nsplit);
   const bool xb = a.x_bf16, yb = a.y_bf16;
 #define BP_WB(XB_, YB_)                                                                                             \
@@ -664,8 +664,18 @@ __global__ __launch_bounds__(256, 2) void wgrad_flatb_k7_kernel(WfArgs a) {
   }
 }
 
+// Every bf16 family: 16-byte loads of 8 channels need 16-byte aligned pixel rows; ragged channel counts take the scalar
+// path.  (conv_wgrad_ws_bf16.hip asks more of its views.)
+bool wb_view_ok(const bp_view* v) {
+  const int esz = v->dtype == BP_BF16 ? 2 : 4;
+  if (reinterpret_cast<uintptr_t>(v->ptr) % 16) return false;
+  if (v->c % 8 == 0) return (v->cstride * esz) % 16 == 0 && (v->coff * esz) % 16 == 0;
+  return true;
+}
+
 static bool wf_ok(const bp_conv* cv, const bp_view* X, const bp_view* Y, const PW& pwy) {
   static const bool off = getenv("BP_BF16_NOFLATW") != nullptr;
+  if (!wb_view_ok(X) || !wb_view_ok(Y)) return false;
   if (off || cv->transposed || cv->k != WF_K || cv->stride != 1 || cv->pad != 3 || X->c != 16 || Y->c != 8) return false;
   if (X->dtype != BP_BF16 || pwy.scale) return false;
   if (X->h != Y->h || X->w != Y->w || X->n != Y->n) return false;
@@ -675,19 +685,19 @@ static bool wf_ok(const bp_conv* cv, const bp_view* X, const bp_view* Y, const P
   return true;
 }
 
-static int wf_launch(const bp_view* X, const PW& pwx, const bp_view* Y, float* ws, size_t ws_bytes, size_t* need,
-                     int* nsplit_out, int* cxp, int* cyp, hipStream_t st, bool dry) {
+static int wgrad_wf(const WgradCall& c, float* ws, size_t ws_bytes, WgradRow* row, hipStream_t st, bool dry) {
+  const bp_view *X = c.X, *Y = c.Y;
+  if (!wf_ok(c.cv, X, Y, c.pwy)) return BP_EUNSUPPORTED;
   WfArgs a{};
   a.X = reinterpret_cast<const u16*>(X->ptr); a.h = X->h; a.w = X->w; a.xcs = X->cstride; a.xco = X->coff;
   a.Y = Y->ptr; a.ycs = Y->cstride; a.yco = Y->coff;
-  a.n = X->n; a.pwx = pwx; a.ws = ws;
+  a.n = X->n; a.pwx = c.pwx; a.ws = ws;
   a.tiles_x = bp_ceil_div(X->w, WF_TW); a.tiles_y = bp_ceil_div(X->h, WF_TH);
   const int64_t ntiles = (int64_t)a.tiles_x * a.tiles_y * a.n;
   const int ns = (int)(ntiles < 512 ? ntiles : 512);                 // two persistent workgroups per CU
-  *need = (size_t)ns * WF_K * WF_K * 8 * 16 * sizeof(float);
-  *nsplit_out = ns; *cxp = 16; *cyp = 8;
+  *row = WgradRow{BP_WG_BF16_WF, ns, 16, 8, (size_t)ns * WF_K * WF_K * 8 * 16 * sizeof(float)};
   if (dry) return BP_OK;
-  if (!ws || ws_bytes < *need) return BP_EWORKSPACE;
+  if (!ws || ws_bytes < row->bytes) return BP_EWORKSPACE;
   static const hipError_t optin = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_flatb_k7_kernel<false>),
                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)WF_LDS);
   static const hipError_t optin_b = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_flatb_k7_kernel<true>),
@@ -839,6 +849,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_flatb_stem_kernel(WsfArgs a) {
 
 static bool sf_ok(const bp_conv* cv, const bp_view* X, const bp_view* Y, const PW& pwy) {
   static const bool off = getenv("BP_BF16_NOFLATW") != nullptr;
+  if (!wb_view_ok(X) || !wb_view_ok(Y)) return false;
   if (off || cv->transposed || cv->k != SF_K || cv->stride != 1 || cv->pad != 2 || X->c > 4 || Y->c != 16) return false;
   if (X->dtype != BP_F32 || Y->dtype != BP_BF16 || pwy.scale) return false;
   if (X->h != Y->h || X->w != Y->w || X->n != Y->n) return false;
@@ -847,19 +858,19 @@ static bool sf_ok(const bp_conv* cv, const bp_view* X, const bp_view* Y, const P
   return true;
 }
 
-static int sf_launch(const bp_view* X, const PW& pwx, const bp_view* Y, float* ws, size_t ws_bytes, size_t* need,
-                     int* nsplit_out, int* cxp, int* cyp, hipStream_t st, bool dry) {
+static int wgrad_sf(const WgradCall& c, float* ws, size_t ws_bytes, WgradRow* row, hipStream_t st, bool dry) {
+  const bp_view *X = c.X, *Y = c.Y;
+  if (!sf_ok(c.cv, X, Y, c.pwy)) return BP_EUNSUPPORTED;
   WsfArgs a{};
   a.X = reinterpret_cast<const float*>(X->ptr); a.h = X->h; a.w = X->w; a.xcs = X->cstride; a.xco = X->coff; a.cx = X->c;
   a.Y = reinterpret_cast<const u16*>(Y->ptr); a.ycs = Y->cstride; a.yco = Y->coff;
-  a.n = X->n; a.pwx = pwx; a.ws = ws;
+  a.n = X->n; a.pwx = c.pwx; a.ws = ws;
   a.tiles_x = bp_ceil_div(X->w, SF_TW); a.tiles_y = bp_ceil_div(X->h, SF_TH);
   const int64_t ntiles = (int64_t)a.tiles_x * a.tiles_y * a.n;
   const int ns = (int)(ntiles < 512 ? ntiles : 512);                 // two persistent workgroups per CU
-  *need = (size_t)ns * SF_K * SF_K * 16 * 4 * sizeof(float);
-  *nsplit_out = ns; *cxp = 4; *cyp = 16;
+  *row = WgradRow{BP_WG_BF16_SF, ns, 4, 16, (size_t)ns * SF_K * SF_K * 16 * 4 * sizeof(float)};
   if (dry) return BP_OK;
-  if (!ws || ws_bytes < *need) return BP_EWORKSPACE;
+  if (!ws || ws_bytes < row->bytes) return BP_EWORKSPACE;
   static const hipError_t optin = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_flatb_stem_kernel),
                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)SF_LDS);
   if (optin != hipSuccess) return BP_ELAUNCH;
@@ -1013,6 +1024,7 @@ __global__ __launch_bounds__(256, 4) void wgrad_head_kernel(WhArgs a) {
 
 static bool wh_ok(const bp_conv* cv, const bp_view* X, const bp_view* Y, const PW& pwy) {
   static const bool off = getenv("BP_BF16_NOHEADW") != nullptr;
+  if (!wb_view_ok(X) || !wb_view_ok(Y)) return false;
   if (off || cv->transposed || cv->k != WH_K || cv->stride != 1 || cv->pad != 2 || X->c != WH_C || Y->c != 1) return false;
   if (X->dtype != BP_BF16 || Y->dtype != BP_F32 || pwy.scale) return false;
   if (X->h != Y->h || X->w != Y->w || X->n != Y->n) return false;
@@ -1020,19 +1032,19 @@ static bool wh_ok(const bp_conv* cv, const bp_view* X, const bp_view* Y, const P
   return true;
 }
 
-static int wh_launch(const bp_view* X, const PW& pwx, const bp_view* Y, float* ws, size_t ws_bytes, size_t* need,
-                     int* nsplit_out, int* cxp, int* cyp, hipStream_t st, bool dry) {
+static int wgrad_wh(const WgradCall& c, float* ws, size_t ws_bytes, WgradRow* row, hipStream_t st, bool dry) {
+  const bp_view *X = c.X, *Y = c.Y;
+  if (!wh_ok(c.cv, X, Y, c.pwy)) return BP_EUNSUPPORTED;
   WhArgs a{};
   a.X = reinterpret_cast<const u16*>(X->ptr); a.h = X->h; a.w = X->w; a.xcs = X->cstride; a.xco = X->coff;
   a.Y = reinterpret_cast<const float*>(Y->ptr); a.ycs = Y->cstride; a.yco = Y->coff;
-  a.n = X->n; a.pwx = pwx; a.ws = ws;
+  a.n = X->n; a.pwx = c.pwx; a.ws = ws;
   a.tiles_x = bp_ceil_div(X->w, WH_TW); a.tiles_y = bp_ceil_div(X->h, WH_TH);
   const int64_t ntiles = (int64_t)a.tiles_x * a.tiles_y * a.n;
   const int ns = (int)(ntiles < 1024 ? ntiles : 1024);               // four persistent workgroups per CU (27 KB of LDS each)
-  *need = (size_t)ns * WH_K * WH_K * WH_C * sizeof(float);
-  *nsplit_out = ns; *cxp = WH_C; *cyp = 1;
+  *row = WgradRow{BP_WG_BF16_WH, ns, WH_C, 1, (size_t)ns * WH_K * WH_K * WH_C * sizeof(float)};
   if (dry) return BP_OK;
-  if (!ws || ws_bytes < *need) return BP_EWORKSPACE;
+  if (!ws || ws_bytes < row->bytes) return BP_EWORKSPACE;
   static const hipError_t optin = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_head_kernel),
                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)WH_LDS);
   if (optin != hipSuccess) return BP_ELAUNCH;
@@ -1041,44 +1053,12 @@ static int wh_launch(const bp_view* X, const PW& pwx, const bp_view* Y, float* w
   return BP_OK;
 }
 
-// 16-byte loads of 8 channels need 16-byte aligned pixel rows; ragged channel counts take the scalar path
-bool wb_view_ok(const bp_view* v) {
-  const int esz = v->dtype == BP_BF16 ? 2 : 4;
-  if (reinterpret_cast<uintptr_t>(v->ptr) % 16) return false;
-  if (v->c % 8 == 0) return (v->cstride * esz) % 16 == 0 && (v->coff * esz) % 16 == 0;
-  return true;
-}
-
-}  // namespace
-
-static thread_local int t_wb_family = BP_WG_BF16_TILED;
-int bp_wgrad_bf16_last_family() { return t_wb_family; }
-
-// Same contract as bp_wgrad_tiles (conv_wgrad_tiles.hip): partial sums to ws, BP_EUNSUPPORTED if no variant fits.
-int bp_wgrad_bf16(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* ws,
-                  size_t ws_bytes, size_t* need, int* nsplit, int* cxp, int* cyp, hipStream_t st, bool dry) {
+// The tiled kernels: partial sums to ws, BP_EUNSUPPORTED if no variant fits.
+int wgrad_tiled(const WgradCall& c, float* ws, size_t ws_bytes, WgradRow* row, hipStream_t st, bool dry) {
+  const bp_view *X = c.X, *Y = c.Y;
   if (!wb_view_ok(X) || !wb_view_ok(Y)) return BP_EUNSUPPORTED;
-  t_wb_family = BP_WG_BF16_WF;
-  if (wf_ok(cv, X, Y, pwy)) return wf_launch(X, pwx, Y, ws, ws_bytes, need, nsplit, cxp, cyp, st, dry);
-  t_wb_family = BP_WG_BF16_SF;
-  if (sf_ok(cv, X, Y, pwy)) return sf_launch(X, pwx, Y, ws, ws_bytes, need, nsplit, cxp, cyp, st, dry);
-  t_wb_family = BP_WG_BF16_WH;
-  if (wh_ok(cv, X, Y, pwy)) return wh_launch(X, pwx, Y, ws, ws_bytes, need, nsplit, cxp, cyp, st, dry);
-  t_wb_family = BP_WG_WS_BF16;
-  {      // the output-stationary kernel of the 128 <-> 128 k3 trunk layers (conv_wgrad_ws_bf16.hip)
-    const int rc = bp_wgrad_ws_bf16(cv, X, pwx, Y, pwy, ws, ws_bytes, need, nsplit, cxp, cyp, st, dry);
-    if (rc == BP_OK && dry) {      // (size the workspace for either kernel: bp_set_option may switch later)
-      size_t need2 = 0;
-      int ns2, cx2, cy2;
-      if (wb_launch<3, 3, 1, 2, 2, 2, 2, 4>(cv, X, pwx, Y, pwy, ws, ws_bytes, &need2, &ns2, &cx2, &cy2, st, true) == BP_OK &&
-          need2 > *need)
-        *need = need2;
-    }
-    if (rc != BP_EUNSUPPORTED) return rc;
-  }
-  t_wb_family = BP_WG_BF16_TILED;
-  const int k = cv->k, s = cv->stride, cx = X->c, cy = Y->c;
-#define BP_WB_(...) return wb_launch<__VA_ARGS__>(cv, X, pwx, Y, pwy, ws, ws_bytes, need, nsplit, cxp, cyp, st, dry)
+  const int k = c.cv->k, s = c.cv->stride, cx = X->c, cy = Y->c;
+#define BP_WB_(...) return wb_launch<__VA_ARGS__>(c, ws, ws_bytes, row, st, dry)
   if (k == 3 && s == 1) {
     // 64 x 64 channel block, 4 x 32 pixel tiles (8-row tiles need 19 staging registers per thread on top of the 144
     // accumulators: 128 bytes of scratch, 118 -> 167 us)
@@ -1102,5 +1082,24 @@ int bp_wgrad_bf16(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_v
   if (k == 7 && s == 1 && cx <= 16 && cy <= 16) BP_WB_(4, 7, 1, 1, 1, 1, 1, 8);
 #undef BP_WB_
   return BP_EUNSUPPORTED;
+}
+
+}  // namespace
+
+const WgradFamily& bp_wgrad_family_bf16_wf() {
+  static const WgradFamily f = {"bf16_wf", bp_wgrad_plan_of<wgrad_wf>, bp_wgrad_run_of<wgrad_wf>, false, false};
+  return f;
+}
+const WgradFamily& bp_wgrad_family_bf16_sf() {
+  static const WgradFamily f = {"bf16_sf", bp_wgrad_plan_of<wgrad_sf>, bp_wgrad_run_of<wgrad_sf>, false, false};
+  return f;
+}
+const WgradFamily& bp_wgrad_family_bf16_wh() {
+  static const WgradFamily f = {"bf16_wh", bp_wgrad_plan_of<wgrad_wh>, bp_wgrad_run_of<wgrad_wh>, false, false};
+  return f;
+}
+const WgradFamily& bp_wgrad_family_bf16_tiled() {
+  static const WgradFamily f = {"bf16_tiled", bp_wgrad_plan_of<wgrad_tiled>, bp_wgrad_run_of<wgrad_tiled>, false, false};
+  return f;
 }
 

@@ -204,31 +204,33 @@ constexpr int FOLD_ROWS = 32;
 
 int flat_tiles(const bp_view* X) { return bp_ceil_div(X->w, TW) * bp_ceil_div(X->h, TH) * X->n; }
 
-}  // namespace
-
-bool bp_wgrad_flat_ok(const bp_conv* cv, const bp_view* X, const bp_view* Y, const PW& pwy) {
-  static const bool off = getenv("BP_NOWFLAT") != nullptr;
-  return !off && !cv->transposed && cv->k == K && cv->stride == 1 && cv->pad == PAD && cv->cin == CI && cv->cout == CO &&
-         X->c == CI && Y->c == CO && X->h == Y->h && X->w == Y->w && pwy.scale == nullptr && X->dtype == BP_F32 &&
-         Y->dtype == BP_F32 && bp_view_vec4(X) && bp_view_vec4(Y);
-}
-
-int bp_wgrad_flat_grid(const bp_view* X, bool shared) { return shared_grid(flat_grid(flat_tiles(X)), shared); }
-
-size_t bp_wgrad_flat_workspace(const bp_view* X) {
-  const int grid = flat_grid(flat_tiles(X));
+// the row of a self-reducing kernel: `grid` partial images of `part` floats (the shared launch has fewer: the workspace
+// is sized for the un-shared one either way) and their first fold in double
+WgradRow self_reducing_row(int id, int grid, bool shared, int part) {
   const int chunks = bp_ceil_div(grid, FOLD_ROWS);
-  return (size_t)grid * PART * sizeof(float) + (size_t)chunks * PART * sizeof(double);
+  return WgradRow{id, shared_grid(grid, shared), 0, 0, (size_t)grid * part * sizeof(float) + (size_t)chunks * part * sizeof(double)};
 }
 
-int bp_wgrad_flat(const bp_view* X, const PW& pwx, const bp_view* Y, float* dst, void* workspace, size_t workspace_bytes,
-                  hipStream_t st, bool shared) {
-  if (!workspace || workspace_bytes < bp_wgrad_flat_workspace(X)) return BP_EWORKSPACE;
+bool flat_plan(const WgradCall& c, WgradRow* row) {
+  static const bool off = getenv("BP_NOWFLAT") != nullptr;
+  const bp_conv* cv = c.cv;
+  const bp_view *X = c.X, *Y = c.Y;
+  if (off || cv->transposed || cv->k != K || cv->stride != 1 || cv->pad != PAD || cv->cin != CI || cv->cout != CO ||
+      X->c != CI || Y->c != CO || X->h != Y->h || X->w != Y->w || c.pwy.scale != nullptr || X->dtype != BP_F32 ||
+      Y->dtype != BP_F32 || !bp_view_vec4(X) || !bp_view_vec4(Y))
+    return false;
+  *row = self_reducing_row(BP_WG_FLAT, flat_grid(flat_tiles(X)), c.shared, PART);
+  return true;
+}
+
+int flat_run(const WgradCall& c, const WgradRow& row, float* dst, void* workspace, size_t workspace_bytes, hipStream_t st) {
+  const bp_view *X = c.X, *Y = c.Y;
+  if (!workspace || workspace_bytes < row.bytes) return BP_EWORKSPACE;
   FlatArgs a{};
   a.x = X->ptr; a.h = X->h; a.w = X->w; a.x_cs = X->cstride; a.x_co = X->coff;
-  a.dy = Y->ptr; a.dy_cs = Y->cstride; a.dy_co = Y->coff; a.pw = pwx; a.n = X->n;
+  a.dy = Y->ptr; a.dy_cs = Y->cstride; a.dy_co = Y->coff; a.pw = c.pwx; a.n = X->n;
   a.tiles_x = bp_ceil_div(X->w, TW); a.tiles_y = bp_ceil_div(X->h, TH);
-  const int grid = shared_grid(flat_grid(flat_tiles(X)), shared);
+  const int grid = row.nsplit;
   const int chunks = bp_ceil_div(grid, FOLD_ROWS);
   a.partial = reinterpret_cast<float*>(workspace);
   double* part2 = reinterpret_cast<double*>(a.partial + (size_t)grid * PART);
@@ -241,6 +243,14 @@ int bp_wgrad_flat(const bp_view* X, const PW& pwx, const bp_view* Y, float* dst,
                      chunks, 0, (double*)nullptr, dst);
   BP_CHECK_LAUNCH();
   return BP_OK;
+}
+
+}  // namespace
+
+// (may_requalify: the predicate looks at the pointwise operand of Y, which a workspace query does not pass)
+const WgradFamily& bp_wgrad_family_flat() {
+  static const WgradFamily f = {"flat", flat_plan, flat_run, true, true};
+  return f;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -464,40 +474,37 @@ int grid_of(int ntiles) {
 int tiles_of(const bp_view* S) { return bp_ceil_div(S->w, SW) * bp_ceil_div(S->h, SH) * S->n; }
 
 }  // namespace s2
-}  // namespace
 
 // X = the full-resolution side, Y = the half-resolution side (conv_wgrad.hip's convention for both directions)
-bool bp_wgrad_flat_s2_ok(const bp_conv* cv, const bp_view* X, const bp_view* Y, const PW& pwx, const PW& pwy) {
+bool flat_s2_plan(const WgradCall& c, WgradRow* row) {
   static const bool off = getenv("BP_NOWFLAT") != nullptr || getenv("BP_NOWFLAT_S2") != nullptr;
-  return !off && cv->k == 4 && cv->stride == 2 && cv->pad == 1 && X->c == s2::CB && Y->c == s2::CS &&
-         X->h == 2 * Y->h && X->w == 2 * Y->w && X->n == Y->n && !(pwx.scale && pwy.scale) && X->dtype == BP_F32 &&
-         Y->dtype == BP_F32 && bp_view_vec4(X) && bp_view_vec4(Y);
+  const bp_conv* cv = c.cv;
+  const bp_view *X = c.X, *Y = c.Y;
+  if (off || cv->k != 4 || cv->stride != 2 || cv->pad != 1 || X->c != s2::CB || Y->c != s2::CS || X->h != 2 * Y->h ||
+      X->w != 2 * Y->w || X->n != Y->n || (c.pwx.scale && c.pwy.scale) || X->dtype != BP_F32 || Y->dtype != BP_F32 ||
+      !bp_view_vec4(X) || !bp_view_vec4(Y))
+    return false;
+  *row = self_reducing_row(BP_WG_FLAT_S2, s2::grid_of(s2::tiles_of(Y)), c.shared, s2::PART);
+  return true;
 }
 
-int bp_wgrad_flat_s2_grid(const bp_view* Y, bool shared) { return shared_grid(s2::grid_of(s2::tiles_of(Y)), shared); }
-
-size_t bp_wgrad_flat_s2_workspace(const bp_view* Y) {
-  const int grid = s2::grid_of(s2::tiles_of(Y));
-  const int chunks = bp_ceil_div(grid, FOLD_ROWS);
-  return (size_t)grid * s2::PART * sizeof(float) + (size_t)chunks * s2::PART * sizeof(double);
-}
-
-int bp_wgrad_flat_s2(const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* dst, void* workspace,
-                     size_t workspace_bytes, hipStream_t st, bool shared) {
-  if (!workspace || workspace_bytes < bp_wgrad_flat_s2_workspace(Y)) return BP_EWORKSPACE;
+int flat_s2_run(const WgradCall& c, const WgradRow& row, float* dst, void* workspace, size_t workspace_bytes,
+                hipStream_t st) {
+  const bp_view *X = c.X, *Y = c.Y;
+  if (!workspace || workspace_bytes < row.bytes) return BP_EWORKSPACE;
   s2::Args a{};
   a.b = X->ptr; a.bh = X->h; a.bw = X->w; a.b_cs = X->cstride; a.b_co = X->coff;
   a.s = Y->ptr; a.sh = Y->h; a.sw = Y->w; a.s_cs = Y->cstride; a.s_co = Y->coff;
   a.n = X->n; a.tiles_x = bp_ceil_div(Y->w, s2::SW); a.tiles_y = bp_ceil_div(Y->h, s2::SH);
-  const int grid = shared_grid(s2::grid_of(s2::tiles_of(Y)), shared);
+  const int grid = row.nsplit;
   const int chunks = bp_ceil_div(grid, FOLD_ROWS);
   a.partial = reinterpret_cast<float*>(workspace);
   double* part2 = reinterpret_cast<double*>(a.partial + (size_t)grid * s2::PART);
-  if (pwy.scale) {
-    a.pw = pwy;
+  if (c.pwy.scale) {
+    a.pw = c.pwy;
     hipLaunchKernelGGL((s2::wgrad_flat_s2_kernel<true>), dim3(grid), dim3(256), 0, st, a);
   } else {
-    a.pw = pwx;
+    a.pw = c.pwx;
     hipLaunchKernelGGL((s2::wgrad_flat_s2_kernel<false>), dim3(grid), dim3(256), 0, st, a);
   }
   BP_CHECK_LAUNCH();
@@ -508,4 +515,12 @@ int bp_wgrad_flat_s2(const bp_view* X, const PW& pwx, const bp_view* Y, const PW
                      chunks, 0, (double*)nullptr, dst);
   BP_CHECK_LAUNCH();
   return BP_OK;
+}
+
+}  // namespace
+
+// (may_requalify: the predicate looks at both pointwise operands, and a workspace query passes none)
+const WgradFamily& bp_wgrad_family_flat_s2() {
+  static const WgradFamily f = {"flat_s2", flat_s2_plan, flat_s2_run, true, true};
+  return f;
 }

@@ -283,24 +283,23 @@ __global__ __launch_bounds__(256) void wgrad_small_kernel(WsArgs a) {
 }
 
 template <int K, int S, int CXS, int CYS, int BH>
-int launch(const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, int pad, float* ws, size_t ws_bytes,
-           size_t* need, int* nsplit, int* cxp, int* cyp, hipStream_t st, bool dry) {
+int launch(const WgradCall& c, float* ws, size_t ws_bytes, WgradRow* row, hipStream_t st, bool dry) {
+  const bp_view *X = c.X, *Y = c.Y;
   using C = WsCfg<K, S, CXS, CYS, BH>;
   static_assert(C::LDS <= 64 * 1024, "LDS budget");
   WsArgs a{};
   a.X = X->ptr; a.xh = X->h; a.xw = X->w; a.xcs = X->cstride; a.xco = X->coff; a.cx = X->c;
   a.Y = Y->ptr; a.yh = Y->h; a.yw = Y->w; a.ycs = Y->cstride; a.yco = Y->coff; a.cy = Y->c;
-  a.n = X->n; a.pad = pad; a.pwx = pwx; a.pwy = pwy; a.ws = ws;
+  a.n = X->n; a.pad = c.cv->pad; a.pwx = c.pwx; a.pwy = c.pwy; a.ws = ws;
   a.tiles_x = bp_ceil_div(Y->w, 32);
   a.tiles_y = bp_ceil_div(Y->h, BH);
   int64_t ntiles = (int64_t)Y->n * a.tiles_x * a.tiles_y;
   static const int cap = getenv("BP_WS_NSPLIT") ? atoi(getenv("BP_WS_NSPLIT")) : 1024;
   int64_t ns = ntiles < cap ? ntiles : cap;          // ~4 workgroups per CU
   a.nsplit = (int)ns;
-  *need = (size_t)a.nsplit * K * K * CYS * CXS * sizeof(float);
-  *nsplit = a.nsplit; *cxp = CXS; *cyp = CYS;
+  *row = WgradRow{BP_WG_SMALL, a.nsplit, CXS, CYS, (size_t)a.nsplit * K * K * CYS * CXS * sizeof(float)};
   if (dry) return BP_OK;
-  if (!ws || ws_bytes < *need) return BP_EWORKSPACE;
+  if (!ws || ws_bytes < row->bytes) return BP_EWORKSPACE;
   a.xvec = (X->cstride % 4 == 0 && X->coff % 4 == 0 && reinterpret_cast<uintptr_t>(X->ptr) % 16 == 0) ? 1 : 0;
   a.yvec = (Y->cstride % 4 == 0 && Y->coff % 4 == 0 && reinterpret_cast<uintptr_t>(Y->ptr) % 16 == 0) ? 1 : 0;
   hipLaunchKernelGGL((wgrad_small_kernel<K, S, CXS, CYS, BH>), dim3((unsigned)a.nsplit), dim3(256), C::LDS, st, a);
@@ -314,13 +313,14 @@ int pow2_at_least(int c) { return c <= 1 ? 1 : (c <= 2 ? 2 : (c <= 4 ? 4 : (c <=
 
 // BP_EUNSUPPORTED unless both channel counts are <= 16, at least one is < 16 and (k, stride, padded
 // channel counts) has an instantiation below.
-int bp_wgrad_small(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* ws,
-                   size_t ws_bytes, size_t* need, int* nsplit, int* cxp, int* cyp, hipStream_t st, bool dry) {
+int bp_wgrad_small(const WgradCall& c, float* ws, size_t ws_bytes, WgradRow* row, hipStream_t st, bool dry) {
+  const bp_conv* cv = c.cv;
+  const bp_view *X = c.X, *Y = c.Y;
   if (X->c > 16 || Y->c > 16 || (X->c == 16 && Y->c == 16)) return BP_EUNSUPPORTED;
   const int cxs = pow2_at_least(X->c), cys = pow2_at_least(Y->c);
 #define BP_WS(K_, S_, CX_, CY_, BH_) \
   if (cv->k == K_ && cv->stride == S_ && cxs == CX_ && cys == CY_) \
-    return launch<K_, S_, CX_, CY_, BH_>(X, pwx, Y, pwy, cv->pad, ws, ws_bytes, need, nsplit, cxp, cyp, st, dry)
+    return launch<K_, S_, CX_, CY_, BH_>(c, ws, ws_bytes, row, st, dry)
   BP_WS(7, 1, 16, 8, 8);
   BP_WS(5, 1, 4, 16, 8);
   BP_WS(5, 1, 8, 1, 16);
@@ -333,7 +333,7 @@ int bp_wgrad_small(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_
   BP_WS(5, 1, 8, 8, 8);
   BP_WS(5, 1, 1, 1, 16);
   BP_WS(7, 1, 1, 1, 16);
-  // k9 stem / head of the CGAN generator, per 16-channel chunk of the wide side (conv_wgrad.hip: wide_side_chunks)
+  // k9 stem / head of the CGAN generator, per 16-channel chunk of the wide side (conv_wgrad.hip: the chunked family)
   BP_WS(9, 1, 2, 16, 8);
   BP_WS(9, 1, 1, 16, 8);
   BP_WS(9, 1, 16, 1, 8);
@@ -346,4 +346,9 @@ int bp_wgrad_small(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_
   BP_WS(8, 4, 1, 1, 8);
 #undef BP_WS
   return BP_EUNSUPPORTED;
+}
+
+const WgradFamily& bp_wgrad_family_small() {
+  static const WgradFamily f = {"small", bp_wgrad_plan_of<bp_wgrad_small>, bp_wgrad_run_of<bp_wgrad_small>, false, false};
+  return f;
 }

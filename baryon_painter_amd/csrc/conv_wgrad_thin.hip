@@ -299,8 +299,7 @@ __global__ __launch_bounds__(256) void wgrad_c1_kernel(ThinArgs a) {
 }
 
 template <int K, int CXS, int BH>
-int launch_cy1(const ThinArgs& a0, float* ws, size_t ws_bytes, size_t* need, int* nsplit, int* cxp, int* cyp,
-               hipStream_t st, bool dry) {
+int launch_cy1(const ThinArgs& a0, float* ws, size_t ws_bytes, WgradRow* row, hipStream_t st, bool dry) {
   using C = Cy1Cfg<K, CXS, BH>;
   static_assert(C::LDS <= 64 * 1024, "LDS budget");
   ThinArgs a = a0;
@@ -309,10 +308,9 @@ int launch_cy1(const ThinArgs& a0, float* ws, size_t ws_bytes, size_t* need, int
   const int64_t ntiles = (int64_t)a.n * a.tiles_x * a.tiles_y;
   static const int cap = getenv("BP_THIN_NSPLIT") ? atoi(getenv("BP_THIN_NSPLIT")) : 1280;     // five workgroups per CU
   a.nsplit = (int)(ntiles < cap ? ntiles : cap);
-  *need = (size_t)a.nsplit * K * K * CXS * sizeof(float);
-  *nsplit = a.nsplit; *cxp = CXS; *cyp = 1;
+  *row = WgradRow{BP_WG_THIN_CY1, a.nsplit, CXS, 1, (size_t)a.nsplit * K * K * CXS * sizeof(float)};
   if (dry) return BP_OK;
-  if (!ws || ws_bytes < *need) return BP_EWORKSPACE;
+  if (!ws || ws_bytes < row->bytes) return BP_EWORKSPACE;
   a.ws = ws;
   hipLaunchKernelGGL((wgrad_cy1_kernel<K, CXS, BH>), dim3((unsigned)a.nsplit), dim3(256), C::LDS, st, a);
   BP_CHECK_LAUNCH();
@@ -320,8 +318,7 @@ int launch_cy1(const ThinArgs& a0, float* ws, size_t ws_bytes, size_t* need, int
 }
 
 template <int K>
-int launch_c1(const ThinArgs& a0, float* ws, size_t ws_bytes, size_t* need, int* nsplit, int* cxp, int* cyp,
-              hipStream_t st, bool dry) {
+int launch_c1(const ThinArgs& a0, float* ws, size_t ws_bytes, WgradRow* row, hipStream_t st, bool dry) {
   ThinArgs a = a0;
   a.qpr = bp_ceil_div(a.yw, 4);
   a.nbands = bp_ceil_div(a.yh, C1_BR);
@@ -329,33 +326,38 @@ int launch_c1(const ThinArgs& a0, float* ws, size_t ws_bytes, size_t* need, int*
   const int64_t nblk = (a.total + 255) / 256;
   if (nblk > 65535) return BP_EUNSUPPORTED;       // (the reduction's split count)
   a.nsplit = (int)nblk;
-  *need = (size_t)a.nsplit * K * K * sizeof(float);
-  *nsplit = a.nsplit; *cxp = 1; *cyp = 1;
+  *row = WgradRow{BP_WG_THIN_C1, a.nsplit, 1, 1, (size_t)a.nsplit * K * K * sizeof(float)};
   if (dry) return BP_OK;
-  if (!ws || ws_bytes < *need) return BP_EWORKSPACE;
+  if (!ws || ws_bytes < row->bytes) return BP_EWORKSPACE;
   a.ws = ws;
   hipLaunchKernelGGL(wgrad_c1_kernel<K>, dim3((unsigned)nblk), dim3(256), 0, st, a);
   BP_CHECK_LAUNCH();
   return BP_OK;
 }
 
-}  // namespace
-
 // BP_EUNSUPPORTED unless: stride 1, one produced channel (Y), and an instantiation below.
-int bp_wgrad_thin(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* ws,
-                  size_t ws_bytes, size_t* need, int* nsplit, int* cxp, int* cyp, hipStream_t st, bool dry) {
+int wgrad_thin(const WgradCall& c, float* ws, size_t ws_bytes, WgradRow* row, hipStream_t st, bool dry) {
+  const bp_conv* cv = c.cv;
+  const bp_view *X = c.X, *Y = c.Y;
   static const bool off = getenv("BP_NOTHIN") != nullptr;
   if (off || cv->stride != 1 || Y->c != 1) return BP_EUNSUPPORTED;
   ThinArgs a{};
   a.X = X->ptr; a.xh = X->h; a.xw = X->w; a.xcs = X->cstride; a.xco = X->coff; a.cx = X->c;
   a.Y = Y->ptr; a.yh = Y->h; a.yw = Y->w; a.ycs = Y->cstride; a.yco = Y->coff;
-  a.n = X->n; a.pad = cv->pad; a.pwx = pwx; a.pwy = pwy;
+  a.n = X->n; a.pad = cv->pad; a.pwx = c.pwx; a.pwy = c.pwy;
   a.xvec = bp_view_vec4(X) ? 1 : 0;
   if (X->c == 1) {
-    if (cv->k == 3) return launch_c1<3>(a, ws, ws_bytes, need, nsplit, cxp, cyp, st, dry);
-    if (cv->k == 5) return launch_c1<5>(a, ws, ws_bytes, need, nsplit, cxp, cyp, st, dry);
+    if (cv->k == 3) return launch_c1<3>(a, ws, ws_bytes, row, st, dry);
+    if (cv->k == 5) return launch_c1<5>(a, ws, ws_bytes, row, st, dry);
     return BP_EUNSUPPORTED;
   }
-  if (cv->k == 5 && X->c > 4 && X->c <= 8) return launch_cy1<5, 8, 16>(a, ws, ws_bytes, need, nsplit, cxp, cyp, st, dry);
+  if (cv->k == 5 && X->c > 4 && X->c <= 8) return launch_cy1<5, 8, 16>(a, ws, ws_bytes, row, st, dry);
   return BP_EUNSUPPORTED;
+}
+
+}  // namespace
+
+const WgradFamily& bp_wgrad_family_thin() {
+  static const WgradFamily f = {"thin", bp_wgrad_plan_of<wgrad_thin>, bp_wgrad_run_of<wgrad_thin>, false, false};
+  return f;
 }

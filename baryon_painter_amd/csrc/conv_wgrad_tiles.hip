@@ -20,15 +20,6 @@
 #include "kernels.hpp"
 #include <cstdlib>
 
-// Workgroup-count target of the next launches on this thread (0: the default).  bp_wgrad_mfma sets it for a launch that
-// runs on a side stream beside the data-gradient chain (BP_IMPL_SHARED): measured on the fiducial step, 512 workgroups
-// (two per CU, the best alone) is the WORST choice there -- 320 ... 448 and 640 ... 768 all give a shorter step, 448 the
-// shortest (43.4 -> 42.9 ms): a grid that does not fill every CU twice leaves room for the main chain's workgroups.
-static thread_local int t_wt_target = 0;
-void bp_wgrad_tiles_target(int target) { t_wt_target = target; }
-static thread_local bool t_wt_last_dma = false;
-bool bp_wgrad_tiles_last_dma() { return t_wt_last_dma; }
-
 namespace {
 
 typedef float v4f __attribute__((ext_vector_type(4)));
@@ -564,18 +555,18 @@ __global__ __launch_bounds__(256) void wgrad_tiles_dma_kernel(WtArgs a) {
 }
 
 template <int KHB, int KW, int S, int NTX, int NTY, int WX, int WY, int WK, int BH, bool DMA = false>
-int launch(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* ws,
-           size_t ws_bytes, size_t* need, int* nsplit_out, int* cxp, int* cyp, hipStream_t st, bool dry) {
+int launch(const WgradCall& c, float* ws, size_t ws_bytes, WgradRow* row, hipStream_t st, bool dry) {
   using Cfg = WtCfg<KHB, KW, S, NTX, NTY, WX, WY, WK, BH>;
   using Dm = WtDma<KHB, KW, S, NTX, NTY, WX, WY, WK, BH>;
-  t_wt_last_dma = DMA;
+  const bp_conv* cv = c.cv;
+  const bp_view *X = c.X, *Y = c.Y;
   static_assert(WK == 1 || (WX == 1 && WY == 1), "k-split variants own the whole channel block");
   static_assert(DMA || Cfg::LDS <= 64 * 1024, "LDS budget");
   static_assert(!DMA || Dm::LDS <= 80 * 1024, "LDS budget: two workgroups per CU");
   WtArgs a{};
   a.X = X->ptr; a.xh = X->h; a.xw = X->w; a.xcs = X->cstride; a.xco = X->coff; a.cx = X->c;
   a.Y = Y->ptr; a.yh = Y->h; a.yw = Y->w; a.ycs = Y->cstride; a.yco = Y->coff; a.cy = Y->c;
-  a.n = X->n; a.k = cv->k; a.pad = cv->pad; a.pwx = pwx; a.pwy = pwy; a.ws = ws;
+  a.n = X->n; a.k = cv->k; a.pad = cv->pad; a.pwx = c.pwx; a.pwy = c.pwy; a.ws = ws;
   a.ncxb = bp_ceil_div(X->c, Cfg::CXC);
   const int ncyb = bp_ceil_div(Y->c, Cfg::CYC);
   a.CXP = a.ncxb * Cfg::CXC;
@@ -585,22 +576,26 @@ int launch(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y,
   const int kyg = bp_ceil_div(cv->k, KHB);
   const int64_t ntiles = (int64_t)Y->n * a.tiles_x * a.tiles_y;
   const int64_t base = (int64_t)a.ncxb * ncyb * kyg;
-  // ~2 workgroups per CU alone; fewer when the launch shares the GPU with the data-gradient chain (bp_wgrad_tiles_target)
+  // ~2 workgroups per CU alone; fewer when the launch runs on a side stream beside the data-gradient chain (c.shared:
+  // BP_IMPL_SHARED).  Measured on the fiducial step, 512 workgroups (two per CU, the best alone) is the WORST choice
+  // there -- 320 ... 448 and 640 ... 768 all give a shorter step, 448 the shortest (43.4 -> 42.9 ms): a grid that does
+  // not fill every CU twice leaves room for the main chain's workgroups.
   static const int wt_target = getenv("BP_WT_TARGET") ? atoi(getenv("BP_WT_TARGET")) : 512;
+  static const int shared_target = getenv("BP_WT_SHARED_TARGET") ? atoi(getenv("BP_WT_SHARED_TARGET")) : 448;
   // (only launches of about a millisecond: a long one -- the CGAN's 256 -> 512 layers run 5 - 18 ms -- loses more to the
   //  uneven grid than the main chain gains: CGAN iteration 345.8 ms at 512, 348.7 at 448)
   const double flop = 2.0 * (double)Y->n * Y->h * Y->w * cv->k * cv->k * X->c * Y->c;
-  // (the target is set for the length of one bp_wgrad_mfma walk only, run or plan: the workspace queries never see it)
-  const int target = (t_wt_target > 0 && t_wt_target < wt_target && flop < 1.5e11) ? t_wt_target : wt_target;
+  // (the workspace queries ask un-shared: they size for the larger split count)
+  const int target = (c.shared && shared_target > 0 && shared_target < wt_target && flop < 1.5e11) ? shared_target : wt_target;
   int64_t ns = (target + base - 1) / base;
   if (ns > ntiles) ns = ntiles;
   if (ns < 1) ns = 1;
   if (ns > 65535) ns = 65535;
   a.nsplit = (int)ns;
-  *need = (size_t)a.nsplit * cv->k * cv->k * a.CYP * a.CXP * sizeof(float);
-  *nsplit_out = a.nsplit; *cxp = a.CXP; *cyp = a.CYP;
+  *row = WgradRow{DMA ? BP_WG_TILES_DMA : BP_WG_TILES, a.nsplit, a.CXP, a.CYP,
+                  (size_t)a.nsplit * cv->k * cv->k * a.CYP * a.CXP * sizeof(float)};
   if (dry) return BP_OK;
-  if (!ws || ws_bytes < *need) return BP_EWORKSPACE;
+  if (!ws || ws_bytes < row->bytes) return BP_EWORKSPACE;
   a.xvec = bp_view_vec4(X) ? 1 : 0;
   a.yvec = bp_view_vec4(Y) ? 1 : 0;
   dim3 grid((unsigned)(a.ncxb * ncyb), (unsigned)kyg, (unsigned)a.nsplit);
@@ -617,13 +612,11 @@ int launch(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y,
   return BP_OK;
 }
 
-}  // namespace
-
-// Returns BP_EUNSUPPORTED when no tap-blocked variant fits (caller falls back to conv_wgrad.hip).
-int bp_wgrad_tiles(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* ws,
-                   size_t ws_bytes, size_t* need, int* nsplit, int* cxp, int* cyp, hipStream_t st, bool dry) {
-  const int k = cv->k, s = cv->stride, cx = X->c, cy = Y->c;
-#define BP_WT(...) return launch<__VA_ARGS__>(cv, X, pwx, Y, pwy, ws, ws_bytes, need, nsplit, cxp, cyp, st, dry)
+// Returns BP_EUNSUPPORTED when no tap-blocked variant fits (the generic kernel of conv_wgrad.hip is next).
+int wgrad_tiles(const WgradCall& c, float* ws, size_t ws_bytes, WgradRow* row, hipStream_t st, bool dry) {
+  const bp_view *X = c.X, *Y = c.Y;
+  const int k = c.cv->k, s = c.cv->stride, cx = X->c, cy = Y->c;
+#define BP_WT(...) return launch<__VA_ARGS__>(c, ws, ws_bytes, row, st, dry)
   // LDS-DMA pipelined variants need 16-byte addressable views and whole channel quads
   static const bool no_dma = getenv("BP_WT_NODMA") != nullptr;
   const bool dma = !no_dma && bp_view_vec4(X) && bp_view_vec4(Y) && cx % 4 == 0 && cy % 4 == 0;
@@ -669,4 +662,11 @@ int bp_wgrad_tiles(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_
   if (k == 8 && s == 4) BP_WT(4, 8, 4, 1, 1, 1, 1, 4, 2);
 #undef BP_WT
   return BP_EUNSUPPORTED;
+}
+
+}  // namespace
+
+const WgradFamily& bp_wgrad_family_tiles() {
+  static const WgradFamily f = {"tiles", bp_wgrad_plan_of<wgrad_tiles>, bp_wgrad_run_of<wgrad_tiles>, false, false};
+  return f;
 }

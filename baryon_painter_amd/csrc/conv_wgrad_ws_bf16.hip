@@ -325,13 +325,11 @@ int wo_launch(const WoArgs& a, unsigned grid, hipStream_t st) {
   return BP_OK;
 }
 
-}  // namespace
-
-void bp_bf16_wgrad_ws_set(int v) { g_wo_override = v; }
-
-// Same contract as wb_launch (conv_wgrad_bf16.hip): BP_EUNSUPPORTED -> the tiled kernel.
-int bp_wgrad_ws_bf16(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* ws,
-                     size_t ws_bytes, size_t* need, int* nsplit, int* cxp, int* cyp, hipStream_t st, bool dry) {
+// BP_EUNSUPPORTED: not this kernel's layer.
+int wgrad_ws_bf16(const WgradCall& c, float* ws, size_t ws_bytes, WgradRow* row, hipStream_t st, bool dry) {
+  const bp_conv* cv = c.cv;
+  const bp_view *X = c.X, *Y = c.Y;
+  const PW &pwx = c.pwx, &pwy = c.pwy;
   if (!(g_wo_override < 0 ? wo_enabled() : g_wo_override != 0)) return BP_EUNSUPPORTED;
   if (cv->transposed || cv->k != 3 || cv->stride != 1 || cv->pad != 1 || cv->cin != WB_C || cv->cout != WB_C) return BP_EUNSUPPORTED;
   if (X->dtype != BP_BF16 || Y->dtype != BP_BF16 || X->c != WB_C || Y->c != WB_C || pwy.scale) return BP_EUNSUPPORTED;
@@ -345,10 +343,9 @@ int bp_wgrad_ws_bf16(const bp_conv* cv, const bp_view* X, const PW& pwx, const b
   wo_bands(X->n, X->h, strips ? strips : 1, &a.BR, &a.bands);
   const int64_t splits = (int64_t)X->n * a.bands * (strips ? strips : 1);
   if (splits * 4 + 32 > 0x7fffffff) return BP_EUNSUPPORTED;
-  *nsplit = (int)splits; *cxp = WB_C; *cyp = WB_C;
-  *need = (size_t)splits * 9 * WB_C * WB_C * sizeof(float);
+  *row = WgradRow{BP_WG_WS_BF16, (int)splits, WB_C, WB_C, (size_t)splits * 9 * WB_C * WB_C * sizeof(float)};
   if (dry) return BP_OK;
-  if (!ws || ws_bytes < *need) return BP_EWORKSPACE;
+  if (!ws || ws_bytes < row->bytes) return BP_EWORKSPACE;
   a.X = reinterpret_cast<const u16*>(X->ptr); a.x_cs = X->cstride; a.x_co = X->coff;
   a.Y = reinterpret_cast<const u16*>(Y->ptr); a.y_cs = Y->cstride; a.y_co = Y->coff;
   a.n = X->n; a.h = X->h; a.pwx = pwx; a.ws = ws; a.nsplit = (int)splits;
@@ -358,4 +355,14 @@ int bp_wgrad_ws_bf16(const bp_conv* cv, const bp_view* X, const PW& pwx, const b
   if (strips) return act ? wo_launch<4, true, true>(a, grid, st) : wo_launch<4, false, true>(a, grid, st);
   if (wo_G(X->w) == 4) return act ? wo_launch<4, true>(a, grid, st) : wo_launch<4, false>(a, grid, st);
   return act ? wo_launch<2, true>(a, grid, st) : wo_launch<2, false>(a, grid, st);
+}
+
+}  // namespace
+
+void bp_bf16_wgrad_ws_set(int v) { g_wo_override = v; }
+
+// (may_requalify: bp_set_option("bf16_wgrad_ws") may switch it off between the workspace query and the call)
+const WgradFamily& bp_wgrad_family_ws_bf16() {
+  static const WgradFamily f = {"ws_bf16", bp_wgrad_plan_of<wgrad_ws_bf16>, bp_wgrad_run_of<wgrad_ws_bf16>, false, true};
+  return f;
 }

@@ -239,13 +239,11 @@ int ww_launch(const WwArgs& a, unsigned grid, hipStream_t st) {
   return BP_OK;
 }
 
-}  // namespace
-
-void bp_f32_wgrad_ws_set(int v) { g_ww_override = v; }
-
-// Same contract as bp_wgrad_tiles (conv_wgrad_tiles.hip): BP_EUNSUPPORTED -> the next kernel in the chain.
-int bp_wgrad_ws_f32(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* ws,
-                    size_t ws_bytes, size_t* need, int* nsplit, int* cxp, int* cyp, hipStream_t st, bool dry) {
+// BP_EUNSUPPORTED: not this kernel's layer.
+int wgrad_ws_f32(const WgradCall& c, float* ws, size_t ws_bytes, WgradRow* row, hipStream_t st, bool dry) {
+  const bp_conv* cv = c.cv;
+  const bp_view *X = c.X, *Y = c.Y;
+  const PW &pwx = c.pwx, &pwy = c.pwy;
   if (!(g_ww_override < 0 ? ww_enabled() : g_ww_override != 0)) return BP_EUNSUPPORTED;
   if (cv->transposed || cv->k != 3 || cv->stride != 1 || cv->pad != 1 || cv->cin != WW_C || cv->cout != WW_C) return BP_EUNSUPPORTED;
   if (X->dtype != BP_F32 || Y->dtype != BP_F32 || X->c != WW_C || Y->c != WW_C || pwy.scale) return BP_EUNSUPPORTED;
@@ -257,10 +255,9 @@ int bp_wgrad_ws_f32(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp
   ww_bands(X->n, X->h, a.strips, &a.BR, &a.bands);
   const int64_t splits = (int64_t)X->n * a.bands * a.strips;
   if (splits * 4 > 0x7fffffff) return BP_EUNSUPPORTED;
-  *nsplit = (int)splits; *cxp = WW_C; *cyp = WW_C;
-  *need = (size_t)splits * 9 * WW_C * WW_C * sizeof(float);
+  *row = WgradRow{BP_WG_WS_F32, (int)splits, WW_C, WW_C, (size_t)splits * 9 * WW_C * WW_C * sizeof(float)};
   if (dry) return BP_OK;
-  if (!ws || ws_bytes < *need) return BP_EWORKSPACE;
+  if (!ws || ws_bytes < row->bytes) return BP_EWORKSPACE;
   a.X = X->ptr; a.x_cs = X->cstride; a.x_co = X->coff;
   a.Y = Y->ptr; a.y_cs = Y->cstride; a.y_co = Y->coff;
   a.n = X->n; a.h = X->h; a.pwx = pwx; a.ws = ws;
@@ -272,4 +269,14 @@ int bp_wgrad_ws_f32(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp
     case 2: return act ? ww_launch<2, true>(a, grid, st) : ww_launch<2, false>(a, grid, st);
     default: return act ? ww_launch<1, true>(a, grid, st) : ww_launch<1, false>(a, grid, st);
   }
+}
+
+}  // namespace
+
+void bp_f32_wgrad_ws_set(int v) { g_ww_override = v; }
+
+// (may_requalify: bp_set_option("f32_wgrad_ws") may switch it off between the workspace query and the call)
+const WgradFamily& bp_wgrad_family_ws_f32() {
+  static const WgradFamily f = {"ws_f32", bp_wgrad_plan_of<wgrad_ws_f32>, bp_wgrad_run_of<wgrad_ws_f32>, false, true};
+  return f;
 }

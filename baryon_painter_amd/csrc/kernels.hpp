@@ -1,6 +1,8 @@
 // Every host function that crosses a translation unit, declared once and grouped by the file that defines it, and the
-// records through which the dispatchers reach the kernel families.  Include after common.hpp.  Default arguments live
-// here only.
+// records through which the dispatchers reach the kernel families: ConvFamily (forward / data gradient; the order is
+// FAMILIES in conv_dispatch.hip) and WgradFamily (weight gradient; the order is F32_FAMILIES and BF16_FAMILIES in
+// conv_wgrad.hip).  A new family: write its record next to its kernels, declare its accessor here, insert it into the
+// table.  Include after common.hpp.  Default arguments live here only.
 #pragma once
 #include "common.hpp"
 
@@ -86,50 +88,84 @@ int bp_direct_gather(const ConvGeom& g, const WeightMap& wm, const bp_view* in, 
 int bp_direct_wgrad(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* dst,
                     hipStream_t st);
 
-// conv_wgrad.hip: the fp32 / bf16 weight gradient behind capi.hip, and its deferred reductions
-size_t bp_wgrad_mfma_workspace(const bp_conv* cv, const bp_view* X, const bp_view* Y);
-int bp_wgrad_mfma(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* dst,
-                  void* workspace, size_t workspace_bytes, hipStream_t st, bool shared, int32_t* plan = nullptr);
-size_t bp_wgrad_bf16_workspace(const bp_conv* cv, const bp_view* X, const bp_view* Y);
-int bp_wgrad_bf16_run(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* dst,
-                      void* workspace, size_t workspace_bytes, hipStream_t st, int32_t* plan = nullptr);
+// ---- weight gradient, fp32 and bf16: one record per kernel family (conv_wgrad.hip walks its two tables in priority
+// order).  A call: X is the tensor on the fine grid, Y the one on the coarse grid (conv_wgrad.hip), each with the
+// pointwise operand that lands on it; `shared`: the launch shares the GPU with another stream (BP_IMPL_SHARED).
+struct WgradCall {
+  const bp_conv* cv;
+  const bp_view* X; PW pwx;
+  const bp_view* Y; PW pwy;
+  bool shared;
+};
+// What a family plans for a call it accepts: the BP_WG_* value of the kernel that runs (a family may hold several
+// variants), its split count and workspace bytes.  Partial-sum kernels write ws[split][ky][kx][cyp][cxp]; the kernels that
+// reduce themselves report their grid as nsplit and cxp = cyp = 0.
+struct WgradRow {
+  int id, nsplit, cxp, cyp;
+  size_t bytes;
+};
+struct WgradFamily {
+  const char* name;
+  // is the call this family's layer, and if so its row: host arithmetic, no launch, pointers looked at for alignment only
+  bool (*plan)(const WgradCall& c, WgradRow* row);
+  // a call plan() accepted with `row`: partial sums into ws for conv_wgrad.hip to reduce in fixed order, or
+  // (reduces_itself) dW into dst
+  int (*run)(const WgradCall& c, const WgradRow& row, float* dst, void* ws, size_t ws_bytes, hipStream_t st);
+  bool reduces_itself;
+  // plan() may answer differently for the call than for its workspace query: the query passes no pointwise operand, and
+  // bp_set_option may switch between the two.  The workspace is sized for the families after it as well, up to the
+  // first acceptor without this flag.
+  bool may_requalify;
+};
+// Most partial-sum kernels answer both questions with one function -- `dry`: fill *row, launch nothing;
+// BP_EUNSUPPORTED: not this kernel's layer -- so that the plan and the launch are the same arithmetic.
+using WgradPartialFn = int(const WgradCall& c, float* ws, size_t ws_bytes, WgradRow* row, hipStream_t st, bool dry);
+template <WgradPartialFn* FN>
+bool bp_wgrad_plan_of(const WgradCall& c, WgradRow* row) { return FN(c, nullptr, 0, row, nullptr, true) == BP_OK; }
+template <WgradPartialFn* FN>
+int bp_wgrad_run_of(const WgradCall& c, const WgradRow&, float*, void* ws, size_t ws_bytes, hipStream_t st) {
+  WgradRow row;
+  return FN(c, reinterpret_cast<float*>(ws), ws_bytes, &row, st, false);
+}
+
+// fp32.  conv_stem.hip: the 3 -> 16 k5 stem; conv_wgrad_flat.hip: the 16 -> 8 k7 head layer and the thin stride-2 k4
+// layers (16 channels at full resolution, 32 at half) -- these three reduce their own partial sums
+const WgradFamily& bp_wgrad_family_stem();
+const WgradFamily& bp_wgrad_family_flat();
+const WgradFamily& bp_wgrad_family_flat_s2();
+// conv_wgrad_ws_f32.hip: output-stationary kernel of the 128 <-> 128 k3 trunk layers
+const WgradFamily& bp_wgrad_family_ws_f32();
+void bp_f32_wgrad_ws_set(int v);
+// conv_enc.hip: the k8 stride-4 encoder layer
+const WgradFamily& bp_wgrad_family_enc();
+// conv_wgrad_thin.hip: one-channel tails (BP_WG_THIN_C1, BP_WG_THIN_CY1)
+const WgradFamily& bp_wgrad_family_thin();
+// conv_wgrad_small.hip: the tap-packed few-channel kernel, and the kernel itself for conv_wgrad.hip's chunked family
+const WgradFamily& bp_wgrad_family_small();
+WgradPartialFn bp_wgrad_small;
+// conv_wgrad_tiles.hip: the tap-blocked kernels (BP_WG_TILES, BP_WG_TILES_DMA)
+const WgradFamily& bp_wgrad_family_tiles();
+// bf16.  conv_wgrad_bf16.hip: the heads' k7 layer, the generator's k5 stem, the heads' 8 -> 1 k5 tail, the tiled kernels
+const WgradFamily& bp_wgrad_family_bf16_wf();
+const WgradFamily& bp_wgrad_family_bf16_sf();
+const WgradFamily& bp_wgrad_family_bf16_wh();
+const WgradFamily& bp_wgrad_family_bf16_tiled();
+// conv_wgrad_ws_bf16.hip: output-stationary kernel of the 128 <-> 128 k3 trunk layers
+const WgradFamily& bp_wgrad_family_ws_bf16();
+void bp_bf16_wgrad_ws_set(int v);
+
+// conv_wgrad.hip: the two tables and their walk behind capi.hip, the fixed-order reduction and its deferral
+struct WgradSelection {
+  const WgradFamily* family;      // the first family that accepts the call, and its row
+  WgradRow row;
+  size_t ws_bytes;                // what a workspace query for this call answers (see WgradFamily::may_requalify)
+};
+int bp_wgrad_select(bool bf16, const WgradCall& c, WgradSelection* s);      // BP_OK / BP_EUNSUPPORTED
+int bp_wgrad_run(const WgradSelection& s, const WgradCall& c, float* dst, void* workspace, size_t workspace_bytes,
+                 hipStream_t st);
 void bp_wgrad_private_ws(bool on);
 int bp_wgrad_defer_begin_impl();
 int bp_wgrad_defer_flush_impl(hipStream_t st, int end);
-
-// Weight-gradient kernels that write partial sums ws[split][ky][kx][cy][cx] for conv_wgrad.hip to reduce in fixed order
-// share one signature: *need bytes of ws, *nsplit partial images of padded channel counts *cxp x *cyp; `dry`: fill those,
-// launch nothing; BP_EUNSUPPORTED: not this kernel's layer.  Each is defined in the file of its name (bp_wgrad_enc:
-// conv_enc.hip, bp_wgrad_bf16: conv_wgrad_bf16.hip).
-using WgradPartialFn = int(const bp_conv* cv, const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* ws,
-                           size_t ws_bytes, size_t* need, int* nsplit, int* cxp, int* cyp, hipStream_t st, bool dry);
-WgradPartialFn bp_wgrad_ws_f32, bp_wgrad_enc, bp_wgrad_thin, bp_wgrad_small, bp_wgrad_tiles, bp_wgrad_bf16, bp_wgrad_ws_bf16;
-void bp_f32_wgrad_ws_set(int v);        // conv_wgrad_ws_f32.hip
-void bp_bf16_wgrad_ws_set(int v);       // conv_wgrad_ws_bf16.hip
-void bp_wgrad_tiles_target(int target); // conv_wgrad_tiles.hip
-// which kernel the last bp_wgrad_tiles / bp_wgrad_bf16 call on this thread chose (for bp_conv_backward_weight_plan)
-bool bp_wgrad_tiles_last_dma();         // conv_wgrad_tiles.hip: the LDS-DMA variant
-int bp_wgrad_bf16_last_family();        // conv_wgrad_bf16.hip: BP_WG_BF16_* / BP_WG_WS_BF16
-
-// Weight-gradient kernels that reduce their own partial sums.
-// conv_stem.hip: weight gradient of the 3 -> 16 k5 stem
-bool bp_stem_wgrad_ok(const bp_conv* cv, const bp_view* X, const bp_view* Y, const PW& pwy, const float* dbias);
-size_t bp_stem_wgrad_workspace(const bp_view* X);
-int bp_stem_wgrad_grid(const bp_view* X);
-int bp_stem_wgrad(const bp_view* X, const PW& pwx, const bp_view* Y, float* dst, void* workspace, size_t workspace_bytes,
-                  hipStream_t st);
-// conv_wgrad_flat.hip: weight gradient of the 16 -> 8 k7 head layer
-bool bp_wgrad_flat_ok(const bp_conv* cv, const bp_view* X, const bp_view* Y, const PW& pwy);
-size_t bp_wgrad_flat_workspace(const bp_view* X);
-int bp_wgrad_flat_grid(const bp_view* X, bool shared);
-int bp_wgrad_flat(const bp_view* X, const PW& pwx, const bp_view* Y, float* dst, void* workspace, size_t workspace_bytes,
-                  hipStream_t st, bool shared);
-// ... and of the thin stride-2 k4 layers (16 channels at full resolution, 32 at half)
-bool bp_wgrad_flat_s2_ok(const bp_conv* cv, const bp_view* X, const bp_view* Y, const PW& pwx, const PW& pwy);
-size_t bp_wgrad_flat_s2_workspace(const bp_view* Y);
-int bp_wgrad_flat_s2_grid(const bp_view* Y, bool shared);
-int bp_wgrad_flat_s2(const bp_view* X, const PW& pwx, const bp_view* Y, const PW& pwy, float* dst, void* workspace,
-                     size_t workspace_bytes, hipStream_t st, bool shared);
 
 // conv_bf16.hip: the bf16 gather entry points behind capi.hip
 bool bp_bf16_igemm_ok(const ConvGeom& g, const bp_view* in, const bp_view* out);

@@ -1,7 +1,7 @@
 """Convolution geometries for the dispatcher sweep, and their float64 reference (plain module, no test in here).
 
 The convolution entry points of include/bp_hip.h take any bp_conv on any valid view; three host-side heuristics
-(igemm_config / bp_igemm_run, b_config, bp_wgrad_mfma) pick a kernel and its tiling from the geometry alone.  cases()
+(igemm_config / bp_igemm_run, b_config, bp_wgrad_select) pick a kernel and its tiling from the geometry alone.  cases()
 lists small tensors at many geometries, in two strata:
 
   grid      every k in 1..9, stride in 1..4, pad in {0, (k-1)//2, k//2, k-1, k+1}, both forms and, for the transposed

@@ -1,7 +1,7 @@
 """GPU: every convolution implementation behind the C ABI, swept over the geometries of tests/conv_sweep.py.
 
 The operator tests run the kernels at the model's own layers.  The dispatcher (igemm_config / bp_igemm_run, b_config,
-bp_wgrad_mfma) picks kernels from the geometry alone, and these paths are reachable through the ABI without being one
+bp_wgrad_select) picks kernels from the geometry alone, and these paths are reachable through the ABI without being one
 of those layers -- the gaps the sweep's targeted cases are numbered after:
   1. the plain igemm_kernel for wide layers (a view that is not 16-byte addressable drops a DMA layer to it);
   2. channel counts off the 4 / 8 / 16 grids: zero-padded chunk tails, the `co < cout` masks, pixel packing COP 4 and 8;

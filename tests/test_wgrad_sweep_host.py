@@ -5,7 +5,10 @@ does is host arithmetic -- the kernel the dispatcher picks, its cap and its tile
 the plan names the family each case is listed under, its nsplit is min(units, cap) of the module's table, the case is in
 its regime, its integer data stay in the exact range, and the plan never needs more than the workspace query grants.
 tests/golden/wgrad_plan.json records every plan row; a retuned heuristic shows here first and the case is re-picked.
+tests/golden/wgrad_dispatch.json records the same queries over the conv sweep and the models' layers, under every
+environment switch that moves a layer between the weight-gradient families.
 """
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
@@ -15,6 +18,7 @@ from baryon_painter_amd import _lib as L
 
 import conv_sweep as S
 import wgrad_sweep as W
+from golden import make_wgrad_dispatch as MD
 from golden import make_wgrad_plan as M
 
 QUERY = {q[0]: i for i, q in enumerate(M.QUERIES)}
@@ -136,6 +140,41 @@ def test_plan_bytes_never_exceed_the_workspace_query(rows):
             need = ns * PART[name] * 4 + -(-ns // 32) * PART[name] * 8 if name in PART else ns * k * k * cxp * cyp * 4
             assert 0 < ws and need <= ws, (W.case_id(e), q[0], name, need, ws)
             assert (ns == 0) == (name == "direct")
+
+
+def test_dispatch_rows_equal_the_recorded_table_under_every_switch():
+    """tests/golden/wgrad_dispatch.json: the same queries over the conv sweep and the models' layers, under the default
+    setting and under every environment switch that moves a weight-gradient layer between families."""
+    doc = MD.load()
+    tagged = MD.cases()
+    assert doc["queries"] == [q[0] for q in MD.QUERIES] and len(doc["default"]) == len(tagged)
+    assert MD.D.load()["tags"] == [t for t, _ in tagged]          # (the cases are dispatch_table.json's)
+    assert set(doc["settings"]) == set(MD.SWITCHES)
+    want = MD.unpack(doc)
+    # (the switches are read once into statics: one child process per setting, all at once)
+    with ThreadPoolExecutor(max_workers=len(MD.SETTINGS)) as ex:
+        got = dict(zip(MD.SETTINGS, ex.map(MD.compute_setting, MD.SETTINGS)))
+    wrong = []
+    for s in MD.SETTINGS:
+        assert len(got[s]) == len(want[s]) == len(tagged)
+        for (tag, case), g, w in zip(tagged, got[s], want[s]):
+            wrong += ["%s %s %s [%s]: got %s, recorded %s" % (tag, case, q[0], s or "default", a, b)
+                      for q, a, b in zip(MD.QUERIES, g, w) if a != b]
+            # the plan never needs more than the workspace query grants
+            k = case[3]
+            for q, (rc, fam, ns, cxp, cyp, ws) in zip(MD.QUERIES, g):
+                if rc != L.BP_OK:
+                    assert fam == -1 and ns == 0, (tag, q[0], s)
+                    continue
+                name = L.WGRAD_FAMILIES[fam]
+                need = ns * PART[name] * 4 + -(-ns // 32) * PART[name] * 8 if name in PART else ns * k * k * cxp * cyp * 4
+                assert 0 < ws and need <= ws, (tag, q[0], s, name, need, ws)
+    print("\n%d settings x %d cases x %d queries compared" % (len(MD.SETTINGS), len(tagged), len(MD.QUERIES)))
+    assert not wrong, "%d rows differ:\n%s" % (len(wrong), "\n".join(wrong[:40]))
+    # the default setting reaches every family: the table cannot silently lose one
+    for table in (got, want):
+        reached = {L.WGRAD_FAMILIES[r[1]] for rows_ in table[""] for r in rows_ if r[0] == L.BP_OK}
+        assert reached == set(L.WGRAD_FAMILIES) and len(reached) == 18, sorted(set(L.WGRAD_FAMILIES) - reached)
 
 
 @pytest.mark.parametrize("case", [(0, 5, 7, 3, 1, 1, 0, 2, 9, 11), (0, 3, 4, 4, 2, 0, 0, 2, 11, 13), (1, 4, 3, 5, 3, 2, 1, 2, 5, 6)],

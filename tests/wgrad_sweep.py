@@ -92,7 +92,7 @@ UNREACHABLE = {
     "BP_WS(5, 1, 1, 1, 16)": "1 -> 1 k5 is thin_c1's layer",
 }
 for _n in ("ws_k9s1_16x1", "ws_k9s1_16x2", "ws_k9s1_1x16", "ws_k9s1_2x16"):
-    INST["chunk_" + _n[3:]] = INST[_n]._replace(family="small_chunked", where=INST[_n].where + " per 16-channel chunk (conv_wgrad.hip wgrad_chunked)")
+    INST["chunk_" + _n[3:]] = INST[_n]._replace(family="small_chunked", where=INST[_n].where + " per 16-channel chunk (conv_wgrad.hip chunked_run)")
 
 
 def _wb(name, khb, kw, s, ntx, nty, wx, wy, bh, wt=False):
@@ -118,8 +118,8 @@ _wb("wb_k5s1", 5, 5, 1, 1, 1, 1, 1, 8)
 _wb("wb_k7s1", 4, 7, 1, 1, 1, 1, 1, 8)
 
 INST.update({
-    "general": Inst("general", 16, 8, ("general", 2048), "staged through LDS, no prefetch", "conv_wgrad.hip WG_BW x WG_BH, wgrad_plan"),
-    "enc": Inst("enc", 16, 2, ("fixed", 768), "persistent over tiles", "conv_enc.hip bp_wgrad_enc: 16 x EW_R, cap 768"),
+    "general": Inst("general", 16, 8, ("general", 2048), "staged through LDS, no prefetch", "conv_wgrad.hip WG_BW x WG_BH, wgrad_general"),
+    "enc": Inst("enc", 16, 2, ("fixed", 768), "persistent over tiles", "conv_enc.hip wgrad_enc: 16 x EW_R, cap 768"),
     "thin_cy1": Inst("thin_cy1", 32, 16, ("fixed", 1280), "next tile's loads issued before the k-steps",
                      "conv_wgrad_thin.hip launch_cy1<5, 8, 16>: Cy1Cfg::BW x BH, cap 1280"),
     "thin_c1": Inst("thin_c1", 4, 16, ("quads",), "one pass, 256 quads of 4 pixels x C1_BR rows per split",
@@ -130,11 +130,11 @@ INST.update({
                     "conv_wgrad_flat.hip s2::SW x s2::SH, s2::grid_of"),
     "ws_f32": Inst("ws_f32", 0, 0, ("bands",), "output-stationary, one band of rows per split", "conv_wgrad_ws_f32.hip ww_bands"),
     "ws_bf16": Inst("ws_bf16", 0, 0, ("bands",), "output-stationary, one band of rows per split", "conv_wgrad_ws_bf16.hip wo_bands"),
-    "bf16_wf": Inst("bf16_wf", 64, 16, ("fixed", 512), "persistent, next tile in registers", "conv_wgrad_bf16.hip WF_TW x WF_TH, wf_launch"),
-    "bf16_sf": Inst("bf16_sf", 64, 16, ("fixed", 512), "persistent, next tile in registers", "conv_wgrad_bf16.hip SF_TW x SF_TH, sf_launch"),
-    "bf16_wh": Inst("bf16_wh", 64, 16, ("fixed", 1024), "persistent, next tile in registers", "conv_wgrad_bf16.hip WH_TW x WH_TH, wh_launch"),
+    "bf16_wf": Inst("bf16_wf", 64, 16, ("fixed", 512), "persistent, next tile in registers", "conv_wgrad_bf16.hip WF_TW x WF_TH, wgrad_wf"),
+    "bf16_sf": Inst("bf16_sf", 64, 16, ("fixed", 512), "persistent, next tile in registers", "conv_wgrad_bf16.hip SF_TW x SF_TH, wgrad_sf"),
+    "bf16_wh": Inst("bf16_wh", 64, 16, ("fixed", 1024), "persistent, next tile in registers", "conv_wgrad_bf16.hip WH_TW x WH_TH, wgrad_wh"),
 })
-SHARED_TARGET = 448                    # conv_wgrad.hip SharedTarget: tap-blocked fp32 launches below 1.5e11 flop
+SHARED_TARGET = 448                    # conv_wgrad_tiles.hip shared_target: tap-blocked fp32 launches below 1.5e11 flop
 SHARED_FLAT_GRID = 256                 # conv_wgrad_flat.hip shared_grid: one workgroup per CU (256 without a device, too)
 # What a view with odd channel stride and offset falls to (a record not named here serves both kinds of view)
 ODD = {"wt_k3s1_64x64_dma": "wt_k3s1_64x64", "wt_k4s2_32x64_dma": "wt_k4s2_32x64", "wt_k4s2_16x32_dma": "wt_k4s2_16x32",
